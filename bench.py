@@ -2,7 +2,7 @@
 """Benchmark of the NMN hot path (BASELINE.json metric: questions/sec on AGQA2-shaped inputs).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode train|infer] [--features bf16|f32]
-                    [--supervision] [--dropout P]
+                    [--supervision] [--dropout P] [--dump-outputs DIR] [--full [--no-extras] [--no-cpu-baseline]]
 
 Default = BASELINE.json configs[1] ("AGQA2 full train, I3D rgb+flow [T=64,2048] feats, bf16, 1 MI355X"): one step = one
 optimizer step over a window of B synthetic questions per GPU -- program packing, plan build, encode_video,
@@ -16,7 +16,12 @@ Appendix B, inputs resident in HBM before the timed region.  For N > 1 the drive
 torch.distributed.run; questions shard across ranks, timing is barrier-bracketed, the max over ranks is reported.
 Rank 0 prints ONE JSON line.
 
-Objects on the line besides the contract's fields:
+A plain run sets up, warms up, times the K steps and prints the line: `value` (questions/s), `ms_per_step` and the workload's
+description, plus `roofline_hbm` / `path_tflops` (arithmetic on `value`).  `--dump-outputs DIR` writes what the last timed step
+returned to its caller as DIR/<name>.npy (float32, see dump_outputs) before anything else runs.  Everything else the benchmark
+measures or checks runs only with `--full` (`--no-extras` / `--no-cpu-baseline` then drop parts of it):
+
+Objects on the line with --full:
   roofline      the dominant kernel -- the video bi-LSTM input projection, a plane GEMM (csrc/gemm_planes.hip) on the
                 stored bf16 features with M = B*T, N = 8*Hh (both directions in one launch), K = V -- timed live with
                 events on its launch stream: algorithmic 2MNK / launch time against the 2.5 PFLOP/s dense bf16 MFMA
@@ -258,6 +263,42 @@ def cpu_model():
     return 'unknown'
 
 
+DUMP_PARAM_SAMPLE = 1 << 16        # elements kept per parameter tensor larger than this (fixed seeded sample)
+DUMP_ROWS_SAMPLE = 1 << 14         # questions kept when a batch has more than this (fixed seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _seeded_sample(n, k):
+    """sorted indices of a fixed k-element sample of range(n): the same for every run and build with the same n"""
+    return np.sort(np.random.default_rng(0).choice(n, k, replace=False)) if n > k else None
+
+
+def dump_outputs(out_dir, model, config, loss, res):
+    """What the last timed step handed its caller, as DIR/<name>.npy in float32: `logits` [B, A] and `pred` [B] of the batch
+    (BatchResult), and for a training step `loss` [B] (per-question decoder CE) and the parameters after the step's Adam update
+    (`param.<state_dict key>`, flattened).  A parameter above DUMP_PARAM_SAMPLE elements, and a batch above DUMP_ROWS_SAMPLE
+    questions, is kept as the fixed seeded sample _seeded_sample(size, limit).  About 12 MB at the defaults."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = _seeded_sample(res.logits.shape[0], DUMP_ROWS_SAMPLE)
+    arrays = {}
+    for name, t in (('logits', res.logits), ('pred', res.pred), ('loss', loss)):
+        if t is not None:
+            a = t.detach().cpu().numpy()
+            arrays[name] = a if rows is None else a[rows]
+    if loss is not None:
+        state = model.state_dict()
+        for key in spec.state_dict_keys(config):
+            a = state[key].detach().cpu().numpy().reshape(-1)
+            idx = _seeded_sample(a.size, DUMP_PARAM_SAMPLE)
+            arrays['param.' + key] = a if idx is None else a[idx]
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, 'output dump of %d bytes exceeds %d' % (total, DUMP_MAX_BYTES)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -269,10 +310,16 @@ def main():
     ap.add_argument('--features', choices=['bf16', 'f32'], default='bf16', help='storage format of the clip features (configs[1]: bf16)')
     ap.add_argument('--supervision', action='store_true', help='configs[4]: gold intermediates + every per-module loss inside the timed step')
     ap.add_argument('--dropout', type=float, default=0.0, help='nn.Dropout p of the training step (the reference trains with 0.25; parity is defined at 0)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also measure and check everything besides the headline: rooflines, the CPU baseline '
+                    'and oracle comparison, other modes, sizes and configurations')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and the oracle comparison')
     ap.add_argument('--native-allreduce', action='store_true', help='N > 1: the gradient all-reduce through the C ABI (stair_allreduce_grads, RCCL from libstair_hip.so) instead of torch.distributed')
-    ap.add_argument('--no-extras', action='store_true', help='skip the supplementary figures (clean kernel profiles)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the supplementary figures (clean kernel profiles)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    extras_on = args.full and not args.no_extras
 
     from stair_amd import launch
     if args.gpus > 1 and not launch.launched_as_rank():
@@ -337,7 +384,7 @@ def main():
         return out
 
     trainer = None
-    gold_qs = gold_questions(qs) if (args.supervision or not args.no_extras) and args.mode == 'train' else None
+    gold_qs = gold_questions(qs) if (args.supervision or extras_on) and args.mode == 'train' else None
     # the contrastive classes of the whole job, one order on every rank: pools of a data-parallel step are then summed on the device
     class_table = L.ClassTable.from_questions(gold_qs, world) if gold_qs is not None else None
     # the loader's collate step: the batch's gold intermediates as flat arrays (losses.GoldBatch), built once per batch outside the
@@ -359,12 +406,12 @@ def main():
     gc.freeze()
 
     def run_step(nq=B, supervised=False):
-        """one pass over the first nq questions of the rank's batch"""
+        """one pass over the first nq questions of the rank's batch: (per-question decoder CE or None, BatchResult)"""
         if trainer is not None:
             # every rank holds nq questions: the window size is known, so the step needs no size exchange (and no host sync)
             return trainer.step(programs[:nq], spans[:nq], video[:nq], question[:off[nq]], q_lens[:nq], answers[:nq],
-                                global_batch=nq * world, questions=gold_batch(nq) if supervised else None)[1]
-        return model.run_programs(programs[:nq], spans[:nq], video[:nq], question[:off[nq]], q_lens[:nq])
+                                global_batch=nq * world, questions=gold_batch(nq) if supervised else None)
+        return None, model.run_programs(programs[:nq], spans[:nq], video[:nq], question[:off[nq]], q_lens[:nq])
 
     def barrier():
         if world > 1:
@@ -384,12 +431,14 @@ def main():
     if trainer is not None and world > 1:
         trainer.allreduce_events = []
         trainer.allreduce_late_events = []
-    elapsed, res = timed(lambda: run_step(B, args.supervision), args.steps, args.warmup)
+    elapsed, (loss, res) = timed(lambda: run_step(B, args.supervision), args.steps, args.warmup)
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     qps = B * args.steps * world / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, config, loss, res)
 
     extras = {}
     if world > 1:
@@ -424,7 +473,7 @@ def main():
             trainer.allreduce_late_events = None
             if trainer.comm is not None:
                 extras['rccl_ranks_native_comm'] = trainer.comm.ranks()[1]
-        if trainer is not None:
+        if trainer is not None and args.full:
             # BASELINE configs[2]: "AGQA2 train DP=8 over xGMI, RCCL grad all-reduce, global batch 1024" = 1024 / N questions per GPU
             # per step (128 at N = 8), the latency-bound regime; same step, same collectives, smaller window
             nq2 = max(1, min(B, 1024 // world))
@@ -442,7 +491,7 @@ def main():
                 'allreduce_exposed_ms_per_step': exposed_ms(trainer.allreduce_late_events[-k2:]),
                 'note': 'BASELINE configs[2] (global batch 1024 over N GPUs); the headline `value` is configs[1]\'s 2048 questions per GPU per step'}
             trainer.allreduce_events = trainer.allreduce_late_events = None
-        if trainer is not None and not args.no_extras:
+        if trainer is not None and extras_on:
             # Supplementary data-parallel legs.  Every rank issues the SAME sequence of torch collectives whatever happens inside a
             # leg (a rank that fails locally records the error and still takes part), so a local failure cannot hang the job.
             if not args.supervision:
@@ -490,7 +539,7 @@ def main():
                                                   'bitwise_equal_to_torch_allreduce': bool(same.item() == 1.0)}
                 else:
                     extras['native_allreduce'] = {'error': err or 'the native communicator failed on another rank'}
-    if not args.no_extras and world == 1:
+    if extras_on and world == 1:
         # ---- forward-only rate, shared clips, host-fed pipeline (SURVEY 8d "a second figure including H2D") ----
         dt, r_inf = timed(lambda: model.run_programs(programs, spans, video, question, q_lens), 3, 1)
         extras['inference_questions_per_s_per_gpu'] = round(3 * B / dt, 1)
@@ -644,11 +693,6 @@ def main():
             del v2, vf
 
     if rank == 0:
-        gemm_ms, (Mg, Ng, Kg), kname = time_dominant_kernel(model, B, T, device, args.features)
-        gemm_flop = 2.0 * Mg * Ng * Kg
-        achieved = gemm_flop / (gemm_ms * 1e-3) / 1e12            # ALGORITHMIC flops (2MNK) per second
-        nprod = 2 if args.features == 'bf16' else 3
-        traffic, tnote = pmc_traffic(Mg, Ng, Kg) if args.features == 'bf16' else (None, 'fp32-feature kernel: see profiles/r01_g_pmc_dominant_t256.json')
         mode_txt = ('AGQA2 full train (BASELINE.json configs[%s]): I3D-like [T=%d,V=%d] features stored in %s, H=512, A=172, 8 program forms, %s, '
                     'one Adam step per window' % ('4' if args.supervision else '1', T, config['video_size'], args.features,
                                                   'decoder CE + per-module intermediate losses' if args.supervision else 'decoder CE loss')
@@ -667,12 +711,6 @@ def main():
                        'encoder_projections_ahead_of_plan': bool(model.early_projection),
                        'parallelism': ('dp%d (questions sharded round-robin, one flat fp32 gradient all-reduce per step, touched mask in the same bucket)'
                                        if args.mode == 'train' else 'dp%d (questions sharded, no collective)') % world},
-            'roofline': {'bound': 'mfma', 'kernel': '%s, M=%d N=%d K=%d' % (kname, Mg, Ng, Kg),
-                         'achieved': round(achieved, 2), 'peak': BF16_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                         'frac': round(achieved / BF16_MFMA_PEAK_TFLOPS, 4), 'traffic': traffic, 'traffic_note': tnote,
-                         'launch_ms': round(gemm_ms, 4),
-                         'note': 'achieved = algorithmic 2MNK / launch time against the dense bf16 MFMA peak; the kernel executes %d bf16 MFMAs per '
-                                 'algorithmic product by design (executed %.0f TFLOP/s = %.3f of peak)' % (nprod, nprod * achieved, nprod * achieved / BF16_MFMA_PEAK_TFLOPS)},
             'roofline_hbm': {'bound': 'hbm', 'scope': 'whole path, algorithmic bytes x q/s (per GPU)',
                              'achieved': round(ALGO_BYTES_PER_QUESTION * qps / world / 1e9, 2), 'peak': HBM_PEAK_GBS,
                              'unit': 'GB/s', 'frac': round(ALGO_BYTES_PER_QUESTION * qps / world / 1e9 / HBM_PEAK_GBS, 5),
@@ -680,24 +718,36 @@ def main():
             'path_tflops': round(ALGO_FLOP_PER_QUESTION * (3.0 if args.mode == 'train' else 1.0) * qps / world / 1e12, 2),
         }
         line.update(extras)
-        # what the matrix pipes of THIS device sustain on random operands (back-to-back MFMAs from registers, no memory): the chip
-        # holds its clock well under 2.4 GHz under such a load, so this -- not the datasheet's 2.5 PFLOP/s -- is the ceiling of a
-        # kernel's EXECUTED flop rate here; `roofline.peak` stays the datasheet figure
-        try:
-            import ctypes as C
-            from stair_amd._lib import lib as _lib, check as _check
-            tf = C.c_double(0.0)
-            _check(_lib.stair_mfma_probe(20000, 3, C.byref(tf), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-            ex = nprod * achieved
-            line['roofline']['sustained_mfma_probe'] = {
-                'TFLOP/s': round(tf.value, 1), 'frac_of_datasheet_peak': round(tf.value / BF16_MFMA_PEAK_TFLOPS, 4),
-                'kernel_executed_over_sustained': round(ex / tf.value, 4),
-                'note': 'stair_mfma_probe: v_mfma_f32_32x32x16_bf16 back to back from registers on every CU (2 waves per SIMD), random '
-                        'operands, 3 launches of ~5 ms after a warm-up, same process and device as the line; the dominant kernel executes '
-                        '%.0f TFLOP/s of MFMAs = %.2f of what the pipes sustain' % (ex, ex / tf.value)}
-        except Exception as e:
-            line['roofline']['sustained_mfma_probe'] = {'error': '%s: %s' % (type(e).__name__, str(e)[:120])}
-        if not args.no_cpu_baseline and world == 1:        # the CPU leg runs on rank 0 at N=1 only
+        if args.full:
+            gemm_ms, (Mg, Ng, Kg), kname = time_dominant_kernel(model, B, T, device, args.features)
+            gemm_flop = 2.0 * Mg * Ng * Kg
+            achieved = gemm_flop / (gemm_ms * 1e-3) / 1e12            # ALGORITHMIC flops (2MNK) per second
+            nprod = 2 if args.features == 'bf16' else 3
+            traffic, tnote = pmc_traffic(Mg, Ng, Kg) if args.features == 'bf16' else (None, 'fp32-feature kernel: see profiles/r01_g_pmc_dominant_t256.json')
+            line['roofline'] = {'bound': 'mfma', 'kernel': '%s, M=%d N=%d K=%d' % (kname, Mg, Ng, Kg),
+                                'achieved': round(achieved, 2), 'peak': BF16_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                                'frac': round(achieved / BF16_MFMA_PEAK_TFLOPS, 4), 'traffic': traffic, 'traffic_note': tnote,
+                                'launch_ms': round(gemm_ms, 4),
+                                'note': 'achieved = algorithmic 2MNK / launch time against the dense bf16 MFMA peak; the kernel executes %d bf16 MFMAs per '
+                                        'algorithmic product by design (executed %.0f TFLOP/s = %.3f of peak)' % (nprod, nprod * achieved, nprod * achieved / BF16_MFMA_PEAK_TFLOPS)}
+            # what the matrix pipes of THIS device sustain on random operands (back-to-back MFMAs from registers, no memory): the chip
+            # holds its clock well under 2.4 GHz under such a load, so this -- not the datasheet's 2.5 PFLOP/s -- is the ceiling of a
+            # kernel's EXECUTED flop rate here; `roofline.peak` stays the datasheet figure
+            try:
+                import ctypes as C
+                from stair_amd._lib import lib as _lib, check as _check
+                tf = C.c_double(0.0)
+                _check(_lib.stair_mfma_probe(20000, 3, C.byref(tf), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                ex = nprod * achieved
+                line['roofline']['sustained_mfma_probe'] = {
+                    'TFLOP/s': round(tf.value, 1), 'frac_of_datasheet_peak': round(tf.value / BF16_MFMA_PEAK_TFLOPS, 4),
+                    'kernel_executed_over_sustained': round(ex / tf.value, 4),
+                    'note': 'stair_mfma_probe: v_mfma_f32_32x32x16_bf16 back to back from registers on every CU (2 waves per SIMD), random '
+                            'operands, 3 launches of ~5 ms after a warm-up, same process and device as the line; the dominant kernel executes '
+                            '%.0f TFLOP/s of MFMAs = %.2f of what the pipes sustain' % (ex, ex / tf.value)}
+            except Exception as e:
+                line['roofline']['sustained_mfma_probe'] = {'error': '%s: %s' % (type(e).__name__, str(e)[:120])}
+        if args.full and not args.no_cpu_baseline and world == 1:        # the CPU leg runs on rank 0 at N=1 only
             # the box gives one GPU a 16-core CPU share; more ATen threads than that only thrash
             ncores = min(16, len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1))
             model.load_state_dict({k: torch.from_numpy(weights[k].copy()) for k in spec.state_dict_keys(config)})
