@@ -703,7 +703,7 @@ int stair_loss_head(int32_t nout, const float *vec, float *d_vec, const int32_t 
                     float *loss, stair_stream stream);
 /* Contrastive CE of Filter / ToAction / Superlative (:113-125) with the per-window class pooling of :388-406:
  * pred = L2Normalize(vec[slot[i]]); logits over class reps G[win_start[i] .. +win_cnt[i]) ; positive row pos[i]
- * (absolute row of G).  max_classes = max(win_cnt). */
+ * (absolute row of G).  max_classes = max(win_cnt); 3 max_classes + H floats must fit in 60 KB of LDS (else an error). */
 int stair_loss_contrastive(const float *vec, float *d_vec, const int32_t *slot, const int32_t *pos,
                            const int32_t *win_start, const int32_t *win_cnt, const float *G, int32_t n, int32_t H,
                            int32_t max_classes, float scale, float *loss, stair_stream stream);

@@ -36,8 +36,8 @@ __device__ __forceinline__ float span_gold(double g0, double g1, int L, int t) {
     if (si <= ei) {
         if (t == si - 1) v += (double)si - start;
         if (t == ei) v += end - (double)ei;
-    } else if (t == ei) {
-        v += end - start;
+    } else if (t == (ei < 0 ? ei + L : ei)) {      // gold_tensor[end_int]: a negative end counts from the clip's end as in Python
+        v += end - start;                             // (only here can ei be < 0: si >= 1; the host refuses ei < -L)
     }
     return (float)v;
 }
@@ -252,6 +252,8 @@ int launch_loss_contrastive(const float *vec, float *d_vec, const int32_t *slot,
                             hipStream_t s) {
     if (n == 0) return 0;
     STAIR_CHECK(H <= 512, "hidden size above 512");
+    STAIR_CHECK(max_classes > 0 && (size_t)(3 * max_classes + H) * sizeof(float) <= 60 * 1024,
+                "window too large for the loss kernel's LDS (3 max_classes + H floats)");
     const LossGroups Gr = take_groups(n);
     hipLaunchKernelGGL(loss_contrastive_kernel, dim3(Gr.n_groups ? Gr.n_groups : n), dim3(kBlock), (size_t)(3 * max_classes + H) * sizeof(float), s, vec, d_vec,
                        slot, pos, win_start, win_cnt, G, n, H, scale, loss, (const float *)nullptr, (const int32_t *)nullptr, 0, Gr.order, Gr.grp_off);

@@ -23,6 +23,7 @@ from . import ops, spec
 from ._lib import check, lib
 
 CONTRASTIVE = ('Filter', 'Superlative', 'ToAction')
+ATTENTION_KINDS = ('Localize', 'Temporal', 'ExistsFrame')       # GoldPack.att_kind 0, 1, 2
 CRITERION_MODULES = frozenset({'Exists', 'Xor', 'Equals', 'Filter', 'ToAction', 'FilterFrame', 'ExistsFrame',
                                'Superlative', 'Localize', 'Temporal', 'decoder'})     # train_module.py:36-48
 
@@ -49,6 +50,18 @@ def _span_mask(start, end, T):
     else:
         g[ei] += np.float32(end - start)
     return g
+
+
+def refuse_unindexable_ends(ends, frames, node):
+    """span_to_attention writes gold_tensor[floor(end)] (train_module.py:79-80); a negative index counts from the clip's end, and
+    floor(end) < -L (L frames) raises IndexError in the reference.  Such a gold has no loss to match, so it is refused here
+    rather than scored.  ends, frames: one entry per interval; node(j) names the supervised node of interval j."""
+    ends, frames = np.asarray(ends, dtype=np.float64), np.asarray(frames, dtype=np.float64)
+    bad = np.flatnonzero(ends < -frames)              # floor(end) < -L  <=>  end < -L for an integer L
+    if bad.size:
+        j = int(bad[0])
+        raise ValueError('%s: gold interval end %r lies before the first frame of its %d-frame clip by more than the clip '
+                         '(the reference cannot index it)' % (node(j), float(ends[j]), int(frames[j])))
 
 
 def filterframe_target(gold, T, O, word2index):
@@ -398,6 +411,9 @@ def prepare_module_losses(model, res, questions, pretrain_modules=CRITERION_MODU
         keep = np.arange(2)[None, :] < K[:, None]
         qf = res.question_frames
         att_len = i32(np.asarray(qf)[gb.att_q]) if qf is not None else np.zeros(0, np.int32)
+        item = np.repeat(np.arange(n_att), K)
+        refuse_unindexable_ends(iv[keep][:, 1], att_len[item] if qf is not None else np.full(item.size, T), lambda j: (
+            '%s at program position %d of question %d' % (ATTENTION_KINDS[kind[item[j]]], gb.att_pos[item[j]], gb.att_q[item[j]])))
         stage('att', i32(slot), i32(K), i32(np.concatenate([[0], np.cumsum(K)])), np.ascontiguousarray(iv[keep], dtype=np.float64), att_len,
               *slot_groups(slot))
     # ---- linear heads (Exists / Xor / Equals) ----
@@ -565,12 +581,12 @@ def evaluate_module_losses(model, res, questions, pretrain_modules=CRITERION_MOD
             gold = sg[step]
             tok_ = int(res._prog_off[qi]) + i
             slot, aux, rel = int(slot_t[tok_]), int(aux_t[tok_]), int(rel_t[tok_])
-            if module == 'Localize':
-                att_items.append((slot, aux, [tuple(map(float, gold[r])) for r in range(aux)], module, qi))
-            elif module == 'Temporal':
-                att_items.append((rel, 1, [tuple(map(float, gold))], module, qi))
-            elif module == 'ExistsFrame':
-                att_items.append((slot, 1, [tuple(map(float, gold))], module, qi))
+            if module in ATTENTION_KINDS:
+                ivs = [tuple(map(float, gold[r])) for r in range(aux)] if module == 'Localize' else [tuple(map(float, gold))]
+                L = int(res.question_frames[qi]) if res.question_frames is not None else T
+                refuse_unindexable_ends([e for _, e in ivs], [L] * len(ivs),
+                                        lambda j: '%s at program position %d of question %d' % (module, i, qi))
+                att_items.append((rel if module == 'Temporal' else slot, len(ivs), ivs, module, qi))
             elif module in head_items:
                 head_items[module].append((slot, int(bool(gold))))
             elif module in CONTRASTIVE:
