@@ -260,8 +260,8 @@ int stair_lstm_bidir_fwd(const stair_lstm_args *args, stair_stream stream);
 /* Backward through time of the same layer (autograd of nn.LSTM in train_module.py:408).  gates = the
  * xproj_ws of a training-mode forward (overwritten in place with the gate pre-activation gradients),
  * cbuf/out from that forward, d_out [rows, ldd] and d_hn [n, 2*Hh] (may be NULL) the incoming gradients.
- * dw_ih/dw_hh/db_ih/db_hh are ACCUMULATED (fp32 atomics).  No input gradient is produced: the inputs
- * of both encoders are data (video features, GloVe vectors).  Scratch: whh_pack_ws [8*Hh*Hh],
+ * dw_ih/dw_hh/db_ih/db_hh are ACCUMULATED (fp32 atomics).  No input gradient is produced here: the gate
+ * gradients left in `gates` are what stair_plan_backward_dlogits multiplies by W_ih for one.  Scratch: whh_pack_ws [8*Hh*Hh],
  * hprev_ws [rows, 2*Hh]. */
 typedef struct stair_lstm_bwd_args {
     const float *x; int64_t ldx; int32_t rows, n, max_len, I, Hh;
@@ -664,6 +664,21 @@ int stair_plan_backward(stair_ctx *ctx, stair_plan *plan, const float *video, co
                                    the gradients injected by the stair_loss_* functions below.  STAIR_RUN_VIDEO_BF16 (2) must be
                                    repeated here when the forward pass ran on bf16 clip features. */
 int stair_plan_zero_grads(stair_plan *plan, void *workspace, stair_stream stream);
+/* Reverse pass of a STAIR_PLAN_TRAIN plan seeded by a caller's logits gradient instead of the decoder CE (torch autograd of the
+ * logits, stair_amd/autograd.py): everything after the seed is the pass of stair_plan_backward.
+ * d_logits [n, A] device fp32 (already scaled: no loss_scale).  Parameter gradients are ACCUMULATED into the
+ * buffers bound with stair_ctx_set_grad, exactly as stair_plan_backward does.
+ * d_video (may be NULL): [n_videos, T, V] fp32, OVERWRITTEN with dL/d(video) -- rows past a clip's video_len are 0;
+ *   with video_index every clip's gradient is the sum over the questions that read it; for STAIR_RUN_VIDEO_BF16 it is
+ *   the gradient with respect to the stored bf16 values, still written as fp32.
+ * d_question (may be NULL): [q_rows, E] fp32, OVERWRITTEN with dL/d(question).
+ * Both are one product per encoder after BPTT, dX = [dG_fwd | dG_bwd] [W_ih_fwd ; W_ih_bwd] (csrc/enc_input_grad.hip), in the
+ * context's matmul mode.  flags: STAIR_RUN_VIDEO_BF16 as for stair_plan_backward; STAIR_BWD_KEEP_ARENAS keeps its meaning.
+ * Argument errors are reported before anything is enqueued.  The pass overwrites the plan's saved gates: run the plan again
+ * before another reverse pass. */
+int stair_plan_backward_dlogits(stair_ctx *ctx, stair_plan *plan, const float *video, const float *question,
+                                void *workspace, int64_t workspace_bytes, const float *d_logits,
+                                float *d_video, float *d_question, int32_t flags, stair_stream stream);
 
 /* ---- per-module intermediate-supervision losses (train_module.py:33-194, CriterionByModule) -------------------
  * Each call evaluates `n` loss items, writes the unscaled loss of item i to loss[i] and ADDS scale * dloss/dresult

@@ -1,0 +1,83 @@
+"""Torch autograd for ``VideoNMN``'s logits: the native reverse pass (csrc/plan.hip) seeded by whatever gradient autograd hands it.
+
+``VideoNMN.logits(...)`` applies ``PlanLogits``: the forward pass runs a training plan on buffers of its own, and the backward pass
+calls ``stair_plan_backward_dlogits`` with the incoming logits gradient -- any loss on the logits works (label smoothing, class
+weights, distillation), and ``video`` / ``question`` receive input gradients when they require them (a trainable adapter in front of
+the executor, frame- or word-level saliency).  What the reference does with ``batch_loss.backward()`` (train_module.py:408).
+
+Semantics:
+
+* the parameters are INPUTS of the Function: their gradients go back through autograd, so ``torch.autograd.grad``, hooks and
+  ``.grad`` accumulation over several ``backward()`` calls behave as for any module.  Parameters that no program of the batch uses
+  (``stair_plan_touched``) get ``None``, as unused modules do in the reference (train_module.py:408-410);
+* every differentiable call owns its workspace and projection buffer until its backward has run (the model's shared buffers are
+  rewritten by the next batch), so several outstanding forwards may go backward together; the buffers are released afterwards;
+* a batch goes backward ONCE: BPTT overwrites the saved gates with their gradients.  A second backward through the same logits
+  raises, with or without ``retain_graph=True``;
+* double backward is not supported (``once_differentiable``).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from ._lib import check, lib
+
+_SEG = 64          # gradient buffers start on 256-byte boundaries inside one flat allocation
+
+
+class PlanLogits(torch.autograd.Function):
+    """apply(model, call, video, question, *params) -> logits [n, A]; `call` = (programs, spans, q_lens, video_index, video_len,
+    dropout, cse) as for ``VideoNMN.run_programs``; `params` in the order of ``model._weight_names``."""
+
+    @staticmethod
+    def forward(ctx, model, call, video, question, *params):
+        programs, spans, q_lens, video_index, video_len, dropout, cse = call
+        shared = model._ws, model._proj
+        model._ws = model._proj = None           # run_programs allocates buffers for THIS batch; the shared ones are put back
+        try:
+            res = model.run_programs(programs, spans, video.detach(), question.detach(), q_lens, train=True, video_index=video_index,
+                                     dropout=dropout, video_len=video_len, cse=cse)
+        finally:
+            model._ws, model._proj = shared
+        ctx.model, ctx.res = model, res
+        ctx.video_dtype = video.dtype
+        return res.logits
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_logits):
+        res = ctx.res
+        if res is None:
+            raise RuntimeError('VideoNMN.logits: this batch has been through backward() already -- its reverse pass overwrote the '
+                               'saved LSTM gates with their gradients, so it cannot go backward again (retain_graph does not change '
+                               'that); run model.logits(...) again')
+        ctx.res = None
+        model = ctx.model
+        params = dict(model.named_parameters())
+        names = model._weight_names
+        need_p = ctx.needs_input_grad[4:]
+        # a fresh zeroed gradient buffer per call: the pass ACCUMULATES into whatever is bound
+        offs, total = [], 0
+        for name in names:
+            offs.append(total)
+            total += (params[name].numel() + _SEG - 1) // _SEG * _SEG
+        dev = res.logits.device
+        flat = torch.zeros(total, dtype=torch.float32, device=dev)
+        grads = [flat[o: o + params[name].numel()].view_as(params[name]) for o, name in zip(offs, names)]
+        d_video = torch.empty(res._video.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        d_question = torch.empty(res._question.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
+        try:
+            for i, g in enumerate(grads):
+                check(lib.stair_ctx_set_grad(model._ctx, i, C.c_void_p(g.data_ptr()), g.numel()))
+            res.backward_dlogits(d_logits.detach().to(torch.float32).contiguous(), d_video, d_question, bind_grads=False)
+            touched = res.touched()
+        finally:
+            model._gbound = {}                   # a Trainer (or BatchResult.backward) used later binds its own buffers again
+            del res                              # the plan, its workspace and projection buffer go (stream-ordered reuse)
+        if d_video is not None and ctx.video_dtype != torch.float32:
+            d_video = d_video.to(ctx.video_dtype)
+        out = [g if (t and need) else None for g, t, need in zip(grads, touched, need_p)]
+        return (None, None, d_video, d_question, *out)

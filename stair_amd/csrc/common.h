@@ -168,5 +168,11 @@ int launch_colsum(const float *A, int64_t lda, float *out, int M, int N, hipStre
 int launch_transpose(const float *in, float *out, int rows, int cols, hipStream_t s);
 // bytes % 4 == 0 zero bytes at a 4-byte aligned address, as a kernel (never a memset node of a captured graph; csrc/rowops.hip)
 int launch_zero(void *ptr, int64_t bytes, hipStream_t s);
+// csrc/enc_input_grad.hip (stair_plan_backward_dlogits): the caller's logits gradient into the plan's dlogits region, and one encoder's
+// input gradient dX [rows, I] = gates [rows, 8 Hh] (the gate pre-activation gradients after BPTT) times [W_ih_fwd ; W_ih_bwd] [8 Hh, I];
+// wt_ws: scratch of 8 Hh * I floats for the transposed image of the stacked W_ih
+int launch_seed_dlogits(const float *src, float *dst, int64_t n, hipStream_t s);
+int launch_enc_input_grad(const float *gates, int64_t rows, int Hh, const float *w_ih_fwd, const float *w_ih_bwd, int I, float *wt_ws,
+                          float *dx, hipStream_t s);
 
 }  // namespace stair

@@ -2325,10 +2325,13 @@ long long *stair::det_shadow(const float *g) {
     return d.base + d.off[r.id] + (g - r.beg);
 }
 
-extern "C" int stair_plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, const float *question,
-                                   void *workspace, int64_t workspace_bytes, const int32_t *answers, float loss_scale,
-                                   float *loss_out, int32_t flags, stair_stream stream) {
-    STAIR_CHECK(ctx && pl && video && question && workspace && answers, "null argument");
+// The reverse pass behind both entry points.  Seed: the decoder CE against `answers` (stair_plan_backward), or the caller's logits
+// gradient when d_logits_in is set (stair_plan_backward_dlogits); d_video / d_question (optional) receive the encoders' input
+// gradients after BPTT.  With d_logits_in, d_video and d_question all NULL this is exactly the pass stair_plan_backward always ran.
+static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, const float *question, void *workspace,
+                         int64_t workspace_bytes, const int32_t *answers, float loss_scale, float *loss_out, const float *d_logits_in,
+                         float *d_video, float *d_question, int32_t flags, stair_stream stream) {
+    STAIR_CHECK(ctx && pl && video && question && workspace && (answers || d_logits_in), "null argument");
     PolicyScope policy_scope(&ctx->policy);
     STAIR_CHECK(pl->train, "plan was not built with STAIR_PLAN_TRAIN");
     // slab products queued by a pass that failed half-way must not be added into THIS pass's buffers: the queue starts empty and
@@ -2476,7 +2479,8 @@ extern "C" int stair_plan_backward(stair_ctx *ctx, stair_plan *pl, const float *
     }
 
     // ---- loss + decoder ------------------------------------------------------------------------
-    RUN(launch_ce_loss(logits, answers, loss_scale, loss, dlogits, n, A, s));
+    if (d_logits_in) RUN(launch_seed_dlogits(d_logits_in, dlogits, (int64_t)n * A, s));
+    else RUN(launch_ce_loss(logits, answers, loss_scale, loss, dlogits, n, A, s));
     {
         const float *cat = ws + pl->o_cat, *hid = ws + pl->o_hid;     // decoder buffers are never reused by buckets in training
         if (grouped) {
@@ -2933,8 +2937,41 @@ extern "C" int stair_plan_backward(stair_ctx *ctx, stair_plan *pl, const float *
     RUN(det_flush(ctx, s));                  // the encoders' fixed-point shadows -> the fp32 gradients
     if (g_det.active) ctx->gshadow_dirty = false;    // every touched shadow has been emptied again
     g_det.active = false;
+
+    // ---- encoder input gradients: dX = [dG_fwd | dG_bwd] [W_ih_fwd ; W_ih_bwd], the gate gradients BPTT left in the gates buffers ----
+    // The transposed module-weight images of the wt region were consumed by the level walk above; the region holds every weight of the
+    // context (ctx_weight_floats), so it fits the transposed [8 Hh, I] image of either encoder's two W_ih.
+    if (d_question)
+        RUN(launch_enc_input_grad((pl->ext_proj ? pl->proj : ws) + pl->o_xpt, pl->rows_q, Hh, W.enc[1][0], W.enc[1][4], E, ws + pl->o_wt,
+                                  d_question, s));
+    if (d_video)
+        RUN(launch_enc_input_grad((pl->ext_proj ? pl->proj : ws) + pl->o_xpv, (int64_t)pl->n_vid * T, Hh, W.enc[0][0], W.enc[0][4], V,
+                                  ws + pl->o_wt, d_video, s));
 #undef RUN
     return 0;
+}
+
+extern "C" int stair_plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, const float *question,
+                                   void *workspace, int64_t workspace_bytes, const int32_t *answers, float loss_scale,
+                                   float *loss_out, int32_t flags, stair_stream stream) {
+    STAIR_CHECK(ctx && pl && video && question && workspace && answers, "null argument");
+    return plan_backward(ctx, pl, video, question, workspace, workspace_bytes, answers, loss_scale, loss_out, nullptr, nullptr, nullptr,
+                         flags, stream);
+}
+
+extern "C" int stair_plan_backward_dlogits(stair_ctx *ctx, stair_plan *pl, const float *video, const float *question,
+                                           void *workspace, int64_t workspace_bytes, const float *d_logits, float *d_video,
+                                           float *d_question, int32_t flags, stair_stream stream) {
+    // every argument error is reported here, before anything is enqueued
+    STAIR_CHECK(ctx && pl && video && question && workspace && d_logits, "null argument");
+    STAIR_CHECK(pl->train, "plan was not built with STAIR_PLAN_TRAIN");
+    STAIR_CHECK(workspace_bytes >= pl->total * (int64_t)sizeof(float), "workspace too small");
+    STAIR_CHECK(((reinterpret_cast<uintptr_t>(d_logits) | reinterpret_cast<uintptr_t>(d_video) | reinterpret_cast<uintptr_t>(d_question)) & 15) == 0,
+                "d_logits / d_video / d_question must be 16-byte aligned");
+    const stair_config &g = ctx->cfg;
+    STAIR_CHECK(8ll * (g.hidden_size / 2) * std::max(g.video_size, g.text_size) <= ctx_weight_floats(ctx), "no room for the W_ih image");
+    return plan_backward(ctx, pl, video, question, workspace, workspace_bytes, nullptr, 0.0f, nullptr, d_logits, d_video, d_question, flags,
+                         stream);
 }
 
 // Which weights receive a gradient from this plan (1) and which do not (0).  torch leaves .grad = None

@@ -6,8 +6,9 @@ Differences that matter to a caller:
 
 * ``forward_batch`` runs MANY questions in one pass (the reference is batch-1 by construction,
   train_module.py:282); ``forward(data)`` is the drop-in single-question form built on it.
-* no autograd graph: training goes through ``run_programs(train=True)`` + ``BatchResult.backward`` (HIP
-  backward kernels) driven by ``stair_amd.train.Trainer``; only the decoder cross-entropy loss is built.
+* ``forward`` builds no autograd graph: training goes through ``run_programs(train=True)`` + ``BatchResult.backward`` (HIP
+  backward kernels) driven by ``stair_amd.train.Trainer``, where the decoder cross-entropy loss is built in.  ``logits(...)``
+  is the differentiable form (stair_amd/autograd.py): any loss on the logits, gradients for parameters and inputs.
 * programs whose operand kinds do not fit a module raise ``StairError`` at plan-build time instead
   of a torch shape error in the middle of execution.
 
@@ -140,6 +141,32 @@ class BatchResult:
                                       C.c_void_p(loss.data_ptr()), flags,
                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return loss
+
+    def backward_dlogits(self, d_logits, d_video=None, d_question=None, keep_arenas=False, bind_grads=True):
+        """Reverse pass of a train=True run seeded by an arbitrary logits gradient (stair_plan_backward_dlogits): d_logits
+        float32 [n, A] on the GPU, already scaled.  Parameter gradients are accumulated into the model's gradient buffers
+        (bind_grads=False: into the buffers the caller bound with stair_ctx_set_grad).  d_video (float32, the shape of the
+        run's video) and d_question (float32 [q_rows, E]) are optional and OVERWRITTEN with the input gradients.  The pass
+        overwrites the plan's saved gates: a batch goes backward once."""
+        n, A = self.info.n_questions, self._model.config['answer_vocab_length']
+        ops._req(d_logits, 'd_logits')
+        if tuple(d_logits.shape) != (n, A):
+            raise ValueError('d_logits must be [%d, %d]' % (n, A))
+        if d_video is not None:
+            ops._req(d_video, 'd_video')
+            if tuple(d_video.shape) != tuple(self._video.shape):
+                raise ValueError('d_video must have the shape of the video %s' % (tuple(self._video.shape),))
+        if d_question is not None:
+            ops._req(d_question, 'd_question')
+            if tuple(d_question.shape) != tuple(self._question.shape):
+                raise ValueError('d_question must have the shape of the question rows %s' % (tuple(self._question.shape),))
+        if bind_grads:
+            self._model._bind_grads()
+        flags = (1 if keep_arenas else 0) | (RUN_VIDEO_BF16 if self._video.dtype == torch.bfloat16 else 0)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        check(lib.stair_plan_backward_dlogits(self._model._ctx, self._plan, ptr(self._video), ptr(self._question), ptr(self._ws),
+                                              self._ws.numel() * 4, ptr(d_logits), ptr(d_video), ptr(d_question), flags,
+                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)))
 
     def capture_graph(self):
         """Record this batch's forward pass (encoders, every program level, decoder, argmax) into a hipGraph and
@@ -479,6 +506,21 @@ class VideoNMN(nn.Module):
         if train:       # a training plan keeps its logits inside the workspace for the backward pass; hand the caller a copy
             res.logits = ws[info.logits_off: info.logits_off + n * A].view(n, A).clone()    # (n x A floats) that survives the next step
         return res
+
+    def logits(self, programs, spans, video, question, q_lens, video_index=None, video_len=None, dropout=None, cse=True):
+        """[n, A] logits of a batch (arguments as for run_programs) with a torch autograd graph: when grad mode is on and any
+        parameter, `video` or `question` requires grad, the result has a grad_fn whose backward runs the native reverse pass
+        seeded by the logits gradient (stair_amd.autograd.PlanLogits) -- parameter gradients, and input gradients for `video`
+        (fp32 or bf16) / `question` when they require grad.  A batch goes backward once; double backward is not supported.
+        Otherwise an inference plan runs (dropout does not apply there) and the logits are those of run_programs."""
+        params = [dict(self.named_parameters())[n] for n in self._weight_names]
+        if not (torch.is_grad_enabled() and (video.requires_grad or question.requires_grad or any(p.requires_grad for p in params))):
+            with torch.no_grad():
+                return self.run_programs(programs, spans, video, question, q_lens, video_index=video_index, video_len=video_len,
+                                         cse=cse).logits
+        from .autograd import PlanLogits
+        call = (programs, spans, q_lens, video_index, video_len, dropout, cse)
+        return PlanLogits.apply(self, call, video, question, *params)
 
     def forward_batch(self, batch, train=False, share_videos=True, dropout=None, cse=True):
         """batch: list of question dicts in the reference layout (dataset.py:191-233).  Clips may differ in their
