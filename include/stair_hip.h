@@ -412,11 +412,11 @@ typedef struct stair_vec_problem {
 int stair_vec_group(const stair_vec_problem *problems, int32_t count, stair_stream stream);
 
 /* stair_plan_run uses the fused operators where they apply (hidden_size 512, T <= 64, split matmul mode; with dropout too since ABI 6);
- * on = 0 keeps the GEMM / row-kernel sequences everywhere, on < 0 restores the default (env STAIR_TILE_MLP, default on). */
+ * on = 0 keeps the GEMM / row-kernel sequences everywhere, on < 0 restores the default (on). */
 int stair_set_tile_mlp(int32_t on);
 /* Tiles of a fused launch are dealt out through a self-resetting atomic work queue in the plan workspace (on != 0, default; two
  * words that every launch leaves at zero, so eager runs and hipGraph replays need no reset between launches) or by a static round
- * robin (on = 0); on < 0 restores the default (env STAIR_TILE_QUEUE).  Results are bit-identical either way. */
+ * robin (on = 0); on < 0 restores the default (on).  Results are bit-identical either way. */
 int stair_set_tile_queue(int32_t on);
 /* W [N, K] fp32 row-major -> planes: [N/32][K/16][hi, lo][64 lanes][8 bf16] (2 * N * K * 2 bytes, 16-byte aligned);
  * N % 32 == 0, K % 16 == 0.  transpose != 0: W is stored [K, N] and the planes are those of W^T (backward chains). */
@@ -505,7 +505,7 @@ int stair_cosine_topk(const float *queries, int64_t ldq, const int32_t *q_idx, c
                                computed ONCE per batch and every other occurrence -- in another question about the same clip, or
                                again in the same program -- aliases its slot (same value; gradients of all users add up in it).
                                Filter's tensor keyword does not enter the comparison: its attention is identically 1
-                               (modules.py:354,373).  Env STAIR_PLAN_CSE=0 has the same effect. */
+                               (modules.py:354,373). */
 #define STAIR_PLAN_EXT_PROJECTION 4 /* flags (ABI 6): the regions of the encoders' input projections (x W_ih^T + biases of every clip frame and
                                token row: the gates of a training plan; bias sums; W_ih / token-row planes) are NOT laid out in the plan's
                                workspace but live in a caller-owned buffer of stair_projection_floats floats, handed over with

@@ -53,6 +53,11 @@ __device__ __forceinline__ float tanh_fast(float x) {
     return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x));
 }
 
+// ---- settings from the environment (INTEGRATION.md "Environment switches"); each variable is read at one site -----------------
+// env_str: the value, or NULL when the variable is unset or empty; env_int: its integer value, or dflt when unset or empty
+inline const char *env_str(const char *name) { const char *e = getenv(name); return e && e[0] ? e : nullptr; }
+inline int env_int(const char *name, int dflt) { const char *e = env_str(name); return e ? atoi(e) : dflt; }
+
 static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 // ---- run-to-run reproducible weight gradients -----------------------------------------------------------------------------------
@@ -63,6 +68,7 @@ static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * 
 // the fp32 gradients by one launch at the end of the pass (csrc/plan.hip det_*).  det_shadow(g): the shadow of the gradient
 // element g points at, or NULL outside a backward pass / for a pointer that is not inside a bound gradient tensor / STAIR_DETERMINISTIC=0.
 long long *det_shadow(const float *gptr);
+bool det_enabled();                                      // STAIR_DETERMINISTIC (default 1)
 constexpr float kFxScale = 17592186044416.0f;            // 2^44
 __device__ __forceinline__ void fx_add(long long *p, float v) {
     atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__float2ll_rn(v * kFxScale));
@@ -100,7 +106,7 @@ int launch_gemm(const stair_gemm_args &a, hipStream_t s);
 int launch_lstm(const stair_lstm_args &a, hipStream_t s);
 int launch_lstm_bwd(const stair_lstm_bwd_args &a, hipStream_t s);
 // STAIR_GEMM_TRACE=1: every GEMM launcher prints its shape to stderr (tools/gemm_shapes.py joins the lines with a rocprofv3 kernel trace)
-inline bool gemm_trace_on() { static const bool on = [] { const char *e = getenv("STAIR_GEMM_TRACE"); return e && e[0] == '1'; }(); return on; }
+inline bool gemm_trace_on() { static const bool on = env_int("STAIR_GEMM_TRACE", 0) == 1; return on; }
 
 struct TransposeBatch {          // up to 32 matrices transposed by one launch (launch_transpose_many)
     const float *in[32]; float *out[32];

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
 static int g_matmul_mode = -1;
 int matmul_mode() {
     if (g_matmul_mode < 0) {
-        const char *e = getenv("STAIR_MATMUL");
+        const char *e = env_str("STAIR_MATMUL");
         g_matmul_mode = (e && std::string(e) == "f32") ? STAIR_MATMUL_F32 : (e && std::string(e) == "bf16") ? STAIR_MATMUL_BF16 : STAIR_MATMUL_BF16X3;
     }
     return policy_or(STAIR_OPT_MATMUL_MODE, g_matmul_mode);

@@ -586,11 +586,6 @@ __global__ void c_rows_reduce_kernel(float *C, int64_t ldc, int64_t gs, const in
     }
 }
 
-static bool gemm_w8_enabled() {
-    static const bool on = [] { const char *e = getenv("STAIR_GEMM_W8"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 int launch_gemm_bf16x3(const stair_gemm_args &a, hipStream_t s) {
     XParams p;
     p.a = a;
@@ -603,12 +598,11 @@ int launch_gemm_bf16x3(const stair_gemm_args &a, hipStream_t s) {
     const size_t shmem = 2 * 2 * 2 * IMG * sizeof(__bf16);
     const bool plain = a.K % 64 == 0 && !a.row_scale;
     const bool one = matmul_mode() == STAIR_MATMUL_BF16;        // single product per operand pair (top-1 identity only)
-    static const int t256_min = [] { const char *e = getenv("STAIR_GEMM_T256"); return e ? atoi(e) : 256; }();   // 0 = off
     const int t2m = (p.M + 255) / 256, t2n = (a.N + 255) / 256;
     // one 256 x 256 workgroup per CU: the launch runs in rounds of 256 tiles, so it only pays when the last round is
     // (nearly) full -- 266 tiles took 1.4x the time of the 128 x 128 kernel's 1064, 2048 tiles 0.85x.
     const int t2 = t2m * t2n, rounds = (t2 + 255) / 256;
-    if (plain && t256_min > 0 && t2 >= t256_min && a.K >= 64 && (t256_min == 1 || rounds * 256 * 100 <= t2 * 108)) {
+    if (plain && t2 >= 256 && a.K >= 64 && rounds * 256 * 100 <= t2 * 108) {
         XParams q = p;
         q.tilesM = t2m; q.tilesN = t2n;
         const size_t shmem2 = 2 * 2 * 2 * IMG2 * sizeof(__bf16);       // 128 KB
@@ -639,14 +633,12 @@ int launch_gemm_bf16x3(const stair_gemm_args &a, hipStream_t s) {
     // bias or activation (the dX products of training) add their partial sums with the atomics they use anyway; forward
     // products write partials to the caller's scratch (stair_gemm_args.splitk_ws) and a second kernel reduces them in
     // a fixed order and applies bias + activation -- results stay deterministic and independent of the batch.
-    static const bool splitk_on = [] { const char *e = getenv("STAIR_GEMM_SPLITK"); return !(e && e[0] == '0'); }();
     const int tiles128 = p.tilesM * p.tilesN;
-    if (splitk_on && tiles128 <= 64 && a.K >= 256 && a.K <= 128 * 16) {
+    if (tiles128 <= 64 && a.K >= 256 && a.K <= 128 * 16) {
         const int kchunk = 128;                         // fixed, so the order of the partial sums does not depend on the batch
         const int ksplit = (a.K + kchunk - 1) / kchunk;
         // (K pieces that add into the target with atomics land in any order: only when run-to-run reproducibility is switched off)
-        static const bool det = [] { const char *e = getenv("STAIR_DETERMINISTIC"); return !(e && e[0] == '0'); }();
-        const bool direct = a.accumulate && a.act == 0 && !a.bias && !det;
+        const bool direct = a.accumulate && a.act == 0 && !a.bias && !det_enabled();
         const bool staged = !a.accumulate && a.splitk_ws && a.splitk_ws_floats >= (int64_t)ksplit * M * a.N;
         if (ksplit > 1 && (direct || staged)) {
             p.ksplit = ksplit; p.kchunk = kchunk;
@@ -667,7 +659,7 @@ int launch_gemm_bf16x3(const stair_gemm_args &a, hipStream_t s) {
             return 0;
         }
     }
-    const bool w8 = gemm_w8_enabled() && p.tilesM * p.tilesN >= 512;   // enough tiles for two 8-wave workgroups on every CU
+    const bool w8 = p.tilesM * p.tilesN >= 512;   // enough tiles for two 8-wave workgroups on every CU
     STAIR_ACCT_MFMA(w8 ? "gemm_bf16x3_w8" : "gemm_bf16x3", (M * a.K + (int64_t)a.N * a.K + M * a.N) * 4, 2 * M * a.N * a.K);
 #define X_LAUNCH1(ACT_, NP_)                                                                                       \
     if (w8 && plain) hipLaunchKernelGGL((gemm_bf16x3_w8_kernel<ACT_, true, NP_>), grid, dim3(512), shmem, s, p);    \
@@ -871,7 +863,7 @@ template <bool PLAIN, int NP, bool BX = false, bool RS = true>
 __global__ __launch_bounds__(256, (RS && !PLAIN) ? 1 : 2) void gemm_tn_bf16x3_kernel(XTnParams p) {
     gemm_tn_bf16x3_body<PLAIN, NP, BX, RS>(p, (int)blockIdx.x);
 }
-// Several small weight-gradient products in one launch of the same body over a problem table (STAIR_TN_BATCH=0: one launch each).  The body is
+// Several small weight-gradient products in one launch of the same body over a problem table.  The body is
 // the form without scale registers: the form with them spilled, and a spilling kernel with two workgroups on a CU is what made this launch
 // irreproducible when it was first tried ("scratch and co-resident workgroups").
 constexpr int XTN_BATCH = 20;
@@ -1052,11 +1044,10 @@ int launch_gemm_tn_bf16x3(const stair_gemm_tn_args &a, hipStream_t s) {
         if (rc >= 0) return rc;
     }
     {   // 256 x 256 tiles where the output is large enough (>= 16 of them) and the staging is the simple case
-        static const int tn256 = [] { const char *e = getenv("STAIR_GEMM_TN256"); return e ? atoi(e) : 16; }();   // 0 = off
         const int t2n = (a.N + 255) / 256, t2k = (a.K + 255) / 256, t2 = t2n * t2k;
         // (a short reduction dimension gives each of the 512 workgroups a handful of chunks and a 256 x 256 atomic epilogue:
         // the decoder's dW at M = 2048 took 122 us here against ~40 us on the 128 x 128 kernel, so M must be long)
-        if (tn256 > 0 && t2 >= tn256 && p.fast8 == 1 && !p.row_scale && a.M % 64 == 0 && (a.M >= 16384 || tn256 == 1)) {
+        if (t2 >= 16 && p.fast8 == 1 && !p.row_scale && a.M % 64 == 0 && a.M >= 16384) {
             XTnParams q = p;
             q.tilesN = t2n; q.tilesK = t2k;
             int slabs = std::max(1, std::min(a.M / 64, (512 + t2 - 1) / t2));
@@ -1084,9 +1075,7 @@ int launch_gemm_tn_bf16x3(const stair_gemm_tn_args &a, hipStream_t s) {
     const int tiles = p.tilesN * p.tilesK;
     // M is split into slabs so that ~512 workgroups (2 per CU) exist; more slabs only add fp32 atomics (each slab adds
     // its whole N x K tile set: measured 172 -> 205 TFLOP/s at M=32768, N=K=512 going from 1024 to 512 workgroups)
-    static const int target = [] { const char *e = getenv("STAIR_TN_BLOCKS"); return e ? std::max(8, atoi(e)) : 512; }();
-    static const int minrows = [] { const char *e = getenv("STAIR_TN_MINROWS"); return e ? std::max(32, atoi(e)) : 256; }();
-    int slabs = std::max(1, std::min((a.M + minrows - 1) / minrows, (target + tiles - 1) / tiles));
+    int slabs = std::max(1, std::min((a.M + 255) / 256, (512 + tiles - 1) / tiles));
     slabs = (slabs + 7) / 8 * 8;                                   // a multiple of the XCD count
     p.mslab = ((a.M + slabs - 1) / slabs + 63) / 64 * 64;
     const size_t shmem = 2 * 2 * 2 * IMG * sizeof(__bf16);
@@ -1094,41 +1083,26 @@ int launch_gemm_tn_bf16x3(const stair_gemm_tn_args &a, hipStream_t s) {
                                                    // (the bias sums still meet from several threads of a workgroup: they keep their shadow)
     const bool plain = !p.row_scale && a.M % 64 == 0 && p.mslab % 64 == 0;
     STAIR_ACCT_MFMA("gemm_tn_bf16x3", ((int64_t)a.M * a.N * 4 + (int64_t)a.M * a.K * (bx ? 2 : 4) + (int64_t)a.N * a.K * 4), 2ll * a.M * a.N * a.K);
-    // non-PLAIN launches without a row scale take the kernels that keep no scale registers (RS = false)
-    static const bool rs_always = [] { const char *e = getenv("STAIR_TN_RS_ALWAYS"); return e && e[0] == '1'; }();   // diagnostics
-    static const size_t lds_force = [] { const char *e = getenv("STAIR_TN_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();   // diagnostics: 98304 = one workgroup per CU
-    const bool rs = p.row_scale != nullptr || rs_always;
-    size_t lds = shmem;
-    if (lds_force > shmem) {
-        lds = lds_force;
-        static bool attr_set = false;
-        if (!attr_set) {
-#define TN_ATTR(...) STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_bf16x3_kernel<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-            TN_ATTR(true, 3, true); TN_ATTR(false, 3, true, false); TN_ATTR(false, 3, true, true); TN_ATTR(true, 1); TN_ATTR(true, 3);
-            TN_ATTR(false, 1, false, true); TN_ATTR(false, 1, false, false); TN_ATTR(false, 3, false, true); TN_ATTR(false, 3, false, false);
-#undef TN_ATTR
-            attr_set = true;
-        }
-    }
+    // non-PLAIN launches without a row scale take the kernels that keep no scale registers (RS = false); bf16 B rows never
+    // carry a row scale
+    const bool rs = p.row_scale != nullptr;
     const dim3 grid(tiles * slabs), block(256);
     if (bx) {
         STAIR_CHECK(p.fast8 != 0, "internal: bf16 B rows need a plain row matrix");
-        if (plain) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<true, 3, true>), grid, block, lds, s, p);
-        else if (rs) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 3, true, true>), grid, block, lds, s, p);
-        else hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 3, true, false>), grid, block, lds, s, p);
-    } else if (plain && one) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<true, 1>), grid, block, lds, s, p);
-    else if (plain) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<true, 3>), grid, block, lds, s, p);
-    else if (one && rs) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 1, false, true>), grid, block, lds, s, p);
-    else if (one) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 1, false, false>), grid, block, lds, s, p);
-    else if (rs) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 3, false, true>), grid, block, lds, s, p);
-    else hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 3, false, false>), grid, block, lds, s, p);
+        if (plain) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<true, 3, true>), grid, block, shmem, s, p);
+        else hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 3, true, false>), grid, block, shmem, s, p);
+    } else if (plain && one) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<true, 1>), grid, block, shmem, s, p);
+    else if (plain) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<true, 3>), grid, block, shmem, s, p);
+    else if (one && rs) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 1, false, true>), grid, block, shmem, s, p);
+    else if (one) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 1, false, false>), grid, block, shmem, s, p);
+    else if (rs) hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 3, false, true>), grid, block, shmem, s, p);
+    else hipLaunchKernelGGL((gemm_tn_bf16x3_kernel<false, 3, false, false>), grid, block, shmem, s, p);
     STAIR_LAUNCH_CHECK();
     return 0;
 }
 
 int launch_gemm_tn_batch(const stair_gemm_tn_args *a, int n, hipStream_t s) {
-    static const bool on = [] { const char *e = getenv("STAIR_TN_BATCH"); return !(e && e[0] == '0'); }();
-    bool ok = on && n >= 2 && matmul_mode() == STAIR_MATMUL_BF16X3;
+    bool ok = n >= 2 && matmul_mode() == STAIR_MATMUL_BF16X3;
     for (int i = 0; i < n && ok; ++i)
         ok = a[i].M > 0 && a[i].M < 16384 && !a[i].b_is_bf16 && !a[i].row_scale && a[i].N % 4 == 0 && a[i].K % 4 == 0 && a[i].lda % 4 == 0 && a[i].ldb % 4 == 0 &&
              a[i].b_gstride % 4 == 0 && a[i].rows_per_group > 0;
@@ -1138,16 +1112,10 @@ int launch_gemm_tn_batch(const stair_gemm_tn_args *a, int n, hipStream_t s) {
                 if (int rc = launch_gemm_tn(a[i], s)) return rc;
         return 0;
     }
-    static const int lds_req = [] { const char *e = getenv("STAIR_TN_BATCH_LDS"); return e ? atoi(e) : 0; }();
-    const size_t shmem = lds_req > 0 ? (size_t)lds_req : 2 * 2 * 2 * IMG * sizeof(__bf16);
-    if (lds_req > 65536) {
-        static bool set_ = false;
-        if (!set_) { STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_bf16x3_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_req)); set_ = true; }
-    }
-    static const int bmax = [] { const char *e = getenv("STAIR_TN_BATCH_MAX"); return e ? std::max(1, std::min(XTN_BATCH, atoi(e))) : XTN_BATCH; }();
-    for (int i0 = 0; i0 < n; i0 += bmax) {
+    const size_t shmem = 2 * 2 * 2 * IMG * sizeof(__bf16);
+    for (int i0 = 0; i0 < n; i0 += XTN_BATCH) {
         XTnBatch b;
-        b.n = std::min(bmax, n - i0);
+        b.n = std::min(XTN_BATCH, n - i0);
         b.first[0] = 0;
         for (int i = 0; i < XTN_BATCH; ++i) {
             if (i >= b.n) { b.p[i] = b.p[0]; b.first[i + 1] = b.first[b.n]; continue; }

@@ -73,15 +73,17 @@ __device__ __forceinline__ int pl_swz(int R) {
 // NPA: A planes (1: exact bf16 A, two products per pair; 2: hi + lo, three products).  ACT as stair_gemm_args.act.
 // WT: W planes in the tiled layout [K/32][N][32] written by stair_split_planes_tiled: one LDS-DMA instruction then reads
 // 1 KB of contiguous memory (16 rows x 64 B) instead of 16 half lines 2*ldw bytes apart.
-// MF: 0 = v_mfma_f32_32x32x16_bf16 (wave tile 4 x 2 blocks of 32 x 32, two k steps per stage, fragments of the next k
-//     step prefetched across the barrier); 1 = v_mfma_f32_16x16x32_bf16 (8 x 4 blocks of 16 x 16, one k step per stage).
+// MF, the MFMA shape, follows NPA: 0 = v_mfma_f32_32x32x16_bf16 for one A plane (wave tile 4 x 2 blocks of 32 x 32, two k steps
+//     per stage, fragments of the next k step prefetched across the barrier); 1 = v_mfma_f32_16x16x32_bf16 for two (8 x 4 blocks of
+//     16 x 16, one k step per stage).  Measured equal for two products (0.95 ms either way on the dominant shape); with three the
+//     16x16x32 form is 4 % faster (1.32 vs 1.37 ms) -- profiles/r02_a_planes_bench.txt.
 // The grid is at most one workgroup per CU and every workgroup walks its tiles itself, treating (tile, k step) as ONE
 // stream of stages: the LDS-DMA of the next tile's first stages is issued while the current tile's last stages are
 // multiplied, and the epilogue's stores drain behind the next tile's loads.
-// ABL: ablation builds for measurements (1: no LDS-DMA in the loop, 2: no fragment reads / MFMAs); 0 in the product.
-template <int NPA, int ACT, bool WT, int MF, int ABL = 0>
+template <int NPA, int ACT, bool WT>
 __global__ __launch_bounds__(512, 1) void gemm_planes_kernel(PlParams p) {
     extern __shared__ __attribute__((aligned(16))) char plds[];
+    constexpr int MF = NPA == 2 ? 1 : 0;
     constexpr int NPL = NPA + 2;                         // planes per stage: A hi [, A lo], W hi, W lo
     constexpr int NST = NPA == 1 ? 3 : 2;                // ring depth (144 KB / 128 KB)
     constexpr int STAGE_BYTES = NPL * PLANE_BYTES;
@@ -179,16 +181,9 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_kernel(PlParams p) {
             if (NPA == 2) fal[s_][i_] = *reinterpret_cast<const bf16x8 *>(sb_ + PLANE_BYTES + (offA[i_] ^ cx_));     \
         }                                                                                                            \
     }
-#define PL_MUL(s_)                                                                                                   \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                                 \
-        _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_) {                                                           \
-            if (NPA == 2) acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal[s_][i_], fwh[s_][j_], acc[i_][j_], 0, 0, 0);   \
-            acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s_][i_], fwl[s_][j_], acc[i_][j_], 0, 0, 0);    \
-            acc[i_][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s_][i_], fwh[s_][j_], acc[i_][j_], 0, 0, 0);    \
-        }
-        // one (i, j) block of PL_MUL, and the rest: the first half of a step multiplies ONE block before it issues its reads -- the
-        // fragments of k step 0 come out of the previous iteration, and hipcc's wait-count pass, which cannot count across the loop's
-        // back edge, puts an lgkmcnt(0) in front of their first use: placed after the reads it waited for all eight of them
+        // the products of k step s_ as one (i, j) block and the rest: the first half of a step multiplies ONE block before it issues
+        // its reads -- the fragments of k step 0 come out of the previous iteration, and hipcc's wait-count pass, which cannot count
+        // across the loop's back edge, puts an lgkmcnt(0) in front of their first use: placed after the reads it waited for all eight
 #define PL_MUL_ONE(s_)                                                                                               \
     {                                                                                                                \
         if (NPA == 2) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fal[s_][0], fwh[s_][0], acc[0][0], 0, 0, 0); \
@@ -216,7 +211,7 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_kernel(PlParams p) {
         wait_vm<(NST - 2) * LPS>();
         __builtin_amdgcn_s_barrier();
         int sbuf = 0, ibuf = (NST - 1) * STAGE_BYTES;
-        if (ABL != 2) PL_READ(sbuf, 0);         // (the MFMA-only ablations multiply these fragments over and over)
+        PL_READ(sbuf, 0);
         // STAGGER: the two waves of a SIMD (w and w + 4) run this same program in lockstep, so they used to issue their LDS-DMA -- six
         // instructions of ~100 cycles of issue each, as long as half a wave's MFMAs of the stage -- at the same moment, with the SIMD's
         // matrix pipe idle meanwhile.  Waves 4..7 now issue theirs HALF a stage later (after the barrier, before k step 1), beside their
@@ -224,32 +219,27 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_kernel(PlParams p) {
         const bool late = stagger && wave >= 4;
         for (int ord = 0; ord < my_tiles; ++ord) {
             for (int t = 0; t < nt; ++t) {
-                // ABL (measurements): 1 no LDS-DMA; 2 no reads, no MFMAs; 3 MFMAs only (no DMA, reads, barrier); 4 MFMAs + barrier;
-                // 5 MFMAs + reads, no barrier (and no DMA); 6 everything but the epilogue's stores
-                constexpr bool PIN = ABL != 7;          // (7: the reads unpinned, as before)
-                constexpr bool DMA = ABL == 0 || ABL == 2 || ABL == 6 || ABL == 7, RD = ABL == 0 || ABL == 1 || ABL == 5 || ABL == 6 || ABL == 7, MM = ABL != 2,
-                               BAR = ABL != 3 && ABL != 5;
-                if (DMA && !late) PL_STAGE(ibuf, i_k);
-                if (MM && PIN) { PL_MUL_ONE(0); __builtin_amdgcn_sched_barrier(0); }
-                if (RD) PL_READ(sbuf, 1);
+                if (!late) PL_STAGE(ibuf, i_k);
+                PL_MUL_ONE(0);
+                __builtin_amdgcn_sched_barrier(0);
+                PL_READ(sbuf, 1);
                 // the reads stay ABOVE the MFMAs they hide behind: hipcc otherwise sinks all eight to the END of the block (shorter live
                 // ranges), right in front of the lgkmcnt(0) below, and every half stage waits out an LDS round trip with the matrix pipe idle
-                if (PIN) __builtin_amdgcn_sched_barrier(0);
-                if (MM) { if (PIN) { PL_MUL_REST(0); } else { PL_MUL(0); } }
                 __builtin_amdgcn_sched_barrier(0);
-                if (BAR) {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if (late) wait_vm<0>(); else wait_vm<(NST - 2) * LPS>();
-                    __builtin_amdgcn_s_barrier();
-                }
+                PL_MUL_REST(0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (DMA && late) PL_STAGE(ibuf, i_k);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (late) wait_vm<0>(); else wait_vm<(NST - 2) * LPS>();
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+                if (late) PL_STAGE(ibuf, i_k);
                 sbuf = sbuf + STAGE_BYTES == NST * STAGE_BYTES ? 0 : sbuf + STAGE_BYTES;
                 ibuf = ibuf + STAGE_BYTES == NST * STAGE_BYTES ? 0 : ibuf + STAGE_BYTES;
-                if (MM && PIN) { PL_MUL_ONE(1); __builtin_amdgcn_sched_barrier(0); }     // (as above: the compiler's own wait for k step 1's fragments lands here, where it is free)
-                if (RD) PL_READ(sbuf, 0);
-                if (PIN) __builtin_amdgcn_sched_barrier(0);
-                if (MM) { if (PIN) { PL_MUL_REST(1); } else { PL_MUL(1); } }
+                PL_MUL_ONE(1);                      // (as above: the compiler's own wait for k step 1's fragments lands here, where it is free)
+                __builtin_amdgcn_sched_barrier(0);
+                PL_READ(sbuf, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                PL_MUL_REST(1);
                 advance();                  // (the branches of the cursor sit at the end: the blocks above stay straight-line)
             }
             const int tile = first + ord * G;
@@ -273,7 +263,7 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_kernel(PlParams p) {
                         if (ACT == 2) v = sigmoid_acc(v);
                         __attribute__((address_space(1))) float *rowp =
                             (__attribute__((address_space(1))) float *)(ctile + (int64_t)rl * p.ldc + j * 32);
-                        if (ABL != 6 && (full || (n < p.N && m0 + wm * 128 + 4 * h + rl < p.M))) {
+                        if (full || (n < p.N && m0 + wm * 128 + 4 * h + rl < p.M)) {
                             if (p.nt_store) __builtin_nontemporal_store(v, rowp + loff);
                             else rowp[loff] = v;
                         }
@@ -283,7 +273,6 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_kernel(PlParams p) {
             }
         }
 #undef PL_READ
-#undef PL_MUL
 #undef PL_MUL_ONE
 #undef PL_MUL_REST
     } else {
@@ -331,8 +320,8 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_kernel(PlParams p) {
         int sbuf = 0, ibuf = (NST - 1) * STAGE_BYTES;
         for (int ord = 0; ord < my_tiles; ++ord) {
             for (int t = 0; t < nt; ++t) {
-                if (ABL != 1) PL_STAGE(ibuf, i_k);
-                if (ABL != 2) PL_STEP(sbuf);
+                PL_STAGE(ibuf, i_k);
+                PL_STEP(sbuf);
                 __builtin_amdgcn_sched_barrier(0);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // every read of this stage done before its buffer is refilled
                 wait_vm<(NST - 2) * LPS>();
@@ -380,7 +369,6 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_kernel(PlParams p) {
 // and a wave needs only ITS 64 columns of W: here W never enters LDS.  It is stored in MFMA fragment order (stair_pack_wfrag:
 // [N/32][K/16][hi, lo][64 lanes][8 bf16], 1 KB per fragment) and each wave loads its own fragments global -> VGPR one stage ahead (the two
 // waves that share a column block load the same lines: L1 hits); LDS-DMA stages A alone (16 KB per stage, ring of 4).  NPA == 1, act 0.
-template <int ABL = 0>
 __global__ __launch_bounds__(512, 1) void gemm_planes_wr_kernel(PlParams p) {
     extern __shared__ __attribute__((aligned(16))) char plds[];
     constexpr int NSTA = 4;                              // A stages in the ring (64 KB)
@@ -506,7 +494,7 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_wr_kernel(PlParams p) {
         if (done > 0) { WR_WAITW(slot_, 2); } else { WR_WAITW(slot_, 0); }                                   \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
         WR_LOADW(1 - (slot_))                            /* W of the NEXT stage: 8 ops */                     \
-        if (ABL != 1) WR_STAGE(ibuf, i_k);               /* then A of the stage NSTA-1 ahead: 2 ops */       \
+        WR_STAGE(ibuf, i_k);                             /* then A of the stage NSTA-1 ahead: 2 ops */       \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
         WR_MUL_ONE(0, slot_); __builtin_amdgcn_sched_barrier(0);                                             \
         WR_READ(sbuf, 1); __builtin_amdgcn_sched_barrier(0);                                                 \
@@ -680,12 +668,8 @@ int launch_gemm_planes(const stair_gemm_planes_args &a, hipStream_t s) {
     p.A[0] = static_cast<const __bf16 *>(a.A_hi); p.A[1] = static_cast<const __bf16 *>(a.A_lo);
     p.W[0] = static_cast<const __bf16 *>(a.W_hi); p.W[1] = static_cast<const __bf16 *>(a.W_lo);
     p.lda = a.lda; p.ldw = a.ldw; p.bias = a.bias; p.C = a.C; p.ldc = a.ldc;
-    {   // measured: 1.985 -> 1.969 ms per launch at the bench shape (two A/B pairs on one box); STAIR_PLANES_NT_STORE=0 switches it off
-        static const int nts = [] { const char *e = getenv("STAIR_PLANES_NT_STORE"); return (e && e[0] == '0') ? 0 : 1; }();
-        p.nt_store = nts;
-        static const int stg = [] { const char *e = getenv("STAIR_PLANES_STAGGER"); return (e && e[0] == '0') ? 0 : 1; }();
-        p.stagger = stg;
-    }
+    p.nt_store = 1;             // measured: 1.985 -> 1.969 ms per launch at the bench shape (two A/B pairs on one box)
+    p.stagger = 1;
     p.M = a.M; p.N = a.N; p.K = a.K;
     p.tilesM = (a.M + 255) / 256; p.tilesN = (a.N + 255) / 256;
     const int nb = p.tilesM * p.tilesN;
@@ -695,55 +679,34 @@ int launch_gemm_planes(const stair_gemm_planes_args &a, hipStream_t s) {
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
         return n > 0 ? n : 256;
     }();
-    static const int ablate = [] { const char *e = getenv("STAIR_PLANES_ABLATE"); return e ? atoi(e) : 0; }();   // measurements only
     const dim3 grid(std::min(nb, ncu)), block(512);
     if (a.w_tiled == 2) {               // W in fragment order, loaded global -> VGPR by the wave that multiplies it (gemm_planes_wr_kernel)
         STAIR_CHECK(!a.A_lo && a.act == 0, "fragment-order W: exact-bf16 A, no activation");
         STAIR_CHECK(a.N % 32 == 0 && a.N >= 64 && a.K % 64 == 0, "fragment-order W: N % 32 == 0, N >= 64, K % 64 == 0");
         const size_t shw = 4 * PLANE_BYTES;
-        if (ablate == 1) hipLaunchKernelGGL((gemm_planes_wr_kernel<1>), grid, block, shw, s, p);
-        else hipLaunchKernelGGL((gemm_planes_wr_kernel<0>), grid, block, shw, s, p);
+        hipLaunchKernelGGL(gemm_planes_wr_kernel, grid, block, shw, s, p);
         STAIR_LAUNCH_CHECK();
         return 0;
     }
     const size_t sh1 = 3 * 3 * PLANE_BYTES, sh2 = 2 * 4 * PLANE_BYTES;
     static bool attr_set = false;       // one device per process (one ctx per GPU / process, see stair_hip.h)
-    // MFMA shape: measured equal for two products (0.95 ms either way on the dominant shape); with three the 16x16x32 form
-    // is 4 % faster (1.32 vs 1.37 ms) -- profiles/r02_a_planes_bench.txt.  STAIR_PLANES_MFMA = 0 / 1 forces one.
-    static const int mf_force = [] { const char *e = getenv("STAIR_PLANES_MFMA"); return e ? atoi(e) : -1; }();
-    const int mf_env = mf_force >= 0 ? mf_force : (a.A_lo ? 1 : 0);
-#define P_FOREACH(X) X(0, false, 0) X(1, false, 0) X(2, false, 0) X(0, true, 0) X(1, true, 0) X(2, true, 0) \
-                     X(0, false, 1) X(1, false, 1) X(2, false, 1) X(0, true, 1) X(1, true, 1) X(2, true, 1)
+#define P_FOREACH(X) X(0, false) X(1, false) X(2, false) X(0, true) X(1, true) X(2, true)
     if (!attr_set) {
-#define P_ATTR(ACT_, WT_, MF_)                                                                                          \
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_planes_kernel<1, ACT_, WT_, MF_>),            \
+#define P_ATTR(ACT_, WT_)                                                                                               \
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_planes_kernel<1, ACT_, WT_>),                 \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh1));                            \
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_planes_kernel<2, ACT_, WT_, MF_>),            \
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_planes_kernel<2, ACT_, WT_>),                 \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh2));
         P_FOREACH(P_ATTR)
 #undef P_ATTR
-#define P_ATTR_A(MF_, ABL_) STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_planes_kernel<1, 0, true, MF_, ABL_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh1));
-        P_ATTR_A(0, 1) P_ATTR_A(0, 2) P_ATTR_A(1, 1) P_ATTR_A(1, 2) P_ATTR_A(0, 3) P_ATTR_A(0, 4) P_ATTR_A(0, 5) P_ATTR_A(0, 6) P_ATTR_A(0, 7)
-#undef P_ATTR_A
         attr_set = true;
     }
-#define P_LAUNCH2(ACT_, WT_, MF_)                                                                                       \
+#define P_LAUNCH(ACT_, WT_)                                                                                             \
     {                                                                                                                   \
-        if (a.A_lo) hipLaunchKernelGGL((gemm_planes_kernel<2, ACT_, WT_, MF_>), grid, block, sh2, s, p);                 \
-        else hipLaunchKernelGGL((gemm_planes_kernel<1, ACT_, WT_, MF_>), grid, block, sh1, s, p);                        \
+        if (a.A_lo) hipLaunchKernelGGL((gemm_planes_kernel<2, ACT_, WT_>), grid, block, sh2, s, p);                      \
+        else hipLaunchKernelGGL((gemm_planes_kernel<1, ACT_, WT_>), grid, block, sh1, s, p);                             \
     }
-#define P_LAUNCH(ACT_, WT_) { if (mf_env) P_LAUNCH2(ACT_, WT_, 1) else P_LAUNCH2(ACT_, WT_, 0) }
-    if (ablate && a.act == 0 && a.w_tiled && !a.A_lo) {
-        if (mf_env == 0 && ablate == 3) hipLaunchKernelGGL((gemm_planes_kernel<1, 0, true, 0, 3>), grid, block, sh1, s, p);
-        else if (mf_env == 0 && ablate == 4) hipLaunchKernelGGL((gemm_planes_kernel<1, 0, true, 0, 4>), grid, block, sh1, s, p);
-        else if (mf_env == 0 && ablate == 5) hipLaunchKernelGGL((gemm_planes_kernel<1, 0, true, 0, 5>), grid, block, sh1, s, p);
-        else if (mf_env == 0 && ablate == 6) hipLaunchKernelGGL((gemm_planes_kernel<1, 0, true, 0, 6>), grid, block, sh1, s, p);
-        else if (mf_env == 0 && ablate == 7) hipLaunchKernelGGL((gemm_planes_kernel<1, 0, true, 0, 7>), grid, block, sh1, s, p);
-        else if (mf_env == 0 && ablate == 1) hipLaunchKernelGGL((gemm_planes_kernel<1, 0, true, 0, 1>), grid, block, sh1, s, p);
-        else if (mf_env == 0) hipLaunchKernelGGL((gemm_planes_kernel<1, 0, true, 0, 2>), grid, block, sh1, s, p);
-        else if (ablate == 1) hipLaunchKernelGGL((gemm_planes_kernel<1, 0, true, 1, 1>), grid, block, sh1, s, p);
-        else hipLaunchKernelGGL((gemm_planes_kernel<1, 0, true, 1, 2>), grid, block, sh1, s, p);
-    } else if (a.w_tiled) {
+    if (a.w_tiled) {
         switch (a.act) {
             case 0: P_LAUNCH(0, true) break;
             case 1: P_LAUNCH(1, true) break;
@@ -757,7 +720,6 @@ int launch_gemm_planes(const stair_gemm_planes_args &a, hipStream_t s) {
         }
     }
 #undef P_LAUNCH
-#undef P_LAUNCH2
 #undef P_FOREACH
     STAIR_LAUNCH_CHECK();
     return 0;

@@ -78,8 +78,6 @@ __device__ __forceinline__ bf16x8 join8(v2u a, v2u b) {
 
 }  // namespace
 
-// ABL (diagnostic builds only, STAIR_TN_TR_ABLATE): 1 = no dG loads / splits / writes, 2 = no fragment reads / MFMAs, 3 = no DMA of X
-template <int ABL>
 __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
     extern __shared__ __attribute__((aligned(16))) char tl[];      // [3 stages][3 planes][2 halves][32 rows][256 B]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -143,7 +141,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char *)tl;
     auto issue_x = [&](int s) {                                    // stage s of this slab -> ring slot s % 3
-        if (ABL == 3) return;
         const unsigned st = lds0 + (s % TR_NST) * TR_STAGE;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -158,13 +155,11 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
     // dG goes through ordinary loads: hipcc counts them and waits for exactly the set it is about to split.  (X's DMA is asm
     // and therefore NOT counted by hipcc: its counted waits for dG may leave fewer operations in flight than they say, never more.)
     auto load_g = [&](int s, v4f (&g)[4]) {
-        if (ABL == 1) return;
         const float *src = g_base + (int64_t)s * TR_ROWS * p.lda + g_src;
 #pragma unroll
         for (int i = 0; i < 4; ++i) g[i] = *(const __attribute__((address_space(1))) v4f *)(src + 4 * i);
     };
     auto write_g = [&](int s, const v4f (&g)[4]) {
-        if (ABL == 1) return;
         const unsigned st = lds0 + (s % TR_NST) * TR_STAGE;
         bf16x8 hi[2], lo[2];
 #pragma unroll
@@ -181,7 +176,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
         lds_write16<TR_PLANE>(st + g_dst1, __builtin_bit_cast(v4u, lo[1]));
     };
     auto compute = [&](int s) {
-        if (ABL == 2) return;
         const unsigned st = lds0 + (s % TR_NST) * TR_STAGE;
 #define TR_KSTEP(KS_)                                                                                                     \
         {                                                                                                                 \
@@ -234,8 +228,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
         // g_next holds dG(s+1) (in flight or landed); g_next2 is free and receives dG(s+2)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's ds_writes of dG(s) are done
         // X(s) has landed once at most the 6 operations issued after its DMA -- dG(s+1) and X(s+1) -- are outstanding
-        if (ABL == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -251,8 +244,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
     }
     // stage S - 2: nothing left to issue
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (ABL == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -287,8 +279,7 @@ int launch_gemm_tn_tr(const stair_gemm_tn_args &a, hipStream_t s) { return launc
 // scratch (8 * N * K floats, needs ldc == K): the slabs' partial products are stored there and queued for the fixed-order reduction
 // of csrc/gemm_tn_x3tr.hip (tn_x3tr_flush on the same stream adds them to C): no atomics, the same sum every run
 int launch_gemm_tn_tr_slabs(const stair_gemm_tn_args &a, float *scratch, hipStream_t s) {
-    static const bool on = [] { const char *e = getenv("STAIR_GEMM_TN_TR"); return !(e && e[0] == '0'); }();
-    if (!on || !a.b_is_bf16 || a.row_scale || a.b_gidx || a.colsum || a.colsum2) return -1;
+    if (!a.b_is_bf16 || a.row_scale || a.b_gidx || a.colsum || a.colsum2) return -1;
     if (a.rows_per_group != 1 && a.b_gstride != (int64_t)a.rows_per_group * a.ldb) return -1;
     if (a.N % 256 || a.K % 256 || a.M % (8 * 64) || a.M < 2048) return -1;        // >= 4 stages per slab; measured down to M = 2048 (32 questions)
     if (32 * a.lda + 256 >= (1ll << 31) || 32 * a.ldb + 256 >= (1ll << 31)) return -1;
@@ -304,19 +295,12 @@ int launch_gemm_tn_tr_slabs(const stair_gemm_tn_args &a, float *scratch, hipStre
     const size_t shmem = (size_t)TR_NST * TR_STAGE;
     static bool attr_set = false;
     if (!attr_set) {
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_tr_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_tr_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_tr_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_tr_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_tr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
         attr_set = true;
     }
-    static const int abl = [] { const char *e = getenv("STAIR_TN_TR_ABLATE"); return e ? atoi(e) : 0; }();     // timing experiments: wrong results
     const dim3 grid(8 * p.tilesN * p.tilesK);
     STAIR_ACCT_MFMA("gemm_tn_tr", (int64_t)a.M * a.N * 4 + (int64_t)a.M * a.K * 2 + (int64_t)a.N * a.K * 4, 2ll * a.M * a.N * a.K);
-    if (abl == 1) hipLaunchKernelGGL(gemm_tn_tr_kernel<1>, grid, dim3(512), shmem, s, p);
-    else if (abl == 2) hipLaunchKernelGGL(gemm_tn_tr_kernel<2>, grid, dim3(512), shmem, s, p);
-    else if (abl == 3) hipLaunchKernelGGL(gemm_tn_tr_kernel<3>, grid, dim3(512), shmem, s, p);
-    else hipLaunchKernelGGL(gemm_tn_tr_kernel<0>, grid, dim3(512), shmem, s, p);
+    hipLaunchKernelGGL(gemm_tn_tr_kernel, grid, dim3(512), shmem, s, p);
     STAIR_LAUNCH_CHECK();
     if (p.P) return tn_x3tr_queue(p.P, a.C, 8, (int)((int64_t)a.N * a.K / 4), s);
     return 0;

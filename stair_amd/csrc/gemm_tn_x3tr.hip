@@ -295,8 +295,7 @@ int tn_x3tr_slabs(int64_t M) {                                       // slabs of
 int64_t tn_x3tr_scratch_floats(int64_t M, int64_t N, int64_t K) { return (int64_t)tn_x3tr_slabs(M) * (N * K + N); }
 
 bool tn_x3tr_takes(const stair_gemm_tn_args &a) {
-    static const bool on = [] { const char *e = getenv("STAIR_GEMM_TN_X3TR"); return !(e && e[0] == '0'); }();
-    if (!on || a.b_is_bf16 || matmul_mode() != STAIR_MATMUL_BF16X3) return false;
+    if (a.b_is_bf16 || matmul_mode() != STAIR_MATMUL_BF16X3) return false;
     if (a.N % 256 || a.K % 4 || a.K < 4 || a.M % XT_ROWS || a.M < 2 * XT_ROWS || a.rows_per_group < 1) return false;
     if (a.rows_per_group % XT_ROWS && (a.rows_per_group != 1 || a.b_gidx || a.row_scale || a.b_gstride != a.ldb)) return false;   // groups of whole stages, or a plain row matrix
     if (a.K % 128 && (a.b_gidx || a.row_scale)) return false;

@@ -63,12 +63,11 @@ __device__ __forceinline__ int lds_unit(int seq, int chunk) { return (seq * 32 +
 
 }  // namespace
 
-// NT: sequence tiles (of 32) a group carries through the steps together, 1..3.  The hand-off of a tile is spread over the
-// computes of the other tiles: h(t) of tile x is PUBLISHED (sc1 stores) at the end of its own compute, FLAGGED in the
-// middle of the next compute (by then the stores have drained: the wait costs nothing), its slab loads are ISSUED at the
-// start of the compute after that and WRITTEN to LDS at its end -- with NT = 3 that is exactly when tile x is next, so no
-// phase waits for memory; NT = 2 and 1 expose part of the latency (small batches).
-template <bool TRAIN, int NT, bool PROF>
+// NT: sequence tiles (of 32) a group carries through the steps together, 1 or 2.  With two tiles the hand-off of a tile
+// overlaps the compute of the other one: h(t) of tile x is PUBLISHED (sc1 stores) at the end of its own compute and
+// FLAGGED in the middle of the next compute (by then the stores have drained: the wait costs nothing); its slab loads
+// follow that compute, so part of the latency stays exposed.
+template <bool TRAIN, int NT>
 __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const int b, char *hl) {
     // hl: [NT tiles][2 planes][32 seq][256] bf16, swizzled
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -104,18 +103,6 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
     auto slab_off = [&](unsigned ep, int x) { return (int)(((int64_t)((ep & 1) * G + g) * NT + x) * TILE_BYTES); };
     auto flag_of = [&](int x, int wg) { return (gu32 *)(p.flags + ((g * NT + x) * CP + wg) * FLAG_STRIDE); };
 
-    // diagnostic build only (PROF): cycles per phase of wave 0 of workgroup 0, summed over the launch, into err[8..]
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
-    auto stamp = [&](int slot) {
-        if (PROF) {
-            __builtin_amdgcn_sched_barrier(0);
-            unsigned long long tnow;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tnow)::"memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if (slot >= 0) prof[slot] += tnow - tlast;
-            tlast = tnow;
-        }
-    };
     unsigned ebase = 0;                                            // epochs published before this chunk (same on all 4 workgroups)
     bool dead = false;                                             // a spin timed out: stop waiting, drain
     for (int chunk = gl; chunk * SPG < p.n; chunk += p.gpd) {
@@ -137,12 +124,11 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
         __syncthreads();
 
         v4u inflight[4];                                           // slab of the tile being fetched (16 B x 4 per thread)
-        // Every wave checks the 4 flags of tile x for epoch ep itself (lanes 0..3; `seen` is a value loaded earlier, behind
-        // the previous compute, so in the steady state nothing is waited for), then issues the sc1 loads of its share of
+        // Every wave checks the 4 flags of tile x for epoch ep itself (lanes 0..3), then issues the sc1 loads of its share of
         // the slab: no workgroup barrier between the poll and the loads (MI355X_MICROARCH.md "Valid forms": the wave that
         // polled loads after its poll has matched).
-        auto fetch_issue = [&](const int x, const unsigned ep, unsigned seen) {
-            stamp(-1);
+        auto fetch_issue = [&](const int x, const unsigned ep) {
+            unsigned seen = 0;
             if (!dead) {
                 const gu32 *fl = flag_of(x, lane & 3);
                 unsigned spins = 0;
@@ -164,23 +150,17 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 inflight[i] = __builtin_amdgcn_raw_buffer_load_b128(xh_rs, so + (tid + 512 * i) * 16, 0, 16);     // aux 16 = sc1
-            stamp(7);                                              // 7: poll + slab load issue
         };
         auto fetch_land = [&](const int x) {
-            stamp(-1);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int u = tid + 512 * i;                       // 16-byte unit: plane = u >> 10, seq = (u >> 5) & 31, chunk = u & 31
                 *reinterpret_cast<v4u *>(hl + x * TILE_BYTES + (u >> 10) * (32 * CH * 2) + lds_unit((u >> 5) & 31, u & 31)) = inflight[i];
             }
-            stamp(5);                                              // 5: slab wait + ds_write
             __syncthreads();
-            stamp(6);                                              // 6: barrier
         };
         // one tile-step: gates = W h(t-1) + xproj(t); [flag the tile published one compute ago]; cell update; publish h(t)
-        unsigned peek = 0;                                         // flag value of the tile fetched next, loaded behind the cell update
-        auto compute = [&](const int x, const int t, const int flag_x, const unsigned flag_ep, const int peek_x) {
-            stamp(-1);
+        auto compute = [&](const int x, const int t, const int flag_x, const unsigned flag_ep) {
             const bool active = t < len[x];
             const int tt = dir == 0 ? t : len[x] - 1 - t;
             const int64_t row = off[x] + (active ? tt : 0);
@@ -205,10 +185,8 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[s], bl, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[s], bh, acc, 0, 0, 0);
             }
-            stamp(0);                                              // 0: xproj issue + MFMA chain
             // every older store of this wave has drained by now (issued one MFMA chain ago), the xproj loads are due anyway
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            stamp(1);                                              // 1: vmcnt(0)
             // No workgroup barrier here: each wave, after ITS drain, adds to a counter in LDS and the wave whose add comes
             // last stores the flag (MI355X_MICROARCH.md "Valid forms", condition 3).  A wave that is through with its MFMAs
             // goes on to its cell update (VALU) while its SIMD partner still multiplies.
@@ -220,8 +198,6 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
                     __hip_atomic_store(flag_of(flag_x, j), flag_ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
-            stamp(2);                                              // 2: arrival counter / flag
-            if (peek_x >= 0) peek = __hip_atomic_load(flag_of(peek_x, lane & 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (active) {
                 v4f si, sf, tg, so, cn, hv;
 #pragma unroll
@@ -251,7 +227,6 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
                     *(__attribute__((address_space(1))) v4f *)(p.cbuf + row * 2 * Hh + dir * Hh + U0) = cn;
                 }
             }
-            stamp(3);                                              // 3: flag, peek, cell update, out stores
             // publish (finished sequences re-publish their last h): 8 bytes per plane, write-through
             char *slab = p.xh + slab_off(ebase + t + 1, x);
             const int so_ = r * (CH * 2) + U0 * 2;
@@ -259,11 +234,9 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
                                __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store((gu64 *)(slab + 32 * CH * 2 + so_), ((unsigned long long)pl_[1] << 32) | pl_[0], __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
-            stamp(4);                                              // 4: publish
         };
-        // publish -> flag lags one compute; flag -> loads issued lags one more; landed one compute later.
-        // Schedule of compute k = t * NT + x (tile x, step t): before it, issue the fetch of tile (x + 1) % NT [its epoch:
-        // the last one it published]; inside it, flag tile (x - 1) % NT; after it, land the fetch.
+        // publish -> flag lags one compute.  Schedule of compute k = t * NT + x (tile x, step t): inside it, flag tile
+        // (x - 1) % NT; after it, fetch tile (x + 1) % NT [its epoch: the last one it published].
         const int total = lmax * NT;
         for (int t = 0; t < lmax; ++t) {
 #pragma unroll
@@ -277,27 +250,19 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
                     // flagged inside this compute: the tile computed just before (k - 1)
                     const int xq = (x + NT - 1) % NT;
                     const int tq = x == 0 ? t - 1 : t;
-                    if (NT >= 3) {
-                        // tile xf was flagged one compute ago: issue its loads now, land them behind this compute.  The flags
-                        // of the tile fetched before the NEXT compute (xf + 1, flagged inside this one) are peeked at here.
-                        if (do_fetch) fetch_issue(xf, ebase + tf + 1, peek);
-                        compute(x, t, tq >= 0 ? xq : -1, ebase + tq + 1, (xf + 1) % NT);
-                        if (do_fetch) fetch_land(xf);
-                    } else {
-                        // two tiles: tile xf is flagged inside THIS compute, so its fetch follows it (latency partly exposed)
-                        compute(x, t, tq >= 0 ? xq : -1, ebase + tq + 1, -1);
-                        if (do_fetch) {
-                            fetch_issue(xf, ebase + tf + 1, 0u);
-                            fetch_land(xf);
-                        }
+                    // two tiles: tile xf is flagged inside THIS compute, so its fetch follows it (latency partly exposed)
+                    compute(x, t, tq >= 0 ? xq : -1, ebase + tq + 1);
+                    if (do_fetch) {
+                        fetch_issue(xf, ebase + tf + 1);
+                        fetch_land(xf);
                     }
                 } else {
-                    compute(0, t, -1, 0, -1);
+                    compute(0, t, -1, 0);
                     // one tile: nothing to hide behind; drain, flag, fetch right away
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __syncthreads();
                     if (tid == 0) __hip_atomic_store(flag_of(0, j), ebase + t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (t + 1 < lmax) { fetch_issue(0, ebase + t + 1, 0u); fetch_land(0); }
+                    if (t + 1 < lmax) { fetch_issue(0, ebase + t + 1); fetch_land(0); }
                 }
             }
         }
@@ -313,14 +278,12 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
         ebase += lmax + 1;
         __syncthreads();                                           // LDS is re-zeroed for the next chunk
     }
-    if (PROF && b == 0 && tid == 0)
-        for (int i = 0; i < 8; ++i) reinterpret_cast<unsigned long long *>(p.err + 8)[i] = prof[i];
 }
 
-template <bool TRAIN, int NT, bool PROF = false>
+template <bool TRAIN, int NT>
 __global__ __launch_bounds__(512, 1) void lstm_rec_coop_kernel(CoopParams p) {
     extern __shared__ __attribute__((aligned(16))) char hl_dyn[];
-    lstm_rec_coop_body<TRAIN, NT, PROF>(p, (int)blockIdx.x, hl_dyn);
+    lstm_rec_coop_body<TRAIN, NT>(p, (int)blockIdx.x, hl_dyn);
 }
 
 // Two recurrences in ONE launch (the video and the text encoder of a batch small enough that both sets of groups are
@@ -330,11 +293,10 @@ __global__ __launch_bounds__(512, 1) void lstm_rec_coop_kernel(CoopParams p) {
 template <bool TRAIN>
 __global__ __launch_bounds__(512, 1) void lstm_rec_coop_pair_kernel(CoopParams a, CoopParams b, int nb_a) {
     extern __shared__ __attribute__((aligned(16))) char hl_dyn[];
-    if ((int)blockIdx.x < nb_a) lstm_rec_coop_body<TRAIN, 1, false>(a, (int)blockIdx.x, hl_dyn);
-    else lstm_rec_coop_body<TRAIN, 1, false>(b, (int)blockIdx.x - nb_a, hl_dyn);
+    if ((int)blockIdx.x < nb_a) lstm_rec_coop_body<TRAIN, 1>(a, (int)blockIdx.x, hl_dyn);
+    else lstm_rec_coop_body<TRAIN, 1>(b, (int)blockIdx.x - nb_a, hl_dyn);
 }
 
-// tiles per group: 3 once the batch fills most of the chip that way, else as many as it takes to use all groups
 // Per-DEVICE launch state (a process may drive several GPUs): CU count, "dynamic LDS attribute set" and the occupancy the
 // runtime reports for each kernel variant.  STAIR_LSTM_COOP_MAX_BLOCKS caps the number of workgroups a cooperative launch may
 // use (tests: forces the smaller geometries and the fallback to the one-workgroup kernels).
@@ -358,7 +320,7 @@ static CoopDevice &coop_device() {
 }
 static int g_coop_cap = -1;          // stair_lstm_coop_limit; -1 = STAIR_LSTM_COOP_MAX_BLOCKS or no cap
 static int coop_block_cap() {
-    static const int env_cap = [] { const char *e = getenv("STAIR_LSTM_COOP_MAX_BLOCKS"); return e ? std::max(0, atoi(e)) : 1 << 30; }();
+    static const int env_cap = std::max(0, env_int("STAIR_LSTM_COOP_MAX_BLOCKS", 1 << 30));
     return std::min(g_coop_cap >= 0 ? g_coop_cap : env_cap, coop_device().cus);
 }
 static int coop_cu_count() { return coop_block_cap(); }
@@ -381,10 +343,9 @@ static bool coop_fits(K kernel, int variant, int blocks, size_t shmem) {
 }
 
 static void coop_geometry(int n, int &nt, int &gpd) {
-    static const int force = [] { const char *e = getenv("STAIR_LSTM_COOP_TILES"); return e ? atoi(e) : 0; }();
     // measured (profiles/r02_b_lstm_coop.txt): one tile per group while every tile gets a group of its own (n <= 1024), then two;
     // three tiles need more registers than a wave has (spills) and lose
-    nt = force >= 1 && force <= 3 ? force : (n > 32 * 32 ? 2 : 1);
+    nt = n > 32 * 32 ? 2 : 1;
     // every workgroup of the launch must be resident at once (they wait for each other): groups per direction <= CUs / 8
     // (2 directions x 4 workgroups), i.e. 32 on the 256-CU part, fewer on a partitioned device; the cap keeps whole XCD rounds
     const int cap = std::max(1, std::min(32, coop_cu_count() / 8));
@@ -395,14 +356,14 @@ static void coop_geometry(int n, int &nt, int &gpd) {
 static int coop_blocks(int gpd) { return 32 * ((2 * gpd + 7) / 8); }
 
 int64_t lstm_coop_ws_bytes(int n) {
-    // sized for the largest geometry (3 tiles, 32 groups per direction): the choice above may change with n
+    // sized for 3 tiles and 32 groups per direction, more than any geometry above needs: the size does not depend on n
     const int G = 64;
     (void)n;
     return (int64_t)2 * G * 3 * TILE_BYTES + (int64_t)(G * 3 * CP * FLAG_STRIDE + 64) * 4;
 }
 
 bool lstm_coop_usable(int Hh) {
-    static const bool on = [] { const char *e = getenv("STAIR_LSTM_COOP"); return !(e && e[0] == '0'); }();
+    static const bool on = env_int("STAIR_LSTM_COOP", 1) != 0;
     // even the smallest launch (one group per direction) needs 32 co-resident workgroups
     return on && Hh == CH && matmul_mode() != STAIR_MATMUL_F32 && coop_block_cap() >= 32;
 }
@@ -437,11 +398,8 @@ static void coop_attrs() {
     bool &attr_set = coop_device().rec_attrs;
     if (attr_set) return;
 #define C_ATTR(TR_, NT_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_kernel<TR_, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, NT_ * TILE_BYTES + 64);
-    C_ATTR(false, 1) C_ATTR(false, 2) C_ATTR(false, 3) C_ATTR(true, 1) C_ATTR(true, 2) C_ATTR(true, 3)
+    C_ATTR(false, 1) C_ATTR(false, 2) C_ATTR(true, 1) C_ATTR(true, 2)
 #undef C_ATTR
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_kernel<false, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 * TILE_BYTES + 64);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_kernel<false, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TILE_BYTES + 64);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_kernel<false, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * TILE_BYTES + 64);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_pair_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 * TILE_BYTES + 64);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_pair_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 * TILE_BYTES + 64);
     attr_set = true;
@@ -459,24 +417,15 @@ int launch_lstm_rec_coop(const stair_lstm_args &a, hipStream_t s) {
         const size_t sh = (size_t)nt * TILE_BYTES + 64;
         const bool tr = a.cbuf != nullptr;
         const bool ok = nt == 1 ? (tr ? coop_fits(&lstm_rec_coop_kernel<true, 1>, 0, nb, sh) : coop_fits(&lstm_rec_coop_kernel<false, 1>, 1, nb, sh))
-                      : nt == 2 ? (tr ? coop_fits(&lstm_rec_coop_kernel<true, 2>, 2, nb, sh) : coop_fits(&lstm_rec_coop_kernel<false, 2>, 3, nb, sh))
-                                : (tr ? coop_fits(&lstm_rec_coop_kernel<true, 3>, 4, nb, sh) : coop_fits(&lstm_rec_coop_kernel<false, 3>, 5, nb, sh));
+                                : (tr ? coop_fits(&lstm_rec_coop_kernel<true, 2>, 2, nb, sh) : coop_fits(&lstm_rec_coop_kernel<false, 2>, 3, nb, sh));
         if (!ok) return -1;
     }
     if (int rc = coop_prepare(a, s, p, nt, blocks)) return rc;
-    static const bool prof = [] { const char *e = getenv("STAIR_LSTM_COOP_PROF"); return e && e[0] == '1'; }();   // diagnostic build, never the product
-    if (prof && !a.cbuf) {
-        if (nt == 1) hipLaunchKernelGGL((lstm_rec_coop_kernel<false, 1, true>), dim3(blocks), dim3(512), 1 * TILE_BYTES + 64, s, p);
-        else if (nt == 2) hipLaunchKernelGGL((lstm_rec_coop_kernel<false, 2, true>), dim3(blocks), dim3(512), 2 * TILE_BYTES + 64, s, p);
-        else hipLaunchKernelGGL((lstm_rec_coop_kernel<false, 3, true>), dim3(blocks), dim3(512), 3 * TILE_BYTES + 64, s, p);
-        STAIR_LAUNCH_CHECK();
-        return 0;
-    }
     STAIR_ACCT_MFMA("lstm_rec_coop", 0, 2ll * 2 * a.rows * 4 * CH * CH);
 #define C_LAUNCH(NT_)                                                                                                              \
     if (a.cbuf) hipLaunchKernelGGL((lstm_rec_coop_kernel<true, NT_>), dim3(blocks), dim3(512), NT_ * TILE_BYTES + 64, s, p);        \
     else hipLaunchKernelGGL((lstm_rec_coop_kernel<false, NT_>), dim3(blocks), dim3(512), NT_ * TILE_BYTES + 64, s, p);
-    if (nt == 1) { C_LAUNCH(1) } else if (nt == 2) { C_LAUNCH(2) } else { C_LAUNCH(3) }
+    if (nt == 1) { C_LAUNCH(1) } else { C_LAUNCH(2) }
 #undef C_LAUNCH
     STAIR_LAUNCH_CHECK();
     return 0;
@@ -485,19 +434,16 @@ int launch_lstm_rec_coop(const stair_lstm_args &a, hipStream_t s) {
 // Both recurrences in one launch when each has one sequence tile per group and all their workgroups are co-resident;
 // -1: not applicable (the caller runs them one after the other).  a and b need DISJOINT coop_ws regions.
 int launch_lstm_rec_coop_pair(const stair_lstm_args &a, const stair_lstm_args &b, hipStream_t s) {
-    static const bool on = [] { const char *e = getenv("STAIR_LSTM_COOP_PAIR"); return !(e && e[0] == '0'); }();
-    if (!on || !a.coop_ws || !b.coop_ws || a.coop_ws == b.coop_ws || !lstm_coop_usable(a.Hh) || !lstm_coop_usable(b.Hh)) return -1;
+    if (!a.coop_ws || !b.coop_ws || a.coop_ws == b.coop_ws || !lstm_coop_usable(a.Hh) || !lstm_coop_usable(b.Hh)) return -1;
     if ((a.cbuf != nullptr) != (b.cbuf != nullptr) || a.n <= 0 || b.n <= 0) return -1;
     int nta = 1, ntb = 1, ga = 0, gb = 0;
     coop_geometry(a.n, nta, ga);
     coop_geometry(b.n, ntb, gb);
     if (nta != 1 || ntb != 1) return -1;
     if (coop_blocks(ga) + coop_blocks(gb) > coop_cu_count()) return -1;
-    static const bool prof = [] { const char *e = getenv("STAIR_LSTM_COOP_PROF"); return e && e[0] == '1'; }();
-    if (prof) return -1;
     coop_attrs();
-    if (a.cbuf ? !coop_fits(&lstm_rec_coop_pair_kernel<true>, 6, coop_blocks(ga) + coop_blocks(gb), TILE_BYTES + 64)
-               : !coop_fits(&lstm_rec_coop_pair_kernel<false>, 7, coop_blocks(ga) + coop_blocks(gb), TILE_BYTES + 64)) return -1;
+    if (a.cbuf ? !coop_fits(&lstm_rec_coop_pair_kernel<true>, 4, coop_blocks(ga) + coop_blocks(gb), TILE_BYTES + 64)
+               : !coop_fits(&lstm_rec_coop_pair_kernel<false>, 5, coop_blocks(ga) + coop_blocks(gb), TILE_BYTES + 64)) return -1;
     CoopParams pa, pb;
     int blocks_a = 0, blocks_b = 0;
     if (int rc = coop_prepare(a, s, pa, nta, blocks_a)) return rc;
@@ -803,7 +749,7 @@ int launch_lstm_bwd_coop(const stair_lstm_bwd_args &a, hipStream_t s) {
         int gpd = 0;
         coop_bwd_geometry(a.n, nt, gpd);
         const size_t sh = (size_t)nt * TILE_BYTES + 64;
-        if (nt == 1 ? !coop_fits(&lstm_bwd_coop_kernel<1>, 8, coop_blocks(gpd), sh) : !coop_fits(&lstm_bwd_coop_kernel<2>, 9, coop_blocks(gpd), sh)) return -1;
+        if (nt == 1 ? !coop_fits(&lstm_bwd_coop_kernel<1>, 6, coop_blocks(gpd), sh) : !coop_fits(&lstm_bwd_coop_kernel<2>, 7, coop_blocks(gpd), sh)) return -1;
     }
     if (int rc = coop_bwd_prepare(a, s, p, nt, blocks)) return rc;
     STAIR_ACCT_MFMA("lstm_bwd_coop", 0, 2ll * 2 * a.rows * 4 * CH * CH);
@@ -815,8 +761,7 @@ int launch_lstm_bwd_coop(const stair_lstm_bwd_args &a, hipStream_t s) {
 
 // BPTT of two encoders in one launch; -1: not applicable.  a and b need DISJOINT coop_ws regions.
 int launch_lstm_bwd_coop_pair(const stair_lstm_bwd_args &a, const stair_lstm_bwd_args &b, hipStream_t s) {
-    static const bool on = [] { const char *e = getenv("STAIR_LSTM_COOP_PAIR"); return !(e && e[0] == '0'); }();
-    if (!on || !a.coop_ws || !b.coop_ws || a.coop_ws == b.coop_ws || !lstm_coop_usable(a.Hh) || !lstm_coop_usable(b.Hh)) return -1;
+    if (!a.coop_ws || !b.coop_ws || a.coop_ws == b.coop_ws || !lstm_coop_usable(a.Hh) || !lstm_coop_usable(b.Hh)) return -1;
     if (a.n <= 0 || b.n <= 0) return -1;
     int nta = 1, ntb = 1, ga = 0, gb = 0;
     coop_geometry(a.n, nta, ga);
@@ -824,7 +769,7 @@ int launch_lstm_bwd_coop_pair(const stair_lstm_bwd_args &a, const stair_lstm_bwd
     if (nta != 1 || ntb != 1) return -1;
     if (coop_blocks(ga) + coop_blocks(gb) > coop_cu_count()) return -1;
     coop_bwd_attrs();
-    if (!coop_fits(&lstm_bwd_coop_pair_kernel, 10, coop_blocks(ga) + coop_blocks(gb), TILE_BYTES + 64)) return -1;
+    if (!coop_fits(&lstm_bwd_coop_pair_kernel, 8, coop_blocks(ga) + coop_blocks(gb), TILE_BYTES + 64)) return -1;
     CoopBwdParams pa, pb;
     int blocks_a = 0, blocks_b = 0;
     if (int rc = coop_bwd_prepare(a, s, pa, nta, blocks_a)) return rc;

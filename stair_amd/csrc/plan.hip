@@ -53,10 +53,6 @@ struct stair_ctx {
     std::vector<const float *> ptr;
     std::vector<float *> gptr;           // gradient buffers (training), same ids
     std::unordered_map<std::string, int> by_name;
-    // backward pass: the per-weight gradient products are leaves of the graph, they run on a second stream beside BPTT
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_fork_enc = nullptr, ev_join_enc = nullptr;     // the text encoder's backward beside the video encoder's
     // 64-bit fixed-point shadows of the weight gradients (common.h det_shadow): owned by the context, all zero between two backward
     // passes (the flush empties what it adds), so a pass does not start by clearing 8 bytes per parameter; `dirty`: a pass that did not
     // reach its end left something behind -> the next one clears first
@@ -66,11 +62,6 @@ struct stair_ctx {
     Policy policy;                       // stair_ctx_set_option: this context's overrides of the process-wide settings
     ~stair_ctx() {
         if (gshadow) (void)hipFree(gshadow);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-        if (ev_fork_enc) (void)hipEventDestroy(ev_fork_enc);
-        if (ev_join_enc) (void)hipEventDestroy(ev_join_enc);
-        if (side) (void)hipStreamDestroy(side);
     }
 
     void add(const std::string &name, int64_t n) {
@@ -229,12 +220,9 @@ namespace {
 constexpr int64_t kSplitKFloats = 16ll * 64 * 128 * 128;     // split-K scratch: 16 K pieces x 64 output tiles of 128 x 128
 
 // how a fused tile launch deals its tiles out: the self-resetting atomic queue (default) or a static round robin
-// (stair_set_tile_queue(0) / STAIR_TILE_QUEUE=0); both run eagerly and inside a stream capture
-int g_tile_queue = -1;
-bool tile_queue_on() {
-    static const bool env_on = [] { const char *e = getenv("STAIR_TILE_QUEUE"); return !(e && e[0] == '0'); }();
-    return policy_or(STAIR_OPT_TILE_QUEUE, g_tile_queue >= 0 ? g_tile_queue : (env_on ? 1 : 0)) != 0;
-}
+// (stair_set_tile_queue(0)); both run eagerly and inside a stream capture
+int g_tile_queue = 1;
+bool tile_queue_on() { return policy_or(STAIR_OPT_TILE_QUEUE, g_tile_queue) != 0; }
 
 // Diagnostic twin of the tile operator's work queue (stair_debug_queue_probe): the same ticket protocol, no tile work, every
 // ticket a workgroup sees is RECORDED instead of used as an index -- safe whatever the words hold.
@@ -682,13 +670,13 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     Builder B{pl};
     std::vector<int> stack;
     const auto t_begin = std::chrono::steady_clock::now();
+    static const bool debug = env_int("STAIR_PLAN_DEBUG", 0) != 0;         // build statistics to stderr
     // Common-subexpression sharing across the batch (module_net.py:100-106 evaluates every node of every question; a node
     // whose operands are the encoded clip, keyword strings, identical question spans or other such nodes has the SAME value
     // wherever it occurs -- in another question about the same clip, or twice in one program).  key[i] names the computation
     // of token i ("" = not shareable); the first node with a key is computed, later ones alias its slot.  Filter ignores its
     // tensor keyword (its attention is identically 1, modules.py:354,373), so that operand does not enter the key.
-    static const bool cse_env = [] { const char *e = getenv("STAIR_PLAN_CSE"); return !(e && e[0] == '0'); }();
-    const bool cse_on = cse_env && !(flags & STAIR_PLAN_NO_CSE);
+    const bool cse_on = !(flags & STAIR_PLAN_NO_CSE);
     // keys are interned: a computation is (tag, operand key ids) -> a small integer id; id 0 = not shareable
     struct CseKey {
         int32_t v[4];
@@ -1004,7 +992,7 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
         pl->roots[q] = root.slot;
     }
     pl->rows_q = q_off[n];
-    if (getenv("STAIR_PLAN_DEBUG"))
+    if (debug)
         fprintf(stderr, "cse: %ld inserts, %ld extra probes, cap %zu; scan %.3f ms\n", cse_probe_inserts, cse_probe_steps, cap,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
 
@@ -1289,12 +1277,12 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
         pl->o_gExtra = take(I, 64);
     }
     pl->total = align_up(o, 64);
-    if (getenv("STAIR_PLAN_DEBUG") && pl->train) {
+    if (debug && pl->train) {
         fprintf(stderr, "weight-gradient regions (instances of T rows):");
         for (int w = 0; w < WF_COUNT; ++w) fprintf(stderr, " %ld", (long)pl->wg_rows[w]);
         fprintf(stderr, "\n");
     }
-    if (getenv("STAIR_PLAN_DEBUG"))
+    if (debug)
         fprintf(stderr, "plan build total %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
     *out = plp.release();
     return 0;
@@ -1491,23 +1479,13 @@ int resolve(const stair_ctx *ctx, Weights &W, bool grads) {
     return 0;
 }
 
-// Where the fused tile operators pay (measured on one box per pair, same build, STAIR_TILE_MLP / STAIR_TILE_TRAIN = 0 against 1;
-// profiles/r03_*):
+// Where the fused tile operators pay (measured on one box per pair, same build, fused against the GEMM sequences; profiles/r03_*):
 //   inference       32 / 128 / 512 / 2048 questions per batch: 1.36 / 1.49 / 2.19 / 5.6-6.1 ms fused, 1.58 / 1.91 / 2.59 / 6.1 ms sequenced
 //   training step   32 / 128 / 512 / 1024 / 2048: 4.47 / 5.34 / 8.01 / 12.08 / 18.50 ms fused, 4.60 / 5.71 / 8.33 / 12.18 / 18.85 ms sequenced
 // (the training figures after two fixes that were worth 2.2 ms at 2048 questions: the backward chain's accumulation as
 // 256-byte wave-instructions instead of 16-byte-strided lanes -- float atomics run at full rate only in that shape -- and
 // every mask load / activation save between layers row-wise through the fp32 staging instead of 32-byte pieces from the
-// accumulator layout).  Fused is the default for both kinds of plan; STAIR_TILE_TRAIN=0 / STAIR_TILE_TRAIN_BWD=0 put a
-// training plan's forward / backward back on the GEMM sequences.
-bool tile_policy(const stair_plan *pl, bool backward = false) {
-    if (!pl->train) return true;
-    static const int force = [] { const char *e = getenv("STAIR_TILE_TRAIN"); return e ? atoi(e) : -1; }();
-    static const int force_bwd = [] { const char *e = getenv("STAIR_TILE_TRAIN_BWD"); return e ? atoi(e) : -1; }();
-    if (backward && force_bwd >= 0) return force_bwd != 0;
-    if (force >= 0) return force != 0;
-    return true;
-}
+// accumulator layout).  Fused is the default for both kinds of plan (stair_set_tile_mlp(0) selects the sequences).
 
 // dense helper: C[g][r] = act(rs * A[g][r] W^T + b)
 thread_local float *g_splitk_ws = nullptr;      // set by stair_plan_run for the duration of the call, on the calling thread
@@ -1533,15 +1511,9 @@ VgProblem vg_fwd(int rows, const float *a, const int32_t *ia, int64_t lda, const
     p.kred = 512; p.W = Wm; p.ldw = ldw; p.bias = bias; p.N = N; p.act = act; p.out = out; p.io = io; p.ldo = ldo;
     return p;
 }
-// STAIR_VEC_GROUP=0 keeps the per-module pack -> GEMM -> reduction sequences (and the tile form for large buckets)
-static bool tile_dropout_on() {
-    static const bool on = [] { const char *e = getenv("STAIR_TILE_DROPOUT"); return !(e && e[0] == '0'); }();
-    return on;
-}
-bool vec_group_on() {
-    static const bool on = [] { const char *e = getenv("STAIR_VEC_GROUP"); return !(e && e[0] == '0'); }();
-    return policy_or(STAIR_OPT_VEC_GROUP, on ? 1 : 0) != 0;
-}
+// the context option STAIR_OPT_VEC_GROUP = 0 keeps the per-module pack -> GEMM -> reduction sequences (and the tile form for large
+// buckets)
+bool vec_group_on() { return policy_or(STAIR_OPT_VEC_GROUP, 1) != 0; }
 
 struct Ptrs {     // workspace views shared by forward and backward
     float *ws, *vec, *map, *att, *tok, *qfeat;
@@ -1624,8 +1596,7 @@ extern "C" int stair_encoders_project(stair_ctx *ctx, const void *video, int32_t
     }
     a.xproj_ws = buf + L.xpv; a.bias_ws = buf + L.bias;
     t.x = question; t.ldx = E; t.rows = (int32_t)question_rows; t.n = 1; t.max_len = (int32_t)question_rows; t.I = E; t.Hh = Hh;
-    static const bool text_planes = [] { const char *e = getenv("STAIR_TEXT_PLANES"); return !(e && e[0] == '0'); }();
-    if (text_planes) { t.wih_planes_ws = buf + L.wplanes_t; t.x_planes_ws = buf + L.xplanes_t; }
+    t.wih_planes_ws = buf + L.wplanes_t; t.x_planes_ws = buf + L.xplanes_t;
     t.xproj_ws = buf + L.xpt; t.bias_ws = buf + L.bias + 4 * H;
     if (int rc = launch_lstm_project(a, s)) return rc;
     return launch_lstm_project(t, s);
@@ -1723,8 +1694,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
             t.w_ih[d] = W.enc[1][4 * d]; t.w_hh[d] = W.enc[1][4 * d + 1];
             t.b_ih[d] = W.enc[1][4 * d + 2]; t.b_hh[d] = W.enc[1][4 * d + 3];
         }
-        static const bool text_planes = [] { const char *e = getenv("STAIR_TEXT_PLANES"); return !(e && e[0] == '0'); }();
-        if (text_planes) { t.wih_planes_ws = pb + pl->o_wplanes_t; t.x_planes_ws = pb + pl->o_xplanes_t; }
+        t.wih_planes_ws = pb + pl->o_wplanes_t; t.x_planes_ws = pb + pl->o_xplanes_t;
         t.xproj_ws = pb + pl->o_xpt; t.bias_ws = pb + pl->o_bias + 4 * H; t.whh_pack_ws = ws + pl->o_wpack + 2 * (int64_t)H * H;
         t.out = tok; t.ldo = H; t.h_n = qfeat;
         t.coop_ws = ws + pl->o_coop2; t.coop_ws_bytes = pl->coop_bytes; t.status = status;
@@ -1748,8 +1718,8 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
 
     // ---- fused per-clip tile operators (csrc/tile_mlp.hip): weights of the buckets that run fused, as fragment-order planes ----
     // (under dropout the tile operators and the grouped vector-level launches stay on: their kernels draw stair_dropout_fwd's bits in their
-    // epilogues; STAIR_TILE_DROPOUT=0: launch-per-layer forms everywhere, as before ABI 6)
-    const bool fused = pl->o_wfrag > 0 && tile_mlp_usable(H, T) && (dp <= 0.0f || tile_dropout_on()) && tile_policy(pl);
+    // epilogues)
+    const bool fused = pl->o_wfrag > 0 && tile_mlp_usable(H, T);
     pl->bits_written = fused && pl->train;
     auto WF = [&](int slot) { return static_cast<const void *>(ws + pl->o_wfrag + (int64_t)slot * H * H); };
     if (fused) {
@@ -1779,7 +1749,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
     // inference 5.61 / 5.73; 128 questions, 13..66 instances: training 5.06 / 5.01 -- one workgroup carries a tile's whole
     // [64 x 1536 x 512] first layer (3 x 17 us) where the split-K GEMM spreads it over 64 workgroups (13 us), so the tile form
     // pays only when a bucket fills several tiles.  STAIR_TILE_VEC = minimum instances per bucket (0: never).
-    const int vec_min = [] { const char *e = getenv("STAIR_TILE_VEC"); return e ? atoi(e) : 128; }();      // read per pass: tests switch it
+    const int vec_min = env_int("STAIR_TILE_VEC", 128);      // read per pass: tests switch it
     // The row-wise Linear layers of a level -- vector-level modules, Filter's dense layer, Localize's keyword rows, the decoder -- as
     // problems of ONE launch before the level's tile operators (first layers, keyword rows) and ONE after them (second layers, the
     // dense layers on the pooled rows): csrc/vec_group.hip.  Takes precedence over the tile form of the vector-level modules.
@@ -2127,10 +2097,9 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
             vg1.clear(); vg2.clear();
             for (size_t k = lo_; k < hi_; ++k) RUN(run_bucket(pl->buckets[k], (int)k, 1));
             if (!vg1.empty()) RUN(launch_vec_group(vg1.data(), (int)vg1.size(), s));
-            static const int merge_max = [] { const char *e = getenv("STAIR_TILE_MERGE"); return e ? std::max(1, std::min(8, atoi(e))) : 8; }();
             const bool use_queue = tile_queue_on();
-            for (size_t q0 = 0; q0 < tile_queue.size(); q0 += merge_max) {
-                const int nq = (int)std::min<size_t>(merge_max, tile_queue.size() - q0);
+            for (size_t q0 = 0; q0 < tile_queue.size(); q0 += 8) {          // launch_tile_mlp_batch takes up to 8 buckets
+                const int nq = (int)std::min<size_t>(8, tile_queue.size() - q0);
                 RUN(launch_tile_mlp_batch(tile_queue.data() + q0, nq, use_queue ? tile_ctr : nullptr, s));
             }
             if (!vg2.empty()) RUN(launch_vec_group(vg2.data(), (int)vg2.size(), s));
@@ -2178,11 +2147,6 @@ struct DetState {
     std::vector<char> touched;
 };
 thread_local DetState g_det;
-
-bool det_enabled() {
-    static const bool on = [] { const char *e = getenv("STAIR_DETERMINISTIC"); return !(e && e[0] == '0'); }();
-    return on;
-}
 
 struct FxFlushBatch { float *dst[128]; long long *src[128]; int count[128]; int n; };
 __global__ void fx_flush_kernel(FxFlushBatch b) {
@@ -2310,6 +2274,11 @@ extern "C" int stair_set_tn_slab_min_rows(int32_t rows) {
     return 0;
 }
 
+bool stair::det_enabled() {
+    static const bool on = env_int("STAIR_DETERMINISTIC", 1) != 0;
+    return on;
+}
+
 long long *stair::det_shadow(const float *g) {
     DetState &d = g_det;
     if (!d.active || !g) return nullptr;
@@ -2416,7 +2385,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         RUN(launch_transpose_many(tb, tiles, s));       // one launch for all 31 images
     }
     // ---- backward chains of the fused tile operators (csrc/tile_mlp.hip): dX = (dZ2 W2 * relu'(Z1)) W1 stays on the tile ----
-    const bool fused = pl->o_wfragT > 0 && tile_mlp_usable(H, T) && (pl->drop_p <= 0.0f || tile_dropout_on()) && tile_policy(pl, true);
+    const bool fused = pl->o_wfragT > 0 && tile_mlp_usable(H, T);
     auto WFT = [&](int slot) { return static_cast<const void *>(ws + pl->o_wfragT + (int64_t)slot * H * H); };
     // the row-wise layers' backward as grouped launches (csrc/vec_group.hip): per level one launch for everything that starts from a
     // gradient row of the arena (relu' on load, kept as dZ), one for the second stage of the two-layer modules
@@ -2510,11 +2479,9 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     std::vector<stair_tile_mlp_args> chain_queue;
     // every same-level reader of a gradient slot has a target of its own (build_grad_fanin) and the chains of a level are ONE launch
     // per kernel form: no two instances of a launch add into the same tile, so the chains add with plain read - add - write
-    // (STAIR_TILE_RMW=0: float atomics)
-    static const int chain_rmw = [] { const char *e = getenv("STAIR_TILE_RMW"); return (e && e[0] == '0') ? 0 : 1; }();
-    // relu' masks as bits (written by the fused forward launches of THIS plan's last run; STAIR_TILE_BITS=0: the fp32 activations)
-    static const bool bits_on = [] { const char *e = getenv("STAIR_TILE_BITS"); return !(e && e[0] == '0'); }();
-    const bool use_bits = bits_on && pl->bits_written;
+    // (acc_exclusive = 1)
+    // relu' masks as bits (written by the fused forward launches of THIS plan's last run; without them the fp32 activations)
+    const bool use_bits = pl->bits_written;
     auto BITS = [&](int64_t off) { return reinterpret_cast<const unsigned long long *>(ws + off); };
     auto bwd_bucket = [&](const Bucket &b, const int phase) -> int {
         if (b.cnt == 0) return 0;
@@ -2546,14 +2513,13 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
             a.W[0] = WFT(slot3); a.act[0] = 3; a.act_scale = inv_keep; a.save[0] = gA;
             if (use_bits && b.bitA >= 0) a.act_bits[0] = BITS(b.bitA); else a.act_mask[0] = svA;
             a.W[1] = WFT(slot0); a.act[1] = 0;
-            a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = chain_rmw;
+            a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = 1;
             chain_queue.push_back(a);
             return 0;
         };
-        // Temporal's backward as a chain of its own kernel form (LayerNorm adjoint in, row-scale adjoint out): STAIR_TILE_TEMPORAL_BWD=0
-        // keeps the four-launch sequence per bucket
-        static const bool temporal_chain_on = [] { const char *e = getenv("STAIR_TILE_TEMPORAL_BWD"); return !(e && e[0] == '0'); }();
-        const bool temporal_chain = fused && temporal_chain_on && b.op == STAIR_OP_TEMPORAL && b.dzA >= 0;
+        // Temporal's backward as a chain of its own kernel form (LayerNorm adjoint in, row-scale adjoint out); unfused plans keep the
+        // four-launch sequence per bucket
+        const bool temporal_chain = fused && b.op == STAIR_OP_TEMPORAL && b.dzA >= 0;
         const bool chain_op = fused && (b.op == STAIR_OP_FILTER || (b.op == STAIR_OP_FILTERFRAME && b.variant != 0) || b.op == STAIR_OP_HASITEM ||
                                         b.op == STAIR_OP_LOCALIZE || b.op == STAIR_OP_SUPERLATIVE || temporal_chain);
         if (phase == 2 && !chain_op) return 0;
@@ -2662,7 +2628,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                     if (use_bits && b.bitB >= 0) a.act_bits[0] = BITS(b.bitB); else a.act_mask[0] = svB;
                     if (use_bits && b.bitA >= 0) a.act_bits[1] = BITS(b.bitA); else a.act_mask[1] = svA;
                     a.W[2] = WFT(WF_FF0 + v); a.act[2] = 0;
-                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = chain_rmw;
+                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = 1;
                     chain_queue.push_back(a);
                     break;
                 }
@@ -2697,7 +2663,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                     a.X = gA; a.x_gstride = TH; a.in_scale = inv_keep; a.save_in = gA;
                     if (use_bits && b.bitA >= 0) a.in_bits = BITS(b.bitA); else { a.in_mask = svA; a.in_mask_gstride = TH; }
                     a.n_layers = 1; a.W[0] = WFT(WF_HI0); a.act[0] = 0;
-                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = chain_rmw;
+                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = 1;
                     chain_queue.push_back(a);
                     break;
                 }
@@ -2746,7 +2712,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                     a.ln_bwd = 1; a.in_mask = svA; a.in_mask_gstride = TH; a.in_scale = inv_keep; a.save_in = gA;
                     a.gamma = W.ln_w; a.dgamma = W.dln_w; a.dbeta = W.dln_b;
                     a.n_layers = 1; a.W[0] = WFT(WF_TD); a.act[0] = 0;
-                    a.tail = STAIR_TILE_ROWSCALE_ADJ; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = chain_rmw;
+                    a.tail = STAIR_TILE_ROWSCALE_ADJ; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = 1;
                     a.adj_feat = map; a.adj_feat_gstride = TH; a.adj_feat_idx = I0;
                     a.adj_rs = att; a.adj_rs_idx = I3; a.adj_drs = g_att;
                     chain_queue.push_back(a);
@@ -2803,22 +2769,9 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
 
     // ---- the deferred weight-gradient products: one long reduction per weight -------------------------------
     // They are leaves (nothing downstream reads dW before the optimizer), and what follows on `s` -- BPTT through both encoders,
-    // HBM-bound on its saved state -- touches none of their operands, so they CAN run on a second stream beside it
-    // (STAIR_BWD_OVERLAP=1).  Measured (profiles/r03_*): 19.11 ms per 2048-question step with the overlap, 18.72 ms without,
-    // 5.53 against 5.44 ms at 128 questions -- the two streams contend for the same LDS / L2 / HBM paths; off by default.
-    static const bool overlap_tn = [] { const char *e = getenv("STAIR_BWD_OVERLAP"); return e && e[0] == '1'; }();
-    hipStream_t s_tn = s;
-    if (overlap_tn) {
-        RUN(tn_x3tr_flush(s));               // sums queued on `s` by the buckets stay on `s`
-        if (!ctx->side) STAIR_HIP(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-        if (!ctx->ev_fork) {
-            STAIR_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            STAIR_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        STAIR_HIP(hipEventRecord(ctx->ev_fork, s));
-        STAIR_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-        s_tn = ctx->side;
-    }
+    // HBM-bound on its saved state -- touches none of their operands.  Running them on a second stream beside it was measured
+    // slower (profiles/r03_*): 19.11 ms per 2048-question step with the overlap, 18.72 ms without, 5.53 against 5.44 ms at 128
+    // questions -- the two streams contend for the same LDS / L2 / HBM paths.
     for (int w = 0; w < WF_COUNT; ++w) {
         if (w == WF_FFD || pl->wg_rows[w] == 0) continue;
         const Lin &l = *lin_of[w];
@@ -2833,8 +2786,8 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
             t.B = map; t.ldb = H; t.b_gstride = TH; t.b_gidx = didx + pl->wg_off_idx[w];
             if (w == WF_TD) { t.row_scale = att; t.rs_gstride = T; t.rs_gidx = didx + pl->wg_off_rs[w]; }
         }
-        if (pl->wg_part[w] && tn_x3tr_takes(t)) RUN(launch_gemm_tn_x3tr(t, ws + pl->wg_part[w], s_tn));      // deterministic: no atomics
-        else RUN(launch_gemm_tn(t, s_tn));
+        if (pl->wg_part[w] && tn_x3tr_takes(t)) RUN(launch_gemm_tn_x3tr(t, ws + pl->wg_part[w], s));      // deterministic: no atomics
+        else RUN(launch_gemm_tn(t, s));
     }
     // the vector-level weights (and Filter's dense layer on the pooled rows): one product per weight over the rows of all its
     // buckets; from 2048 rows on through the slab kernel (whole 32-row stages; the < 32 rows left over by the atomic kernel, one
@@ -2853,20 +2806,18 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         h.M = t.M & ~31;
         const int64_t need = h.M >= 2048 && B.tn_ring && tn_x3tr_takes(h) ? align_up(tn_x3tr_scratch_floats(h.M, H, Kw), 64) : 0;
         if (need && need <= B.tn_ring_floats) {
-            if (B.tn_ring_at + need > B.tn_ring_floats) { RUN(tn_x3tr_flush(s_tn)); B.tn_ring_at = 0; }
-            RUN(launch_gemm_tn_x3tr(h, B.tn_ring + B.tn_ring_at, s_tn));
+            if (B.tn_ring_at + need > B.tn_ring_floats) { RUN(tn_x3tr_flush(s)); B.tn_ring_at = 0; }
+            RUN(launch_gemm_tn_x3tr(h, B.tn_ring + B.tn_ring_at, s));
             B.tn_ring_at += need;
             if (t.M == h.M) continue;
             t.A += (int64_t)h.M * t.lda; t.B += (int64_t)h.M * t.ldb; t.M -= h.M;
         }
         small_tn.push_back(t);
     }
-    if (!small_tn.empty()) RUN(launch_gemm_tn_batch(small_tn.data(), (int)small_tn.size(), s_tn));
-    RUN(tn_x3tr_flush(s_tn));                 // dW, db += the slabs of every product above, in slab order: one launch
-    if (overlap_tn) STAIR_HIP(hipEventRecord(ctx->ev_join, ctx->side));
+    if (!small_tn.empty()) RUN(launch_gemm_tn_batch(small_tn.data(), (int)small_tn.size(), s));
+    RUN(tn_x3tr_flush(s));                    // dW, db += the slabs of every product above, in slab order: one launch
     // Every gradient except the two encoders' is final here (decoder, all module levels, their weight-gradient products): a
     // data-parallel trainer starts reducing that part of its bucket now, beside the BPTT below (stair_plan_set_backward_event)
-    if (overlap_tn && (pl->bwd_event || g_det.active)) STAIR_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));
     RUN(det_flush(ctx, s));                   // ... including what went through the fixed-point shadows (module levels, decoder)
     if (pl->bwd_event) STAIR_HIP(hipEventRecord(static_cast<hipEvent_t>(pl->bwd_event), s));
 
@@ -2904,36 +2855,18 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         if (lstm_bwd_takes_coop(enc[0]) && lstm_bwd_takes_coop(enc[1])) rc_pair = launch_lstm_bwd_coop_pair(enc[1], enc[0], s);
         if (rc_pair > 0) return rc_pair;
         if (rc_pair < 0) {
-            // Two independent passes (disjoint inputs, workspaces and gradient buffers; their slab partials are added after the join), so the
-            // text encoder's backward CAN run beside the video encoder's on a second stream (STAIR_ENC_OVERLAP=1).  Measured: nothing to gain
-            // at 512 or 2048 questions (6.13 vs 6.12 ms; 16.4-16.7 vs 15.9-16.8) -- the one-workgroup reverse recurrence takes 256 registers x
-            // 512 threads, so from 1024 sequences on either pass fills every CU by itself.  Off by default.
-            static const bool enc_overlap = [] { const char *e = getenv("STAIR_ENC_OVERLAP"); return e && e[0] == '1'; }();
-            if (enc_overlap) {
-                if (!ctx->side) STAIR_HIP(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-                if (!ctx->ev_fork_enc) {
-                    STAIR_HIP(hipEventCreateWithFlags(&ctx->ev_fork_enc, hipEventDisableTiming));
-                    STAIR_HIP(hipEventCreateWithFlags(&ctx->ev_join_enc, hipEventDisableTiming));
-                }
-                STAIR_HIP(hipEventRecord(ctx->ev_fork_enc, s));
-                STAIR_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork_enc, 0));
-                const int rc_t = launch_lstm_bwd(enc[1], ctx->side);
-                const int rc_v = rc_t ? 0 : launch_lstm_bwd(enc[0], s);
-                STAIR_HIP(hipEventRecord(ctx->ev_join_enc, ctx->side));       // joined on every path: nothing of this pass is left running on the side stream
-                STAIR_HIP(hipStreamWaitEvent(s, ctx->ev_join_enc, 0));
-                if (rc_t) return rc_t;
-                if (rc_v) return rc_v;
-            } else {
-                RUN(launch_lstm_bwd(enc[1], s));
-                RUN(launch_lstm_bwd(enc[0], s));
-            }
+            // Two independent passes (disjoint inputs, workspaces and gradient buffers).  Running the text encoder's beside the video
+            // encoder's on a second stream was measured: nothing to gain at 512 or 2048 questions (6.13 vs 6.12 ms; 16.4-16.7 vs
+            // 15.9-16.8) -- the one-workgroup reverse recurrence takes 256 registers x 512 threads, so from 1024 sequences on either
+            // pass fills every CU by itself.
+            RUN(launch_lstm_bwd(enc[1], s));
+            RUN(launch_lstm_bwd(enc[0], s));
         } else {
             RUN(launch_lstm_bwd_weights(enc[1], s));
             RUN(launch_lstm_bwd_weights(enc[0], s));
         }
     }
     RUN(tn_x3tr_flush(s));                   // the encoders' slab-reduced weight gradients
-    if (overlap_tn) STAIR_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));      // the optimizer (next on `s`) sees every dW
     RUN(det_flush(ctx, s));                  // the encoders' fixed-point shadows -> the fp32 gradients
     if (g_det.active) ctx->gshadow_dirty = false;    // every touched shadow has been emptied again
     g_det.active = false;

@@ -915,10 +915,9 @@ int launch_pack_wfrag_many(const float *const *W, void *const *out, int count, i
 static bool g_tile_timing = false;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_tile_events;
 
-static int g_tile_on = -1;          // stair_set_tile_mlp; -1 = the environment's STAIR_TILE_MLP (default on)
+static int g_tile_on = 1;           // stair_set_tile_mlp
 bool tile_mlp_usable(int H, int T) {
-    static const bool env_on = [] { const char *e = getenv("STAIR_TILE_MLP"); return !(e && e[0] == '0'); }();
-    const bool on = policy_or(STAIR_OPT_TILE_MLP, g_tile_on >= 0 ? g_tile_on : (env_on ? 1 : 0)) != 0;
+    const bool on = policy_or(STAIR_OPT_TILE_MLP, g_tile_on) != 0;
     return on && H == TM_H && T >= 1 && T <= TM_ROWS && matmul_mode() == STAIR_MATMUL_BF16X3;
 }
 
@@ -992,22 +991,18 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
     static int cus[64] = {};
     if (!attr_set[dev]) {
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<false, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         int v = 256;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         cus[dev] = v;
         attr_set[dev] = true;
     }
-    // non-temporal hints on the tile's own traffic (inputs, masks, saves): with the first version of the kernel plain accesses were
-    // faster (saves 273 -> 290 us per 1024 tiles); now that a layer is bound by the weight stream from L2, keeping the streamed
-    // tiles from displacing the weight planes pays: 17.02 -> 16.89 ms per 2048-question step (three A/B pairs on one box),
-    // neutral at 128 questions and in inference.  STAIR_TILE_NT=0 switches them off.
-    static const bool nt = [] { const char *e = getenv("STAIR_TILE_NT"); return !(e && e[0] == '0'); }();
+    // non-temporal hints on the tile's own traffic (inputs, masks, saves) of every form but the vector-level one: with the first
+    // version of the kernel plain accesses were faster (saves 273 -> 290 us per 1024 tiles); now that a layer is bound by the weight
+    // stream from L2, keeping the streamed tiles from displacing the weight planes pays: 17.02 -> 16.89 ms per 2048-question step
+    // (three A/B pairs on one box), neutral at 128 questions and in inference.
     auto rounds = [&](int x) { return args[x].n_layers + (args[x].vec_pack ? (args[x].vec_pack == 1 ? 1 : 2) : 0); };   // k loops per tile
     // map-level tiles, vector-level tiles and Temporal's backward chains are three kernels (what one form needs in registers the
     // others do not pay for): one launch per form a level has; stream-ordered, so they share the (self-resetting) queue words
@@ -1062,12 +1057,9 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
             STAIR_HIP(hipEventRecord(e0, s));
         }
         if (vec) hipLaunchKernelGGL((tile_mlp_kernel<false, 1>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (kind == 2 && nt) hipLaunchKernelGGL((tile_mlp_kernel<true, 2>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (kind == 2) hipLaunchKernelGGL((tile_mlp_kernel<false, 2>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (kind == 3 && nt) hipLaunchKernelGGL((tile_mlp_kernel<true, 3>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (kind == 3) hipLaunchKernelGGL((tile_mlp_kernel<false, 3>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (nt) hipLaunchKernelGGL((tile_mlp_kernel<true, 0>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else hipLaunchKernelGGL((tile_mlp_kernel<false, 0>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        else if (kind == 2) hipLaunchKernelGGL((tile_mlp_kernel<true, 2>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        else if (kind == 3) hipLaunchKernelGGL((tile_mlp_kernel<true, 3>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        else hipLaunchKernelGGL((tile_mlp_kernel<true, 0>), dim3(grid), dim3(512), TM_LDS, s, pp);
         STAIR_LAUNCH_CHECK();
         if (g_tile_timing) {
             STAIR_HIP(hipEventRecord(e1, s));

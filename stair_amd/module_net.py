@@ -17,7 +17,6 @@ torch is plumbing here (device memory, streams, Parameter containers); the arith
 from __future__ import annotations
 
 import ctypes as C
-import os
 import math
 
 import numpy as np
@@ -348,8 +347,8 @@ class VideoNMN(nn.Module):
         self._gbound = {}
         self._ws = None
         self._proj = None
-        # run_programs: enqueue the encoders' input projections before the plan is built (STAIR_EARLY_PROJECTION=0: inside the plan's pass)
-        self.early_projection = os.environ.get('STAIR_EARLY_PROJECTION', '1') != '0'
+        # run_programs: enqueue the encoders' input projections before the plan is built (False: inside the plan's pass)
+        self.early_projection = True
         self._programs = frontend.ProgramCache()
 
     def __del__(self):

@@ -21,7 +21,6 @@ dev = 'cuda:0'
 shapes = [(131072, 1024, 2048), (131072, 512, 512), (32768, 512, 512), (34048, 1024, 320)]
 if len(sys.argv) > 1:
     shapes = shapes[:int(sys.argv[1])]
-print('STAIR_PLANES_ABLATE =', os.environ.get('STAIR_PLANES_ABLATE', '0'))
 for (M, N, K) in shapes:
     x = torch.randn(M, K, device=dev); w = torch.randn(N, K, device=dev) / K ** 0.5
     out = torch.empty(M, N, device=dev)
