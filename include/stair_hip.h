@@ -262,7 +262,12 @@ int stair_lstm_bidir_fwd(const stair_lstm_args *args, stair_stream stream);
  * cbuf/out from that forward, d_out [rows, ldd] and d_hn [n, 2*Hh] (may be NULL) the incoming gradients.
  * dw_ih/dw_hh/db_ih/db_hh are ACCUMULATED (fp32 atomics).  No input gradient is produced here: the gate
  * gradients left in `gates` are what stair_plan_backward_dlogits multiplies by W_ih for one.  Scratch: whh_pack_ws [8*Hh*Hh],
- * hprev_ws [rows, 2*Hh]. */
+ * hprev_ws [rows, 2*Hh].  hprev_ws holds h of the previous step of each row for the dW_hh product.  When that product runs
+ * through the slab kernel (tn_ws given and large enough, rows >= 2048, Hh % 128 == 0, split matmul mode) the copy is not made:
+ * the product reads `out` itself one row before (forward direction) or behind (reverse direction) the gate-gradient row, under a
+ * 0 / 1 row mask kept in the first 2 * rows floats of hprev_ws; the shifted row index is clamped to [0, rows - 1], so no read
+ * leaves `out`, and a masked row counts as zero whatever it holds.  Only the rows % 32 rows past the last whole 32-row stage are
+ * still copied, to hprev_ws + (rows & ~31) * 2 * Hh.  In every other case all of hprev_ws is written as before. */
 typedef struct stair_lstm_bwd_args {
     const float *x; int64_t ldx; int32_t rows, n, max_len, I, Hh;
     const int32_t *seq_off;
@@ -357,6 +362,10 @@ typedef struct stair_tile_mlp_args {
      * ROWSCALE_ADJ): the tile is read, added to and written back with plain 16-byte accesses instead of float atomics
      * (stair_plan_backward: the deterministic fan-in gives every same-level reader of a slot a target of its own) */
     int32_t acc_exclusive;
+    /* With acc_exclusive, bit STAIR_TILE_STORE_FIRST of out_idx[i] says that instance i's contribution is the first one its output
+     * tile receives and that the tile was NOT cleared: the T rows are stored and the tile is not read (the slot is the entry without
+     * the bit).  A stored row holds what the add would have left in a zeroed tile (-0 where that gave +0). */
+#define STAIR_TILE_STORE_FIRST 0x40000000
     /* relu' of a saved activation as ONE bit per element (4 KB per tile instead of a 128 KB read in the backward chain):
      *   save_bits[l]     [cnt][512] 64-bit words, written by a forward launch: word (i, 64 w + c), byte j, bit e = (layer l's
      *                    activation of tile i, row w + 8 j, column 8 c + e) > 0
@@ -664,6 +673,12 @@ int stair_plan_backward(stair_ctx *ctx, stair_plan *plan, const float *video, co
                                    the gradients injected by the stair_loss_* functions below.  STAIR_RUN_VIDEO_BF16 (2) must be
                                    repeated here when the forward pass ran on bf16 clip features. */
 int stair_plan_zero_grads(stair_plan *plan, void *workspace, stair_stream stream);
+/* First-touch stores of a STAIR_PLAN_TRAIN plan.  A reverse pass WITHOUT STAIR_BWD_KEEP_ARENAS on the fused tile operators does not
+ * clear a gradient tile of the map arena (slots, then fan-in staging tiles: n_map + n_map_stage of stair_plan_info) whose first
+ * writer of the pass is a tile chain that writes the whole [T, H] tile; that chain stores its rows (STAIR_TILE_STORE_FIRST).
+ * n_store_first: tiles stored that way; n_cleared: tiles the pass clears; their sum is n_map + n_map_stage.  With
+ * STAIR_BWD_KEEP_ARENAS, or unfused, every tile is cleared (stair_plan_zero_grads) and every tail adds. */
+int stair_plan_store_first_counts(const stair_plan *plan, int32_t *n_store_first, int32_t *n_cleared);
 /* Reverse pass of a STAIR_PLAN_TRAIN plan seeded by a caller's logits gradient instead of the decoder CE (torch autograd of the
  * logits, stair_amd/autograd.py): everything after the seed is the pass of stair_plan_backward.
  * d_logits [n, A] device fp32 (already scaled: no loss_scale).  Parameter gradients are ACCUMULATED into the

@@ -122,7 +122,7 @@ int tn_x3tr_queue(const float *P, float *dst, int nslab, int count4, hipStream_t
 bool tn_x3tr_takes(const stair_gemm_tn_args &a);
 int tn_x3tr_slabs(int64_t M);
 int64_t tn_x3tr_scratch_floats(int64_t M, int64_t N, int64_t K);
-int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, hipStream_t s);
+int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, hipStream_t s, int b_shift = 0, int64_t b_rows = 0);
 int tn_x3tr_flush(hipStream_t s);
 void tn_x3tr_discard();          // forget queued sums (a pass that failed half-way must not leak them into the next one)
 int launch_lstm_rec_coop(const stair_lstm_args &a, hipStream_t s);
@@ -174,6 +174,8 @@ int launch_colsum(const float *A, int64_t lda, float *out, int M, int N, hipStre
 int launch_transpose(const float *in, float *out, int rows, int cols, hipStream_t s);
 // bytes % 4 == 0 zero bytes at a 4-byte aligned address, as a kernel (never a memset node of a captured graph; csrc/rowops.hip)
 int launch_zero(void *ptr, int64_t bytes, hipStream_t s);
+int launch_zero_segments(float *head, int64_t head_floats, float *tile_base, const int32_t *tiles, int n_tiles, int64_t tile_floats,
+                         float *tail, int64_t tail_floats, hipStream_t s);
 // csrc/enc_input_grad.hip (stair_plan_backward_dlogits): the caller's logits gradient into the plan's dlogits region, and one encoder's
 // input gradient dX [rows, I] = gates [rows, 8 Hh] (the gate pre-activation gradients after BPTT) times [W_ih_fwd ; W_ih_bwd] [8 Hh, I];
 // wt_ws: scratch of 8 Hh * I floats for the transposed image of the stacked W_ih

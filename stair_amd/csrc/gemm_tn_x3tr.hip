@@ -43,6 +43,7 @@ struct XtParams {
     float *P;                                 // [nslab][N][K] partial products
     float *Pc;                                // [nslab][N] partial column sums of dZ, or null
     int N, K, rpg, stages, nslab, tilesK;
+    int b_shift; int64_t b_last;              // SHIFT: row m of the product reads row clamp(m + b_shift, 0, b_last) of B
 };
 
 // the 16-byte chunk ch of row r of half h sits at chunk ch ^ f(r) ^ h (cdna_hip_programming.md T10, image (b); same image as gemm_tn_tr.hip)
@@ -57,7 +58,10 @@ __device__ __forceinline__ bf16x8 join8(bf16x4 a, bf16x4 b) { return __builtin_s
 
 }  // namespace
 
-template <bool GIDX, bool RS, bool KTAIL>
+// SHIFT (with RS, a plain row matrix): X row m is row m + b_shift of B (h(t-1) of an LSTM direction is the output row before or
+// behind), rs is a 0 / 1 mask and a masked row is SELECTED to zero, whatever the shifted address holds (it may be another sequence's
+// row or, clamped at either end of B, a row that was never the one asked for); no read leaves rows 0 .. b_last of B.
+template <bool GIDX, bool RS, bool KTAIL, bool SHIFT = false>
 __global__ __launch_bounds__(512, 1) void gemm_tn_x3tr_kernel(XtParams p) {
     extern __shared__ __attribute__((aligned(16))) char xl[];       // [2 stages][dZ hi | dZ lo | X hi | X lo]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -130,13 +134,21 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_x3tr_kernel(XtParams p) {
     const int kc = k0 + 8 * seg;
     const float bm0 = (!KTAIL || kc < p.K) ? 1.0f : 0.0f, bm1 = (!KTAIL || kc + 4 < p.K) ? 1.0f : 0.0f;
     const int b_off0 = row * (int)p.ldb + ((!KTAIL || kc < p.K) ? kc : 0), b_off1 = row * (int)p.ldb + ((!KTAIL || kc + 4 < p.K) ? kc + 4 : 0);
+    int64_t b_row = m_first + row + p.b_shift;                        // SHIFT: this thread's row of B for the next stage to load
     auto load = [&](XtRegs &g) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) g.a[i] = *(const v4f *)(a_src + 4 * i);
         a_src += a_step;
+        if (SHIFT) {
+            const float *bs = p.B + (b_row < 0 ? 0 : (b_row > p.b_last ? p.b_last : b_row)) * p.ldb;
+            g.b[0] = *(const v4f *)(bs + kc);
+            g.b[1] = *(const v4f *)(bs + kc + 4);
+            b_row += XT_ROWS;
+        } else {
         const float *bs = p.B + (int64_t)gxs[gl] * p.b_gstride + (int64_t)r0 * p.ldb;
         g.b[0] = *(const v4f *)(bs + b_off0);
         g.b[1] = *(const v4f *)(bs + b_off1);
+        }
         if (RS) g.rs = p.rs[(int64_t)grs[gl] * p.rs_gstride + r0 + row];
         const bool wrap = r0 + XT_ROWS >= p.rpg;
         gl += wrap ? 1 : 0;
@@ -164,7 +176,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_x3tr_kernel(XtParams p) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float v = RS ? g.b[i][e] * g.rs : g.b[i][e];
+                float v = SHIFT ? (g.rs != 0.0f ? g.b[i][e] : 0.0f) : RS ? g.b[i][e] * g.rs : g.b[i][e];
                 if (KTAIL) v *= i ? bm1 : bm0;
                 const __bf16 hv = (__bf16)v;
                 bh[4 * i + e] = hv;
@@ -297,7 +309,8 @@ int64_t tn_x3tr_scratch_floats(int64_t M, int64_t N, int64_t K) { return (int64_
 bool tn_x3tr_takes(const stair_gemm_tn_args &a) {
     if (a.b_is_bf16 || matmul_mode() != STAIR_MATMUL_BF16X3) return false;
     if (a.N % 256 || a.K % 4 || a.K < 4 || a.M % XT_ROWS || a.M < 2 * XT_ROWS || a.rows_per_group < 1) return false;
-    if (a.rows_per_group % XT_ROWS && (a.rows_per_group != 1 || a.b_gidx || a.row_scale || a.b_gstride != a.ldb)) return false;   // groups of whole stages, or a plain row matrix
+    // groups of whole stages, or a plain row matrix (one group of M rows; its row scale, if any, is M consecutive floats)
+    if (a.rows_per_group % XT_ROWS && (a.rows_per_group != 1 || a.b_gidx || a.rs_gidx || a.b_gstride != a.ldb || (a.row_scale && a.rs_gstride != 1))) return false;
     if (a.K % 128 && (a.b_gidx || a.row_scale)) return false;
     if (a.colsum2 && !a.colsum) return false;
     if (a.lda % 4 || a.ldb % 4 || a.ldc != a.K || a.b_gstride % 4) return false;
@@ -312,8 +325,12 @@ bool tn_x3tr_takes(const stair_gemm_tn_args &a) {
 static thread_local XtReduceBatch g_pending;                                      // entries queued by launch_gemm_tn_x3tr, flushed by tn_x3tr_flush (one thread per plan pass)
 
 // Partial products of `a` into scratch (tn_x3tr_scratch_floats floats); the sums reach a.C / a.colsum at the next tn_x3tr_flush on the same stream.
-int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, hipStream_t s) {
+// b_shift != 0 (needs a row scale, no gather, K % 128 == 0): the SHIFT form above on the b_rows rows of a.B; row_scale is then a 0 / 1 mask
+int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, hipStream_t s, int b_shift, int64_t b_rows) {
+    STAIR_CHECK(b_shift == 0 || (a.row_scale && !a.b_gidx && !a.rs_gidx && a.K % 128 == 0 && a.rows_per_group == 1 && b_rows >= a.M),
+                "internal: shifted slab product on a masked plain row matrix only");
     XtParams p;
+    p.b_shift = b_shift; p.b_last = b_rows - 1;
     p.A = a.A; p.lda = a.lda; p.B = a.B; p.ldb = a.ldb; p.b_gstride = a.b_gstride; p.b_gidx = a.b_gidx;
     p.rs = a.row_scale; p.rs_gstride = a.rs_gstride; p.rs_gidx = a.rs_gidx;
     p.N = a.N; p.K = a.K; p.rpg = a.rows_per_group % XT_ROWS ? a.M : a.rows_per_group;       // a plain row matrix is one group of M rows
@@ -330,6 +347,7 @@ int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, hipStream_t
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_x3tr_kernel<false, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, XT_LDS));
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_x3tr_kernel<true, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, XT_LDS));
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_x3tr_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, XT_LDS));
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_tn_x3tr_kernel<false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, XT_LDS));
         attr_set[dev] = true;
     }
     if (gemm_trace_on())
@@ -337,6 +355,7 @@ int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, hipStream_t
     STAIR_ACCT_MFMA("gemm_tn_x3tr", ((int64_t)a.M * a.N + (int64_t)a.M * a.K + (int64_t)a.N * a.K) * 4, 2ll * a.M * a.N * a.K);
     const dim3 grid(p.nslab * (a.N / 256) * p.tilesK);
     if (a.K % 128) hipLaunchKernelGGL((gemm_tn_x3tr_kernel<false, false, true>), grid, dim3(512), XT_LDS, s, p);
+    else if (b_shift) hipLaunchKernelGGL((gemm_tn_x3tr_kernel<false, true, false, true>), grid, dim3(512), XT_LDS, s, p);
     else if (a.b_gidx && a.row_scale) hipLaunchKernelGGL((gemm_tn_x3tr_kernel<true, true, false>), grid, dim3(512), XT_LDS, s, p);
     else if (a.b_gidx) hipLaunchKernelGGL((gemm_tn_x3tr_kernel<true, false, false>), grid, dim3(512), XT_LDS, s, p);
     else if (a.row_scale) hipLaunchKernelGGL((gemm_tn_x3tr_kernel<false, true, false>), grid, dim3(512), XT_LDS, s, p);

@@ -444,15 +444,18 @@ __global__ void whh_packT_kernel(const float *w0, const float *w1, float *pack, 
 // weight-gradient GEMMs, which run over ALL rows, add nothing for them)
 // grid (n, ceil(max_len / 8)): a block copies 8 rows of one sequence as float4s, every load issued before the first store
 // (one block per sequence with a scalar loop took 46 us for 128 sequences: a latency chain, not bandwidth)
+// Only the rows from row_begin on are copied: the dW_hh product of the rows before reads `out` itself, shifted by a row and masked
+// (lstm_hmask_kernel, launch_lstm_bwd_weights); row_begin = 0 is the whole copy.
 __global__ __launch_bounds__(256) void lstm_hprev_kernel(const float *out, int64_t ldo, const int32_t *seq_off, const int32_t *seq_len, int n, int Hh,
-                                                         float *hprev, float *G) {
+                                                         float *hprev, float *G, int row_begin) {
     const int s = blockIdx.x;
     const int beg = seq_off[s], span = seq_off[s + 1] - beg, len = seq_len ? seq_len[s] : span;
     const int t0 = blockIdx.y * 8;
     if (t0 >= span) return;
+    using f4 = __attribute__((ext_vector_type(4))) float;
+    if (beg + min(t0 + 8, span) > row_begin) {
     const int q4 = 2 * Hh / 4;                                 // float4s per row
     const int rows = min(8, span - t0);
-    using f4 = __attribute__((ext_vector_type(4))) float;
     for (int i0 = threadIdx.x; i0 < rows * q4; i0 += 4 * 256) {
         f4 v[4];
 #pragma unroll
@@ -470,14 +473,27 @@ __global__ __launch_bounds__(256) void lstm_hprev_kernel(const float *out, int64
             const int i = i0 + 256 * k;
             if (i < rows * q4) {
                 const int t = t0 + i / q4, c = 4 * (i - (i / q4) * q4);
-                *reinterpret_cast<f4 *>(hprev + (int64_t)(beg + t) * 2 * Hh + c) = v[k];
+                if (beg + t >= row_begin) *reinterpret_cast<f4 *>(hprev + (int64_t)(beg + t) * 2 * Hh + c) = v[k];
             }
         }
+    }
     }
     if (seq_len && len < span) {                               // gate-gradient rows past the sequence's length: cleared
         const int z0 = max(t0, len), z1 = min(t0 + 8, span);
         for (int i = threadIdx.x; i < (z1 - z0) * 2 * Hh; i += 256)
             *reinterpret_cast<f4 *>(G + (int64_t)(beg + z0) * 8 * Hh + 4 * (int64_t)i) = f4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+// mask[dir][row] = 1 where h of the previous step of direction dir is the output row before (dir 0) / behind (dir 1) `row`, 0 where
+// lstm_hprev_kernel writes zeros: the first step of the forward direction, the last valid step of the reverse direction, rows past
+// the sequence's length.  One block per sequence.
+__global__ __launch_bounds__(64) void lstm_hmask_kernel(const int32_t *seq_off, const int32_t *seq_len, int64_t rows, float *mask) {
+    const int s = blockIdx.x;
+    const int beg = seq_off[s], span = seq_off[s + 1] - beg, len = seq_len ? seq_len[s] : span;
+    for (int t = threadIdx.x; t < span; t += 64) {
+        mask[beg + t] = (t < len && t >= 1) ? 1.0f : 0.0f;
+        mask[rows + beg + t] = (t + 1 < len) ? 1.0f : 0.0f;
     }
 }
 
@@ -856,10 +872,33 @@ static int lstm_weight_product(stair_gemm_tn_args g, float *&scr, int64_t &left,
 int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, hipStream_t s) {
     if (a.n == 0 || a.rows == 0) return 0;
     const int Hh = a.Hh;
-    hipLaunchKernelGGL(lstm_hprev_kernel, dim3(a.n, (a.max_len + 7) / 8), dim3(256), 0, s, a.out, a.ldo, a.seq_off, a.seq_len, a.n, Hh, a.hprev_ws, a.gates);
-    STAIR_LAUNCH_CHECK();
     float *scr = a.tn_ws;
     int64_t left = a.tn_ws ? a.tn_ws_floats : 0;
+    // dW_hh = dG^T Hprev.  Where the slab kernel takes the product, Hprev is not materialised: h(t-1) of the forward direction is the
+    // output row before, of the reverse direction the row behind, so the product reads `out` moved by one row under a 0 / 1 row mask
+    // (hprev_ws[0 .. 2 rows): rows floats per direction) -- at 2048 questions the copy was 268 MB written and read again per step.
+    // The < 32 rows past the last whole stage keep their copy (in their usual place in hprev_ws, far behind the mask), and so does
+    // everything when the slab kernel does not run (exact-fp32 mode, no scratch, fewer than 2048 rows).
+    const int m_slab = a.rows & ~31;
+    stair_gemm_tn_args hh = {};
+    hh.A = a.gates; hh.lda = 8 * (int64_t)Hh;
+    hh.B = a.out; hh.ldb = a.ldo; hh.b_gstride = a.ldo; hh.rows_per_group = 1;
+    hh.row_scale = a.hprev_ws; hh.rs_gstride = 1;
+    hh.C = a.dw_hh[0]; hh.ldc = Hh; hh.M = m_slab; hh.N = 4 * Hh; hh.K = Hh;
+    hh.colsum = a.db_ih[0]; hh.colsum2 = a.db_hh[0];
+    const int64_t need_hh = align_up(tn_x3tr_scratch_floats(m_slab, 4 * Hh, Hh), 64);
+    const int64_t need_ih = std::max(align_up((int64_t)8 * 4 * Hh * a.I, 64), align_up(tn_x3tr_scratch_floats(m_slab, 4 * Hh, a.I), 64));
+    const bool shifted = scr && m_slab >= 2048 && Hh % 128 == 0 && tn_x3tr_takes(hh) && 2 * (need_hh + need_ih) <= left;
+    const int row_begin = shifted ? m_slab : 0;
+    if (shifted) {
+        hipLaunchKernelGGL(lstm_hmask_kernel, dim3(a.n), dim3(64), 0, s, a.seq_off, a.seq_len, (int64_t)a.rows, a.hprev_ws);
+        STAIR_LAUNCH_CHECK();
+    }
+    if (row_begin < a.rows || a.seq_len) {      // the copy of the rows that need one; with seq_len also the gate-gradient rows past a length
+        hipLaunchKernelGGL(lstm_hprev_kernel, dim3(a.n, (a.max_len + 7) / 8), dim3(256), 0, s, a.out, a.ldo, a.seq_off, a.seq_len, a.n, Hh, a.hprev_ws,
+                           a.gates, row_begin);
+        STAIR_LAUNCH_CHECK();
+    }
     // weight gradients: dW_ih = dG^T X, dW_hh = dG^T Hprev, db_ih = db_hh = colsum(dG)
     for (int dir = 0; dir < 2; ++dir) {
         stair_gemm_tn_args g = {};
@@ -872,6 +911,17 @@ int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, hipStream_t s) {
         g.B = a.hprev_ws + dir * Hh; g.ldb = 2 * (int64_t)Hh; g.b_gstride = 2 * (int64_t)Hh;
         g.C = a.dw_hh[dir]; g.ldc = Hh; g.K = Hh;
         g.colsum = a.db_ih[dir]; g.colsum2 = a.db_hh[dir];     // db_ih = db_hh = colsum(dG), with the smaller of the two products
+        if (shifted) {
+            hh.A = g.A; hh.B = a.out + dir * Hh; hh.row_scale = a.hprev_ws + (int64_t)dir * a.rows;
+            hh.C = g.C; hh.colsum = g.colsum; hh.colsum2 = g.colsum2;
+            if (need_hh > left) STAIR_FAIL("internal: slab scratch of the dW_hh product");
+            if (int rc = launch_gemm_tn_x3tr(hh, scr, s, dir == 0 ? -1 : 1, a.rows)) return rc;
+            scr += need_hh; left -= need_hh;
+            if (m_slab == a.rows) continue;
+            g.A += (int64_t)m_slab * g.lda; g.B += (int64_t)m_slab * g.ldb; g.M = a.rows - m_slab;
+            if (int rc = launch_gemm_tn(g, s)) return rc;
+            continue;
+        }
         if (int rc = lstm_weight_product(g, scr, left, s)) return rc;
     }
     return 0;

@@ -277,6 +277,10 @@ struct Bucket {
     // where a column has no redirected copy
     std::vector<int32_t> gcol[8];
     int64_t goff[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // gcol[0] with STAIR_TILE_STORE_FIRST on the entries whose chain tail is the first writer of its target in a backward pass
+    // (mark_store_first); empty / -1 where the bucket has no such entry
+    std::vector<int32_t> scol;
+    int64_t soff = -1;
     // float offsets of this bucket's intermediates.  Inference: all buckets share one scratch set;
     // training: private regions, kept until stair_plan_backward has consumed them.
     int64_t svA = 0, svB = 0, svK = 0, svCat = 0, svHid = 0, svRs = 0, svSup = 0, svExtra = 0;
@@ -434,6 +438,12 @@ struct stair_plan {
     std::vector<int32_t> fanin;                  // 5 ints per entry
     std::vector<int> fanin_first, fanin_count;   // per level
     int64_t off_fanin = 0;
+    // first-touch stores of the backward chains (mark_store_first): the map-arena gradient tiles (slots, then staging tiles) that
+    // the pass still has to clear, the number of targets it stores instead, and whether a pass may rely on the marks at all
+    std::vector<int32_t> clear_tiles;
+    int64_t off_clear = 0;
+    int n_store_first = 0;
+    bool store_first_ok = false;
     int64_t o_gshadow = 0;
     std::vector<int32_t> tok_ptr, tok_span;      // training: for every question-token row the span means it belongs to (CSR over the span bucket's instances)
     int64_t off_tok_ptr = 0, off_tok_span = 0;                       // 64-bit fixed-point shadows of every weight gradient (two floats per element)
@@ -482,6 +492,51 @@ int64_t ctx_weight_floats(const stair_ctx *ctx) {
 // order by one small kernel (grad_fanin_kernel).  The columns below replace the operand columns wherever a gradient is scattered.
 struct GEdge { int32_t slot; int level; int bidx, col, pos; int width; };
 enum { FAN_VEC = 0, FAN_MAP = 1, FAN_ATT = 2 };
+
+// First-touch stores.  The backward pass walks the levels from the top down and a gradient target of the map arena (a slot or one of
+// its staging tiles) has at most one writer per level, so the first writer of target j of a slot (0: the slot, j >= 1: staging tile
+// j - 1) is reader j of the HIGHEST level that has more than j readers of the slot.  Where that writer is a tile chain whose tail
+// writes the whole [T, H] tile (operand 0 of Filter, FilterFrame variant != 0, HasItem, Localize, Superlative, Temporal), the pass
+// need not clear the target: the chain stores its rows instead of adding them to zeros (STAIR_TILE_STORE_FIRST in Bucket::scol,
+// csrc/tile_mlp.hip).  Every other target -- first written by a row kernel (AttnVideo, ExistsFrame, Superlative's action rows), or
+// written by nobody (a clip tile no module reads still feeds BPTT) -- is listed in clear_tiles.  E: the map edges as assign() sorted them.
+void mark_store_first(stair_plan *pl, const std::vector<GEdge> &E) {
+    const int n_targets = pl->n_map + pl->n_map_stage;
+    std::vector<char> stored(n_targets, 0);
+    pl->n_store_first = 0;
+    for (Bucket &b : pl->buckets) { b.scol.clear(); b.soff = -1; }
+    auto chain_writer = [&](const GEdge &g) {
+        if (g.bidx < 0 || g.col != 0) return false;
+        const Bucket &b = pl->buckets[g.bidx];
+        return b.op == STAIR_OP_FILTER || (b.op == STAIR_OP_FILTERFRAME && b.variant != 0) || b.op == STAIR_OP_HASITEM ||
+               b.op == STAIR_OP_LOCALIZE || b.op == STAIR_OP_SUPERLATIVE || b.op == STAIR_OP_TEMPORAL;
+    };
+    for (size_t i = 0; i < E.size();) {
+        size_t e = i;
+        while (e < E.size() && E[e].slot == E[i].slot) ++e;
+        size_t covered = 0;                                               // targets of this slot that a higher level has written
+        for (size_t z = e; z > i;) {                                      // level groups, highest level first
+            size_t a = z;
+            while (a > i && E[a - 1].level == E[z - 1].level) --a;
+            for (size_t k = a + covered; k < z; ++k) {                    // reader k - a of this level is the first writer of target k - a
+                if (!chain_writer(E[k])) continue;
+                Bucket &b = pl->buckets[E[k].bidx];
+                if (b.scol.empty()) b.scol = b.gcol[0];
+                const int32_t target = b.gcol[0][E[k].pos];
+                if (target < 0 || target >= n_targets || stored[target]) continue;
+                b.scol[E[k].pos] = target | STAIR_TILE_STORE_FIRST;
+                stored[target] = 1;
+                ++pl->n_store_first;
+            }
+            covered = std::max(covered, z - a);
+            z = a;
+        }
+        i = e;
+    }
+    pl->clear_tiles.clear();
+    for (int t = 0; t < n_targets; ++t)
+        if (!stored[t]) pl->clear_tiles.push_back(t);
+}
 
 // vec_fix: where a vec-arena staging index was written with the provisional numbering n_vec + j; the layout pass moves the vec staging
 // rows behind the map staging tiles (the gradient block mirrors [vec arena | map arena]) and adds the difference (fix_vec_staging)
@@ -587,6 +642,7 @@ int build_grad_fanin(stair_plan *pl, int T, std::vector<int32_t *> &vec_fix) {
     assign(ev, FAN_VEC, pl->n_vec, pl->n_vec_stage, lv);
     assign(em, FAN_MAP, pl->n_map, pl->n_map_stage, lm);
     assign(ea, FAN_ATT, pl->n_att, pl->n_att_stage, la);
+    mark_store_first(pl, em);
     pl->fanin_first.assign(pl->n_levels + 1, 0);
     pl->fanin_count.assign(pl->n_levels + 1, 0);
     for (int L = 0; L <= pl->n_levels; ++L) {
@@ -1051,6 +1107,8 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     for (Bucket &b : pl->buckets)
         for (int c = 0; c < 8; ++c) idx_ints += align_up((int64_t)b.col[c].size(), 4) + align_up((int64_t)b.gcol[c].size(), 4);
     if (pl->train) {
+        for (const Bucket &b : pl->buckets) idx_ints += align_up((int64_t)b.scol.size(), 4);
+        idx_ints += align_up((int64_t)pl->clear_tiles.size(), 4);
         // token row -> the spans that average over it (their gradient reaches the row by a gather in span order: no atomics)
         pl->tok_ptr.assign(pl->rows_q + 1, 0);
         pl->tok_span.clear();
@@ -1107,6 +1165,9 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     if (pl->train) {
         pl->off_groots = push(pl->groots); pl->off_fanin = push(pl->fanin);
         pl->off_tok_ptr = push(pl->tok_ptr); pl->off_tok_span = push(pl->tok_span);
+        for (Bucket &b : pl->buckets)
+            if (!b.scol.empty()) b.soff = push(b.scol);
+        pl->off_clear = push(pl->clear_tiles);
     }
     if (pl->train)
         for (int w = 0; w < WF_COUNT; ++w) { pl->wg_off_idx[w] = push(wg_idx[w]); pl->wg_off_rs[w] = push(wg_rs[w]); }
@@ -1277,6 +1338,14 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
         pl->o_gExtra = take(I, 64);
     }
     pl->total = align_up(o, 64);
+    if (pl->train) {
+        // the marks hold for a pass that runs the fused chains (their transposed planes are laid out), whose every marked writer IS a chain
+        // (Temporal's needs its dZ region) and whose indices leave the bit free
+        bool ok = pl->o_wfragT > 0 && H % 4 == 0 && (int64_t)pl->n_map + pl->n_map_stage < STAIR_TILE_STORE_FIRST;
+        for (const Bucket &b : pl->buckets)
+            if (b.op == STAIR_OP_TEMPORAL && b.cnt > 0 && b.dzA < 0) ok = false;
+        pl->store_first_ok = ok;
+    }
     if (debug && pl->train) {
         fprintf(stderr, "weight-gradient regions (instances of T rows):");
         for (int w = 0; w < WF_COUNT; ++w) fprintf(stderr, " %ld", (long)pl->wg_rows[w]);
@@ -1306,6 +1375,14 @@ extern "C" int stair_plan_get_info(const stair_plan *pl, stair_plan_info *info) 
     info->n_launches = launches; info->n_levels = pl->n_levels; info->n_questions = pl->n; info->T = pl->T;
     info->n_aliased = pl->n_aliased;
     info->n_vec_stage = pl->n_vec_stage; info->n_map_stage = pl->n_map_stage; info->n_att_stage = pl->n_att_stage;
+    return 0;
+}
+
+extern "C" int stair_plan_store_first_counts(const stair_plan *pl, int32_t *n_store_first, int32_t *n_cleared) {
+    STAIR_CHECK(pl && n_store_first && n_cleared, "null argument");
+    STAIR_CHECK(pl->train, "plan was not built with STAIR_PLAN_TRAIN");
+    *n_store_first = pl->store_first_ok ? pl->n_store_first : 0;
+    *n_cleared = pl->store_first_ok ? (int32_t)pl->clear_tiles.size() : pl->n_map + pl->n_map_stage;
     return 0;
 }
 
@@ -2329,7 +2406,17 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     float *loss = loss_out ? loss_out : ws + pl->o_loss;
 
 #define RUN(x) do { if (int rc_ = (x)) return rc_; } while (0)
-    if (!(flags & STAIR_BWD_KEEP_ARENAS))
+    // Clear the gradient arenas -- except the map tiles whose first contribution of this pass is a chain tail that stores them
+    // (mark_store_first): one launch over [o_zero_beg, map tiles), the listed tiles, [behind the map tiles, o_zero_end).  The marks
+    // count only here: with STAIR_BWD_KEEP_ARENAS (everything was cleared, gradients are injected) and without the fused chains
+    // every tail adds, as it always did.
+    const bool store_first = !(flags & STAIR_BWD_KEEP_ARENAS) && pl->store_first_ok && pl->o_wfragT > 0 && tile_mlp_usable(H, T) &&
+                             (reinterpret_cast<uintptr_t>(ws) & 15) == 0;
+    if (store_first) {
+        const int64_t m0 = pl->o_gblock + (pl->o_map - pl->o_vec), m1 = m0 + (int64_t)(pl->n_map + pl->n_map_stage) * TH;
+        RUN(launch_zero_segments(ws + pl->o_zero_beg, m0 - pl->o_zero_beg, g_map, didx + pl->off_clear, (int)pl->clear_tiles.size(), TH,
+                                 ws + m1, pl->o_zero_end - m1, s));
+    } else if (!(flags & STAIR_BWD_KEEP_ARENAS))
         if (int rcz_ = launch_zero(ws + pl->o_zero_beg, (pl->o_zero_end - pl->o_zero_beg) * sizeof(float), s)) return rcz_;
 
     // transposed images of every 2-D weight that needs a dX product
@@ -2491,6 +2578,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         const int32_t *LEN = pl->ragged ? didx + b.off[6] : nullptr;
         // where the gradients of the operand columns go: the operand slots themselves, or staging slots (build_grad_fanin)
         const int32_t *G0 = didx + b.goff[0], *G1 = didx + b.goff[1], *G2 = didx + b.goff[2], *G4 = didx + b.goff[4];
+        const int32_t *G0c = store_first && b.soff >= 0 ? didx + b.soff : G0;      // the chain tails' copy of G0: first-touch marks
         const float *svA = ws + b.svA, *svB = ws + b.svB, *svK = ws + b.svK, *svCat = ws + b.svCat, *svHid = ws + b.svHid;
         const float *svRs = ws + b.svRs, *svSup = ws + b.svSup;
         // dZ of the bucket's first / second tile layer: its block of the weight's region (the product with X is deferred), else scratch
@@ -2513,7 +2601,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
             a.W[0] = WFT(slot3); a.act[0] = 3; a.act_scale = inv_keep; a.save[0] = gA;
             if (use_bits && b.bitA >= 0) a.act_bits[0] = BITS(b.bitA); else a.act_mask[0] = svA;
             a.W[1] = WFT(slot0); a.act[1] = 0;
-            a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = 1;
+            a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0c; a.acc_exclusive = 1;
             chain_queue.push_back(a);
             return 0;
         };
@@ -2628,7 +2716,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                     if (use_bits && b.bitB >= 0) a.act_bits[0] = BITS(b.bitB); else a.act_mask[0] = svB;
                     if (use_bits && b.bitA >= 0) a.act_bits[1] = BITS(b.bitA); else a.act_mask[1] = svA;
                     a.W[2] = WFT(WF_FF0 + v); a.act[2] = 0;
-                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = 1;
+                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0c; a.acc_exclusive = 1;
                     chain_queue.push_back(a);
                     break;
                 }
@@ -2663,7 +2751,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                     a.X = gA; a.x_gstride = TH; a.in_scale = inv_keep; a.save_in = gA;
                     if (use_bits && b.bitA >= 0) a.in_bits = BITS(b.bitA); else { a.in_mask = svA; a.in_mask_gstride = TH; }
                     a.n_layers = 1; a.W[0] = WFT(WF_HI0); a.act[0] = 0;
-                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = 1;
+                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0c; a.acc_exclusive = 1;
                     chain_queue.push_back(a);
                     break;
                 }
@@ -2712,7 +2800,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                     a.ln_bwd = 1; a.in_mask = svA; a.in_mask_gstride = TH; a.in_scale = inv_keep; a.save_in = gA;
                     a.gamma = W.ln_w; a.dgamma = W.dln_w; a.dbeta = W.dln_b;
                     a.n_layers = 1; a.W[0] = WFT(WF_TD); a.act[0] = 0;
-                    a.tail = STAIR_TILE_ROWSCALE_ADJ; a.out = g_map; a.out_gstride = TH; a.out_idx = G0; a.acc_exclusive = 1;
+                    a.tail = STAIR_TILE_ROWSCALE_ADJ; a.out = g_map; a.out_gstride = TH; a.out_idx = G0c; a.acc_exclusive = 1;
                     a.adj_feat = map; a.adj_feat_gstride = TH; a.adj_feat_idx = I0;
                     a.adj_rs = att; a.adj_rs_idx = I3; a.adj_drs = g_att;
                     chain_queue.push_back(a);

@@ -644,6 +644,45 @@ int launch_zero(void *ptr, int64_t bytes, hipStream_t s) {
     return 0;
 }
 
+// The same over a segment table, still ONE launch: [head, head + head_floats), the tiles tiles[0 .. n_tiles) of tile_floats floats
+// each behind tile_base, [tail, tail + tail_floats).  A workgroup clears one tile, or a chunk of that size (at least 32 KB) of the
+// head or the tail.  Every pointer 16-byte aligned, every count a multiple of 4 (stair_plan_backward: the arenas that no first-touch
+// store covers).
+__global__ __launch_bounds__(256) void zero_fill_segments_kernel(uint4 *head, int64_t head16, int head_blocks, uint4 *tile_base, const int32_t *tiles,
+                                                                 int n_tiles, int64_t tile16, uint4 *tail, int64_t tail16, int64_t chunk16) {
+    const int b = blockIdx.x;
+    uint4 *p;
+    int64_t n;
+    if (b < head_blocks) {
+        const int64_t off = (int64_t)b * chunk16;
+        p = head + off; n = std::min(chunk16, head16 - off);
+    } else if (b < head_blocks + n_tiles) {
+        p = tile_base + (int64_t)tiles[b - head_blocks] * tile16; n = tile16;
+    } else {
+        const int64_t off = (int64_t)(b - head_blocks - n_tiles) * chunk16;
+        p = tail + off; n = std::min(chunk16, tail16 - off);
+    }
+    for (int64_t i = threadIdx.x; i < n; i += 256) p[i] = uint4{0u, 0u, 0u, 0u};
+}
+
+int launch_zero_segments(float *head, int64_t head_floats, float *tile_base, const int32_t *tiles, int n_tiles, int64_t tile_floats,
+                         float *tail, int64_t tail_floats, hipStream_t s) {
+    STAIR_CHECK(head_floats >= 0 && tail_floats >= 0 && n_tiles >= 0 && tile_floats > 0, "zero fill: bad segment table");
+    STAIR_CHECK(head_floats % 4 == 0 && tail_floats % 4 == 0 && tile_floats % 4 == 0, "zero fill: segments of whole 16-byte words");
+    STAIR_CHECK(((reinterpret_cast<uintptr_t>(head) | reinterpret_cast<uintptr_t>(tile_base) | reinterpret_cast<uintptr_t>(tail)) & 15) == 0,
+                "zero fill: 16-byte aligned segments");
+    const int64_t tile16 = tile_floats / 4, chunk16 = std::max<int64_t>(tile16, 2048);
+    const int64_t hb = (head_floats / 4 + chunk16 - 1) / chunk16, tb = (tail_floats / 4 + chunk16 - 1) / chunk16;
+    const int64_t blocks = hb + n_tiles + tb;
+    if (blocks == 0) return 0;
+    STAIR_CHECK(blocks < (1ll << 31), "zero fill: too many segments");
+    STAIR_ACCT("zero_fill", (head_floats + tail_floats + (int64_t)n_tiles * tile_floats) * 4);
+    hipLaunchKernelGGL(zero_fill_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<uint4 *>(head), head_floats / 4, (int)hb,
+                       reinterpret_cast<uint4 *>(tile_base), tiles, n_tiles, tile16, reinterpret_cast<uint4 *>(tail), tail_floats / 4, chunk16);
+    STAIR_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace stair
 
 extern "C" int stair_l2normalize_fwd(const float *x, float *out, int32_t n, int32_t H, stair_stream stream) {

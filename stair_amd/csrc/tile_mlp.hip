@@ -649,7 +649,10 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             }
             p.save_bits[p.n_layers - 1][(int64_t)inst * TM_H + 64 * wave + lane] = obits;
         }
-        const int64_t oslot = p.out_idx ? __builtin_amdgcn_readfirstlane(p.out_idx[inst]) : inst;
+        // backward chains (forms 2 and 3): bit STAIR_TILE_STORE_FIRST of an out_idx entry marks a target nothing has written yet
+        const int oraw = p.out_idx ? __builtin_amdgcn_readfirstlane(p.out_idx[inst]) : (int)inst;
+        const bool ofirst = KIND >= 2 && (oraw & STAIR_TILE_STORE_FIRST) != 0;
+        const int64_t oslot = KIND >= 2 ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
         if (KIND == 2) {
             // tail ROWSCALE_ADJ: the staged rows are G = dZ W, the gradient of the SCALED input r_t feat_t of the dense layer:
             // d feat_t += r_t G_t (one dword per lane, 256 contiguous bytes per wave-instruction), d r_t += G_t . feat_t
@@ -668,7 +671,22 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 f1[j] = tm_ld<NT>(feat + (int64_t)ts * TM_H + 256 + 4 * lane);
                 rr[j] = rs[ts];
             }
-            if (p.acc_exclusive) {                  // read - add - write instead of atomics (see ACCUMULATE); a branch of its own:
+            if (ofirst) {                           // first contribution to a tile the pass has not cleared: rows stored, the target not read
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int t = wave + 8 * j;
+                    if (t < T) {
+                        const v4f g0 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                        float d = 0.f;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
+                        d = wave_sum(d);
+                        if (lane == 0) unsafeAtomicAdd(drs + t, d);
+                        *reinterpret_cast<v4f *>(dst + (int64_t)t * TM_H + 4 * lane) = rr[j] * g0;
+                        *reinterpret_cast<v4f *>(dst + (int64_t)t * TM_H + 256 + 4 * lane) = rr[j] * g1;
+                    }
+                }
+            } else if (p.acc_exclusive) {           // read - add - write instead of atomics (see ACCUMULATE); a branch of its own:
                 v4f o0[8], o1[8];                   // a condition inside the unrolled loops made every load wait and spill
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
@@ -728,6 +746,16 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 if (KIND != 3) break;
                 // one dword per lane, 256 contiguous bytes per wave-instruction: the shape float atomics run at full rate in
                 // (MI355X_MICROARCH.md "Global float atomics"; 16-byte-strided lanes spread an instruction over 1 KB)
+                if (ofirst) {
+                    // the first contribution of the pass to a tile that was not cleared (stair_plan_backward marks it): what the
+                    // read - add - write below leaves in a zeroed tile, without the 128 KB read (a branch of its own, like that one)
+                    for (int t = wave; t < T; t += 8) {
+                        float *dst = p.out + oslot * p.out_gstride + (int64_t)t * TM_H;
+                        *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane);
+                        *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                    }
+                    break;
+                }
                 if (p.acc_exclusive) {
                     // no other instance of this launch adds into this tile (the caller's promise; stair_plan_backward's fan-in staging
                     // gives every same-level reader of a slot a target of its own): whole rows read, added and written back, every

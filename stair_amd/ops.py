@@ -217,10 +217,12 @@ def lstm_bidir(x, seq_off, max_len, weights, save=False, coop=True, seq_len=None
     return (out, h_n, xproj, cbuf) if save else (out, h_n)
 
 
-def lstm_bidir_bwd(x, seq_off, max_len, weights, out, gates, cbuf, d_out, d_hn=None, coop=True, seq_len=None):
+def lstm_bidir_bwd(x, seq_off, max_len, weights, out, gates, cbuf, d_out, d_hn=None, coop=True, seq_len=None, slabs=False, hprev=None):
     """Gradients of (w_ih, w_hh, b_ih, b_hh) x 2 directions given d_out [rows, 2Hh] and d_hn [n, 2Hh].
     `gates` (from lstm_bidir(save=True)) is overwritten.  coop: use the cooperative BPTT kernel where it applies
-    (Hh = 256, split matmul modes); seq_len: per-sequence lengths of padded storage (int32 [n])."""
+    (Hh = 256, split matmul modes); seq_len: per-sequence lengths of padded storage (int32 [n]).
+    slabs: pass the scratch of the slab-reduced weight-gradient products (stair_lstm_bwd_args.tn_ws), as stair_plan_backward does:
+    from 2048 rows on dW_hh then reads `out` shifted by a row instead of a copy.  hprev: the caller's [rows, 2Hh] scratch."""
     rows, I = x.shape
     n = seq_off.numel() - 1
     Hh = weights[1].shape[1]
@@ -232,7 +234,14 @@ def lstm_bidir_bwd(x, seq_off, max_len, weights, out, gates, cbuf, d_out, d_hn=N
         a.x_bf16 = x.data_ptr()
     a.seq_off = seq_off.data_ptr()
     pack_ws = torch.empty(8 * Hh * Hh, device=x.device, dtype=torch.float32)
-    hprev = torch.empty(rows, 2 * Hh, device=x.device, dtype=torch.float32)
+    if hprev is None:
+        hprev = torch.empty(rows, 2 * Hh, device=x.device, dtype=torch.float32)
+    if slabs:
+        m = max(rows & ~31, 64)
+        per_dir = sum((int(lib.stair_gemm_tn_slabs_scratch(m, 4 * Hh, k)) + 63) // 64 * 64 for k in (Hh, I))
+        per_dir = max(per_dir, (int(lib.stair_gemm_tn_slabs_scratch(m, 4 * Hh, Hh)) + 63) // 64 * 64 + (8 * 4 * Hh * I + 63) // 64 * 64)
+        tn_ws = torch.empty(2 * per_dir, device=x.device, dtype=torch.float32)
+        a.tn_ws, a.tn_ws_floats = tn_ws.data_ptr(), tn_ws.numel()
     for d in range(2):
         a.w_hh[d] = weights[4 * d + 1].data_ptr()
         a.dw_ih[d], a.dw_hh[d] = grads[4 * d].data_ptr(), grads[4 * d + 1].data_ptr()
