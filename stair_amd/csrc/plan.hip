@@ -256,12 +256,104 @@ struct Node {
     int bop = -1, bvariant = 0, bsub = 0, inst = -1;      // the bucket (level, bop, bvariant, bsub) that computes it and its instance there
 };
 
-// The module-level Linear layers that act on [T, H] tiles, as one table (fused tile operators pack their planes by these
-// ids; the backward pass groups the weight-gradient products by them).
+// The module-level Linear layers that act on [T, H] tiles (fused tile operators pack their planes by these ids; the backward pass
+// groups the weight-gradient products by them).
 enum { WF_F0 = 0, WF_F3 = 4, WF_FF0 = 8, WF_FF3 = 11, WF_FFD = 14, WF_HI0 = 15, WF_LV0 = 16, WF_LV3 = 17, WF_TD = 18, WF_COUNT = 19 };
 // plane images of the vector-level modules' weights (forward only): one [H, H] image per H-wide column block of a first layer
 enum { WV_CMP = 19, WV_EQ = 21, WV_XOR = 23, WV_TA0 = 26, WV_TA3 = 28, WV_EX0 = 29, WV_EX3 = 32,
        WV_FD = 33, WV_LK = 34, WV_DEC0 = 35 /* four [512 x 512] blocks: (output block, input segment) */, WV_END = 39 };
+// Vector-level weights whose gradient is ONE product per weight over all buckets that use it (training plans): the dZ rows
+// and the saved inputs of every bucket lie back to back in per-weight regions, like the map level's.  K = columns of the input.
+enum { VD_CMP = 0, VD_EQ, VD_XOR, VD_TA0, VD_TA3, VD_EX0, VD_EX3, VD_FD, VD_COUNT };
+
+struct Lin { const float *w = nullptr, *b = nullptr; float *dw = nullptr, *db = nullptr; int id = -1; };
+struct Weights {
+    Lin compare, equals, exists0, exists3, f0[4], f3[4], fdense, ff0[3], ff3[3], ffatt, ffdense, hi0, hi3, lv0, lv3,
+        lk, supdense, tdense, ta0, ta3, xorl, dec0, dec3;
+    const float *beta = nullptr, *ln_w = nullptr, *ln_b = nullptr;
+    float *dbeta = nullptr, *dln_w = nullptr, *dln_b = nullptr;
+    const float *relate[3][6] = {};
+    float *drelate[3][6] = {};
+    const float *enc[2][8] = {};   // [video|text][w_ih, w_hh, b_ih, b_hh, then reverse]
+    float *denc[2][8] = {};
+};
+
+// THE table of the Linear layers that the plan runner launches as matrix products: which module uses which weight, as what.
+// Everything that used to restate this -- the weights of a bucket, the planes a pass packs, the matrices it transposes, the
+// deferred weight-gradient products, the touched mask -- walks these rows.  (The [*, 1] attention / score layers of Filter,
+// FilterFrame and HasItem are row dots, not products, and are not here; neither are the LSTMs, Relate, LayerNorm and Temporal's
+// relate nets.)
+// The ROW ORDER is the order in which a backward pass transposes the matrices in its one launch_transpose_many call (it fixes
+// first_tile and hence which workgroup does what); the planes of one launch_pack_wfrag_many call are packed in WF_* / WV_* order,
+// which weight_index() recovers from the ids.  Keep all three when adding a row.
+struct WeightRow {
+    Lin &(*lin)(Weights &);
+    const char *prefix;           // state-dict name behind "submodules."
+    int wf;                       // WF_* id (tile-level layer), -1: none
+    int wv, nblk, nseg;           // WV_* slot of its first [H, H] plane block, -1: none; W is [nblk * H, nseg * H]
+    int vd;                       // VD_* id (vector-level layer with a per-weight gradient region), -1: none
+    int op, op2;                  // the module(s) that use it (Superlative shares Localize's weights, module_net.py:31-32); -1: the decoder
+    int variant;                  // ... in this keyword variant only; -1: all
+    int layer;                    // 0 / 1: first / second layer of the module's tile MLP (wf) or vector-level MLP (vd); 2: neither
+    bool used_by(int o, int v) const { return (op == o || op2 == o) && (variant < 0 || variant == v); }
+};
+#define STAIR_LIN(m) [](Weights &W) -> Lin & { return W.m; }
+// first (.0) / second (.3) layer of the keyword variant v of Filter's / FilterFrame's tile MLP
+#define STAIR_KW_ROW0(m, id, prefix, o, v) {STAIR_LIN(m[v]), prefix ".0", id + v, -1, 0, 0, -1, o, -1, v, 0}
+#define STAIR_KW_ROW3(m, id, prefix, o, v) {STAIR_LIN(m[v]), prefix ".3", id + v, -1, 0, 0, -1, o, -1, v, 1}
+const WeightRow kWeightRows[] = {
+    {STAIR_LIN(compare), "Compare.param.0", -1, WV_CMP, 1, 2, VD_CMP, STAIR_OP_COMPARE, -1, -1, 0},
+    {STAIR_LIN(equals), "Equals.param.0", -1, WV_EQ, 1, 2, VD_EQ, STAIR_OP_EQUALS, -1, -1, 0},
+    {STAIR_LIN(exists0), "Exists.param.0", -1, WV_EX0, 1, 3, VD_EX0, STAIR_OP_EXISTS, -1, -1, 0},
+    {STAIR_LIN(exists3), "Exists.param.3", -1, WV_EX3, 1, 1, VD_EX3, STAIR_OP_EXISTS, -1, -1, 1},
+    STAIR_KW_ROW0(f0, WF_F0, "Filter.param.representation", STAIR_OP_FILTER, 0),
+    STAIR_KW_ROW0(f0, WF_F0, "Filter.param.actions", STAIR_OP_FILTER, 1),
+    STAIR_KW_ROW0(f0, WF_F0, "Filter.param.objects", STAIR_OP_FILTER, 2),
+    STAIR_KW_ROW0(f0, WF_F0, "Filter.param.relations", STAIR_OP_FILTER, 3),
+    STAIR_KW_ROW3(f3, WF_F3, "Filter.param.representation", STAIR_OP_FILTER, 0),
+    STAIR_KW_ROW3(f3, WF_F3, "Filter.param.actions", STAIR_OP_FILTER, 1),
+    STAIR_KW_ROW3(f3, WF_F3, "Filter.param.objects", STAIR_OP_FILTER, 2),
+    STAIR_KW_ROW3(f3, WF_F3, "Filter.param.relations", STAIR_OP_FILTER, 3),
+    {STAIR_LIN(fdense), "Filter.dense.0", -1, WV_FD, 1, 1, VD_FD, STAIR_OP_FILTER, -1, -1, 0},      // (its input: the pooled rows)
+    STAIR_KW_ROW0(ff0, WF_FF0, "FilterFrame.param.representation", STAIR_OP_FILTERFRAME, 0),
+    STAIR_KW_ROW0(ff0, WF_FF0, "FilterFrame.param.relations", STAIR_OP_FILTERFRAME, 1),
+    STAIR_KW_ROW0(ff0, WF_FF0, "FilterFrame.param.actions", STAIR_OP_FILTERFRAME, 2),
+    STAIR_KW_ROW3(ff3, WF_FF3, "FilterFrame.param.representation", STAIR_OP_FILTERFRAME, 0),
+    STAIR_KW_ROW3(ff3, WF_FF3, "FilterFrame.param.relations", STAIR_OP_FILTERFRAME, 1),
+    STAIR_KW_ROW3(ff3, WF_FF3, "FilterFrame.param.actions", STAIR_OP_FILTERFRAME, 2),
+    {STAIR_LIN(ffdense), "FilterFrame.dense.0", WF_FFD, -1, 0, 0, -1, STAIR_OP_FILTERFRAME, -1, -1, 2},
+    {STAIR_LIN(hi0), "HasItem.param.0", WF_HI0, -1, 0, 0, -1, STAIR_OP_HASITEM, -1, -1, 0},
+    {STAIR_LIN(lv0), "Localize.video_linear.0", WF_LV0, -1, 0, 0, -1, STAIR_OP_LOCALIZE, STAIR_OP_SUPERLATIVE, -1, 0},
+    {STAIR_LIN(lv3), "Localize.video_linear.3", WF_LV3, -1, 0, 0, -1, STAIR_OP_LOCALIZE, STAIR_OP_SUPERLATIVE, -1, 1},
+    {STAIR_LIN(lk), "Localize.keyword_linear.0", -1, WV_LK, 1, 1, -1, STAIR_OP_LOCALIZE, STAIR_OP_SUPERLATIVE, -1, 2},
+    {STAIR_LIN(supdense), "Superlative.dense.0", -1, -1, 0, 0, -1, STAIR_OP_SUPERLATIVE, -1, -1, 2},
+    {STAIR_LIN(tdense), "Temporal.dense.0", WF_TD, -1, 0, 0, -1, STAIR_OP_TEMPORAL, -1, -1, 0},
+    {STAIR_LIN(ta0), "ToAction.param.0", -1, WV_TA0, 1, 2, VD_TA0, STAIR_OP_TOACTION, -1, -1, 0},
+    {STAIR_LIN(ta3), "ToAction.param.3", -1, WV_TA3, 1, 1, VD_TA3, STAIR_OP_TOACTION, -1, -1, 1},
+    {STAIR_LIN(xorl), "Xor.param.0", -1, WV_XOR, 1, 3, VD_XOR, STAIR_OP_XOR, -1, -1, 0},
+    {STAIR_LIN(dec0), "decoder.0", -1, WV_DEC0, 2, 2, -1, -1, -1, -1, 2},
+    {STAIR_LIN(dec3), "decoder.3", -1, -1, 0, 0, -1, -1, -1, -1, 2},
+};
+#undef STAIR_KW_ROW3
+#undef STAIR_KW_ROW0
+#undef STAIR_LIN
+static_assert(sizeof(kWeightRows) / sizeof(kWeightRows[0]) <= 32, "TransposeBatch holds 32 matrices");
+
+// the rows by id: wf[WF_*], wv[WV_* slot of a weight's first plane] (null at every other slot), vd[VD_*]
+struct WeightIndex { const WeightRow *wf[WF_COUNT], *wv[WV_END], *vd[VD_COUNT]; };
+inline const WeightIndex &weight_index() {
+    static const WeightIndex ix = [] {
+        WeightIndex x = {};
+        for (const WeightRow &r : kWeightRows) {
+            if (r.wf >= 0) x.wf[r.wf] = &r;
+            if (r.wv >= 0) x.wv[r.wv] = &r;
+            if (r.vd >= 0) x.vd[r.vd] = &r;
+        }
+        return x;
+    }();
+    return ix;
+}
+inline int vd_cols(int w, int H) { return weight_index().vd[w]->nseg * H; }
 
 struct Bucket {
     int64_t dzA = -1, dzB = -1;   // training: this bucket's blocks inside the per-WEIGHT dZ regions (first / second layer of its tile MLP)
@@ -289,36 +381,18 @@ struct Bucket {
     int64_t bitA = -1, bitB = -1, bitC = -1;
 };
 
-// Vector-level weights whose gradient is ONE product per weight over all buckets that use it (training plans): the dZ rows
-// and the saved inputs of every bucket lie back to back in per-weight regions, like the map level's.  K = columns of the input.
-enum { VD_CMP = 0, VD_EQ, VD_XOR, VD_TA0, VD_TA3, VD_EX0, VD_EX3, VD_FD, VD_COUNT };
-inline int vd_cols(int w, int H) { return (w == VD_XOR || w == VD_EX0) ? 3 * H : (w == VD_CMP || w == VD_EQ || w == VD_TA0) ? 2 * H : H; }
-// first-layer (reads the packed operands; Filter: the pooled rows) and second-layer (reads the saved hidden rows) weight of a bucket
-inline void bucket_vec_weights(int op, int &v0, int &v3) {
-    v0 = v3 = -1;
-    switch (op) {
-        case STAIR_OP_COMPARE: v0 = VD_CMP; break;
-        case STAIR_OP_EQUALS: v0 = VD_EQ; break;
-        case STAIR_OP_XOR: v0 = VD_XOR; break;
-        case STAIR_OP_TOACTION: v0 = VD_TA0; v3 = VD_TA3; break;
-        case STAIR_OP_EXISTS: v0 = VD_EX0; v3 = VD_EX3; break;
-        case STAIR_OP_FILTER: v0 = VD_FD; break;
-        default: break;
+// first-layer weight (reads the module's input tile; vector level: the packed operands, Filter: the pooled rows) and second-layer
+// weight (reads the saved first activation / hidden rows) of a bucket: WF_* ids of its tile MLP, VD_* ids of its vector-level
+// layers; -1 = none
+struct BucketLayers { int w0 = -1, w3 = -1, v0 = -1, v3 = -1; };
+inline BucketLayers bucket_layers(const Bucket &b) {
+    BucketLayers u;
+    for (const WeightRow &r : kWeightRows) {
+        if (r.layer > 1 || !r.used_by(b.op, b.variant)) continue;
+        if (r.wf >= 0) (r.layer == 0 ? u.w0 : u.w3) = r.wf;
+        if (r.vd >= 0) (r.layer == 0 ? u.v0 : u.v3) = r.vd;
     }
-}
-
-// first-layer weight (reads the module's input tile) and second-layer weight (reads the saved first activation) of a bucket's
-// tile MLP, as WF_* ids; -1 = none
-void bucket_weights(const Bucket &b, int &w0, int &w3) {
-    w0 = w3 = -1;
-    switch (b.op) {
-        case STAIR_OP_FILTER: w0 = WF_F0 + b.variant; w3 = WF_F3 + b.variant; break;
-        case STAIR_OP_FILTERFRAME: w0 = WF_FF0 + b.variant; w3 = WF_FF3 + b.variant; break;
-        case STAIR_OP_HASITEM: w0 = WF_HI0; break;
-        case STAIR_OP_LOCALIZE: case STAIR_OP_SUPERLATIVE: w0 = WF_LV0; w3 = WF_LV3; break;
-        case STAIR_OP_TEMPORAL: w0 = WF_TD; break;
-        default: break;
-    }
+    return u;
 }
 
 }  // namespace
@@ -329,24 +403,34 @@ void bucket_weights(const Bucket &b, int &w0, int &w3) {
 // completed, then it goes back to a small process-wide pool (so a step does not pay a hipHostMalloc).
 namespace {
 struct PinnedBuf { int32_t *p = nullptr; size_t cap = 0; };
+// One region of a plan's workspace as the builder laid it out, in floats.  `name` is a static string; a name that begins with '.'
+// belongs to bucket `index` (stair_plan_regions prints it as b<index>(op<op>v<variant>).<name>), any other name with index >= 0
+// gets the index appended (wg_dz7).
+struct Region { const char *name; int32_t index; int64_t beg, end; };
 std::mutex g_pin_mu;
 std::vector<PinnedBuf> g_pin_pool;
 // Regions of the encoders' input projections, as offsets in floats from a base: [xproj video | xproj text | bias sums | video W_ih planes |
 // text W_ih planes | text row planes].  A function of the batch SHAPE only (clips, frames, token rows): the same layout inside a plan's
 // workspace and in a caller-owned buffer filled by stair_encoders_project before the plan is built.
+// `base`: where the block begins (a plan's workspace: its float offset there, recorded region by region in `rec`).
 struct ProjLayout { int64_t xpv, xpt, bias, wplanes, wplanes_t, xplanes_t, total; };
-static ProjLayout proj_layout(const stair_config &g, int64_t n_vid, int64_t T, int64_t rows_q) {
+static ProjLayout proj_layout(const stair_config &g, int64_t n_vid, int64_t T, int64_t rows_q, int64_t base = 0, std::vector<Region> *rec = nullptr) {
     const int64_t H = g.hidden_size, Ep = (g.text_size + 31) / 32 * 32;
     ProjLayout L;
-    int64_t at = 0;
-    auto take = [&](int64_t len) { const int64_t o = at; at += (len + 63) / 64 * 64; return o; };
-    L.xpv = take(n_vid * T * 4 * H);
-    L.xpt = take(rows_q * 4 * H);
-    L.bias = take(2 * 4 * H);
-    L.wplanes = g.video_size % 32 == 0 ? take(4 * H * g.video_size) : 0;
-    L.wplanes_t = take(4 * H * Ep);
-    L.xplanes_t = take(std::max<int64_t>(rows_q, 1) * Ep);
-    L.total = at;
+    int64_t at = base;
+    auto take = [&](const char *name, int64_t len) {
+        const int64_t o = at;
+        at += (len + 63) / 64 * 64;
+        if (rec && len > 0) rec->push_back({name, -1, o, o + len});
+        return o;
+    };
+    L.xpv = take("xpv", n_vid * T * 4 * H);
+    L.xpt = take("xpt", rows_q * 4 * H);
+    L.bias = take("bias", 2 * 4 * H);
+    L.wplanes = g.video_size % 32 == 0 ? take("wplanes", 4 * H * g.video_size) : 0;
+    L.wplanes_t = take("wplanes_t", 4 * H * Ep);
+    L.xplanes_t = take("xplanes_t", std::max<int64_t>(rows_q, 1) * Ep);
+    L.total = at - base;
     return L;
 }
 
@@ -460,8 +544,19 @@ struct stair_plan {
     // layout depends on the batch shape alone (proj_layout), so that the projections can be enqueued BEFORE the plan exists
     bool ext_proj = false;
     float *proj = nullptr;
-    int64_t o_idx = 0, o_vec = 0, o_map = 0, o_att = 0, o_tok = 0, o_qfeat = 0, o_vhn = 0, o_xpv = 0, o_xpt = 0,
-            o_bias = 0, o_wpack = 0, o_wplanes = 0, o_wplanes_t = 0, o_xplanes_t = 0, o_coop = 0, o_coop2 = 0, o_splitk = 0, o_tmpA = 0, o_tmpB = 0, o_kbuf = 0, o_cat = 0, o_hid = 0, o_rs = 0, o_sup = 0, o_extra = 0,
+    ProjLayout pj = {};             // the projections' regions as offsets from proj_base(): the workspace, or the caller's buffer
+    float *proj_base(float *ws) const { return ext_proj ? proj : ws; }
+    std::vector<Region> regions;    // every region of the workspace, recorded as the builder assigns it (stair_plan_regions)
+    // the next `nfloats` floats of the workspace, aligned to `align` floats; recorded under `name` unless that is null
+    int64_t take(const char *name, int64_t nfloats, int64_t align, int32_t index = -1) {
+        total = align_up(total, align);
+        const int64_t r = total;
+        total += nfloats;
+        if (name && nfloats > 0) regions.push_back({name, index, r, r + nfloats});
+        return r;
+    }
+    int64_t o_idx = 0, o_vec = 0, o_map = 0, o_att = 0, o_tok = 0, o_qfeat = 0, o_vhn = 0,
+            o_wpack = 0, o_coop = 0, o_coop2 = 0, o_splitk = 0, o_tmpA = 0, o_tmpB = 0, o_kbuf = 0, o_cat = 0, o_hid = 0, o_rs = 0, o_sup = 0, o_extra = 0,
             o_logits = 0, o_status = 0, o_wfrag = 0, total = 0;
     // training only
     bool train = false;
@@ -474,6 +569,16 @@ struct stair_plan {
 };
 
 namespace {
+
+// need[WF_*]: the tile-level weights of the plan's buckets, those that `skip` names left out
+template <class Skip> void tile_weights_in_use(const stair_plan *pl, bool (&need)[WF_COUNT], Skip skip) {
+    std::fill(need, need + WF_COUNT, false);
+    for (const Bucket &b : pl->buckets) {
+        if (b.cnt == 0 || skip(b)) continue;
+        for (const WeightRow &r : kWeightRows)
+            if (r.wf >= 0 && r.used_by(b.op, b.variant)) need[r.wf] = true;
+    }
+}
 
 // floats needed for the transposed weight images used by the dX products (all 2-D weights)
 int64_t ctx_weight_floats(const stair_ctx *ctx) {
@@ -675,64 +780,25 @@ std::string where(int q, int i, int tok) {
     return s;
 }
 
-}  // namespace
-
-extern "C" int stair_plan_build(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
-                                const int32_t *span_lo, const int32_t *span_hi, const int32_t *q_off, int32_t T,
-                                int32_t flags, stair_plan **out) {
-    return stair_plan_build_shared(ctx, n, prog_off, tokens, span_lo, span_hi, q_off, n, nullptr, T, flags, out);
+// ---- the builder, in three steps called in sequence, with the plan as the only thing passed between them ----
+bool plan_debug() {                 // STAIR_PLAN_DEBUG=1: build statistics to stderr
+    static const bool on = env_int("STAIR_PLAN_DEBUG", 0) != 0;
+    return on;
 }
 
-extern "C" int stair_plan_build_shared(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
-                                       const int32_t *span_lo, const int32_t *span_hi, const int32_t *q_off,
-                                       int32_t n_videos, const int32_t *video_of_question, int32_t T,
-                                       int32_t flags, stair_plan **out) {
-    return stair_plan_build_ragged(ctx, n, prog_off, tokens, span_lo, span_hi, q_off, n_videos, video_of_question, nullptr, T, flags, out);
-}
-
-extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
-                                       const int32_t *span_lo, const int32_t *span_hi, const int32_t *q_off,
-                                       int32_t n_videos, const int32_t *video_of_question, const int32_t *video_len, int32_t T,
-                                       int32_t flags, stair_plan **out) {
-    STAIR_CHECK(ctx && prog_off && tokens && span_lo && span_hi && q_off && out, "null argument");
-    STAIR_CHECK(n > 0 && T > 0, "n and T must be positive");
-    STAIR_CHECK(n_videos > 0 && (video_of_question || n_videos == n), "video_of_question is required when n_videos != n");
-    if (video_of_question)
-        for (int q = 0; q < n; ++q)
-            STAIR_CHECK(video_of_question[q] >= 0 && video_of_question[q] < n_videos,
-                        "video_of_question[" + std::to_string(q) + "] out of range");
-    STAIR_CHECK(ctx->conv || T == ctx->cfg.max_video_length,
-                "Linear(T,T) Temporal nets need T == max_video_length (modules.py:266-277)");
-    auto plp = std::make_unique<stair_plan>();
-    stair_plan *pl = plp.get();
-    pl->cfg = ctx->cfg;
-    pl->n = n;
-    pl->T = T;
-    pl->train = (flags & STAIR_PLAN_TRAIN) != 0;
-    pl->ext_proj = (flags & STAIR_PLAN_EXT_PROJECTION) != 0;
-    const int ntok = prog_off[n];
-    pl->nodes.assign(ntok, Node());
-    pl->roots.assign(n, -1);
-    pl->n_vid = n_videos;
-    pl->n_map = n_videos;   // map slot v = encoded video v
-    pl->vlen.assign(n_videos, T);
-    if (video_len)
-        for (int v = 0; v < n_videos; ++v) {
-            STAIR_CHECK(video_len[v] >= 1 && video_len[v] <= T, "video_len[" + std::to_string(v) + "] must be in 1..T");
-            pl->vlen[v] = video_len[v];
-            if (video_len[v] != T) pl->ragged = true;
-        }
-    STAIR_CHECK(!pl->ragged || ctx->conv, "clips of different lengths need the Conv1d Temporal nets (Linear(T,T) fixes T, modules.py:266-277)");
+// 1. interpret the programs: every token becomes a node, every module node an instance of its bucket; buckets sorted by level
+int interpret_programs(stair_plan *pl, const int32_t *prog_off, const int32_t *tokens, const int32_t *span_lo, const int32_t *span_hi,
+                       const int32_t *q_off, const int32_t *video_of_question, const bool cse_on) {
+    const int n = pl->n, T = pl->T, ntok = prog_off[n];
     Builder B{pl};
     std::vector<int> stack;
     const auto t_begin = std::chrono::steady_clock::now();
-    static const bool debug = env_int("STAIR_PLAN_DEBUG", 0) != 0;         // build statistics to stderr
+    const bool debug = plan_debug();
     // Common-subexpression sharing across the batch (module_net.py:100-106 evaluates every node of every question; a node
     // whose operands are the encoded clip, keyword strings, identical question spans or other such nodes has the SAME value
     // wherever it occurs -- in another question about the same clip, or twice in one program).  key[i] names the computation
     // of token i ("" = not shareable); the first node with a key is computed, later ones alias its slot.  Filter ignores its
     // tensor keyword (its attention is identically 1, modules.py:354,373), so that operand does not enter the key.
-    const bool cse_on = !(flags & STAIR_PLAN_NO_CSE);
     // keys are interned: a computation is (tag, operand key ids) -> a small integer id; id 0 = not shareable
     struct CseKey {
         int32_t v[4];
@@ -834,6 +900,25 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
                     set_error(std::string("stair_plan_build: operand kind mismatch (") + what + ") at " + where(q, i, tok));
                     return 1;
                 };
+                // which bucket (level, tok, variant, sub) computes this node: the keyword variant of the module, -1 = a keyword it
+                // does not take (reported below, behind the operand-kind checks)
+                int variant = 0, sub = 0;
+                const int kw1 = c1.kind == STAIR_VAL_STR ? c1.aux : -1;
+                switch (tok) {
+                    case STAIR_OP_AND: case STAIR_OP_XORFRAME: sub = c0.kind; break;
+                    case STAIR_OP_FILTER:
+                        variant = c1.kind == STAIR_VAL_VEC ? 0 : kw1 == STAIR_KW_ACTIONS ? 1 : kw1 == STAIR_KW_OBJECTS ? 2 : kw1 == STAIR_KW_RELATIONS ? 3 : -1;
+                        break;
+                    case STAIR_OP_FILTERFRAME:
+                        variant = c1.kind == STAIR_VAL_VEC ? 0 : kw1 == STAIR_KW_RELATIONS ? 1 : kw1 == STAIR_KW_ACTIONS ? 2 : -1;
+                        break;
+                    case STAIR_OP_RELATE: variant = c0.aux == STAIR_KW_FORWARD ? 0 : 1; break;           // modules.py:429
+                    case STAIR_OP_SUPERLATIVE: variant = c0.aux == STAIR_KW_MIN ? 1 : 0; break;          // modules.py:245
+                    case STAIR_OP_TEMPORAL:
+                        variant = c0.aux == STAIR_KW_WHILE ? 0 : c0.aux == STAIR_KW_BEFORE ? 1 : c0.aux == STAIR_KW_AFTER ? 2 : c0.aux == STAIR_KW_BETWEEN ? 3 : -1;
+                        break;
+                    default: break;
+                }
                 switch (tok) {
                     case STAIR_OP_AND:
                     case STAIR_OP_XORFRAME: {
@@ -841,7 +926,7 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
                             return bad("needs two [H] vectors or two [T] frame attentions");
                         nd.kind = c0.kind;
                         nd.slot = c0.kind == STAIR_VAL_VEC ? pl->n_vec++ : pl->n_att++;
-                        Bucket &b = B.bucket(nd.level, tok, 0, c0.kind);
+                        Bucket &b = B.bucket(nd.level, tok, 0, sub);
                         b.col[0].push_back(c0.slot); b.col[1].push_back(c1.slot); b.col[2].push_back(nd.slot);
                         b.cnt++;
                         break;
@@ -886,12 +971,7 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
                     }
                     case STAIR_OP_FILTER: {
                         if (c0.kind != STAIR_VAL_MAP) return bad("Filter(feat [T,H], keyword)");
-                        int variant;
-                        if (c1.kind == STAIR_VAL_VEC) variant = 0;
-                        else if (c1.kind == STAIR_VAL_STR && c1.aux == STAIR_KW_ACTIONS) variant = 1;
-                        else if (c1.kind == STAIR_VAL_STR && c1.aux == STAIR_KW_OBJECTS) variant = 2;
-                        else if (c1.kind == STAIR_VAL_STR && c1.aux == STAIR_KW_RELATIONS) variant = 3;
-                        else return bad("Filter keyword must be a [H] vector or actions/objects/relations (modules.py:346-351)");
+                        if (variant < 0) return bad("Filter keyword must be a [H] vector or actions/objects/relations (modules.py:346-351)");
                         nd.kind = STAIR_VAL_VEC; nd.slot = pl->n_vec++;
                         Bucket &b = B.bucket(nd.level, tok, variant, 0);
                         b.col[0].push_back(c0.slot); b.col[1].push_back(nd.slot); b.col[6].push_back(Lq);
@@ -900,11 +980,7 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
                     }
                     case STAIR_OP_FILTERFRAME: {
                         if (c0.kind != STAIR_VAL_MAP) return bad("FilterFrame(feat [T,H], keyword)");
-                        int variant;
-                        if (c1.kind == STAIR_VAL_VEC) variant = 0;
-                        else if (c1.kind == STAIR_VAL_STR && c1.aux == STAIR_KW_RELATIONS) variant = 1;
-                        else if (c1.kind == STAIR_VAL_STR && c1.aux == STAIR_KW_ACTIONS) variant = 2;
-                        else return bad("FilterFrame keyword must be a [H] vector or relations/actions (modules.py:384-388)");
+                        if (variant < 0) return bad("FilterFrame keyword must be a [H] vector or relations/actions (modules.py:384-388)");
                         nd.kind = STAIR_VAL_MAP; nd.slot = pl->n_map++;
                         Bucket &b = B.bucket(nd.level, tok, variant, 0);
                         b.col[0].push_back(c0.slot); b.col[1].push_back(variant == 0 ? c1.slot : 0); b.col[2].push_back(nd.slot);
@@ -941,7 +1017,7 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
                     case STAIR_OP_RELATE: {
                         if (c0.kind != STAIR_VAL_STR || c1.kind != STAIR_VAL_FRAME) return bad("Relate(mode, attn [T])");
                         nd.kind = STAIR_VAL_FRAME; nd.slot = pl->n_att++;
-                        Bucket &b = B.bucket(nd.level, tok, c0.aux == STAIR_KW_FORWARD ? 0 : 1, 0);   // modules.py:429
+                        Bucket &b = B.bucket(nd.level, tok, variant, 0);
                         b.col[0].push_back(c1.slot); b.col[1].push_back(nd.slot); b.col[6].push_back(Lq);
                         b.cnt++;
                         break;
@@ -951,7 +1027,7 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
                             !(c1.kind == STAIR_VAL_MAP || c1.kind == STAIR_VAL_PAIR || c1.kind == STAIR_VAL_VEC))
                             return bad("Superlative(mode, actions [Ka,H], feat [T,H])");
                         nd.kind = STAIR_VAL_VEC; nd.slot = pl->n_vec++;
-                        Bucket &b = B.bucket(nd.level, tok, c0.aux == STAIR_KW_MIN ? 1 : 0, 0);       // modules.py:245
+                        Bucket &b = B.bucket(nd.level, tok, variant, 0);
                         b.col[0].push_back(c2.slot);          // feat map
                         b.col[1].push_back(b.nrows);          // first action row of this instance
                         const int Ka = c1.kind == STAIR_VAL_MAP ? Lq : (c1.kind == STAIR_VAL_PAIR ? 2 : 1);   // a [T,H] map = one action per frame of the clip
@@ -972,14 +1048,9 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
                     case STAIR_OP_TEMPORAL: {
                         if (c0.kind != STAIR_VAL_STR || c1.kind != STAIR_VAL_MAP || c2.kind != STAIR_VAL_ATT)
                             return bad("Temporal(mode, feat [T,H], attention [K,T])");
-                        int mode;
-                        if (c0.aux == STAIR_KW_WHILE) mode = 0;
-                        else if (c0.aux == STAIR_KW_BEFORE) mode = 1;
-                        else if (c0.aux == STAIR_KW_AFTER) mode = 2;
-                        else if (c0.aux == STAIR_KW_BETWEEN) mode = 3;
-                        else return bad("Temporal mode must be while/before/after/between (modules.py:263,279)");
+                        if (variant < 0) return bad("Temporal mode must be while/before/after/between (modules.py:263,279)");
                         nd.kind = STAIR_VAL_MAP; nd.slot = pl->n_map++; nd.rel = pl->n_att++;
-                        Bucket &b = B.bucket(nd.level, tok, mode, 0);
+                        Bucket &b = B.bucket(nd.level, tok, variant, 0);
                         b.col[0].push_back(c1.slot); b.col[1].push_back(c2.slot); b.col[2].push_back(c2.aux);
                         b.col[3].push_back(nd.rel); b.col[4].push_back(nd.slot); b.col[6].push_back(Lq);
                         b.cnt++;
@@ -993,19 +1064,7 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
                     default:
                         STAIR_FAIL("unknown module token at " + where(q, i, tok));
                 }
-                if (tok != STAIR_OP_ARRAY2) {         // which bucket computes this node, and as which of its instances
-                    int variant = 0, sub = 0;
-                    switch (tok) {
-                        case STAIR_OP_AND: case STAIR_OP_XORFRAME: sub = c0.kind; break;
-                        case STAIR_OP_FILTER:
-                            variant = c1.kind == STAIR_VAL_VEC ? 0 : (c1.aux == STAIR_KW_ACTIONS ? 1 : (c1.aux == STAIR_KW_OBJECTS ? 2 : 3)); break;
-                        case STAIR_OP_FILTERFRAME: variant = c1.kind == STAIR_VAL_VEC ? 0 : (c1.aux == STAIR_KW_RELATIONS ? 1 : 2); break;
-                        case STAIR_OP_RELATE: variant = c0.aux == STAIR_KW_FORWARD ? 0 : 1; break;
-                        case STAIR_OP_SUPERLATIVE: variant = c0.aux == STAIR_KW_MIN ? 1 : 0; break;
-                        case STAIR_OP_TEMPORAL:
-                            variant = c0.aux == STAIR_KW_WHILE ? 0 : (c0.aux == STAIR_KW_BEFORE ? 1 : (c0.aux == STAIR_KW_AFTER ? 2 : 3)); break;
-                        default: break;
-                    }
+                if (tok != STAIR_OP_ARRAY2) {         // ... and as which of its instances
                     nd.bop = tok; nd.bvariant = variant; nd.bsub = sub;
                     nd.inst = B.bucket(nd.level, tok, variant, sub).cnt - 1;
                 }
@@ -1055,9 +1114,14 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     std::sort(pl->buckets.begin(), pl->buckets.end(), [](const Bucket &a, const Bucket &b) {
         return std::tie(a.level, a.op, a.variant, a.sub) < std::tie(b.level, b.op, b.variant, b.sub);
     });
+    return 0;
+}
 
-    // ---- sizes & the device index buffer image --------------------------------------------
-    const int64_t H = ctx->cfg.hidden_size, A = ctx->cfg.answer_vocab_length;
+// 2. sizes, the gradient fan-in and the host image of the device index buffer -- together with the three regions the image refers
+// to by position (its own, the vec arena, the map arena), which therefore open the workspace layout
+int build_index_image(stair_plan *pl, const int32_t *q_off) {
+    const int n = pl->n, T = pl->T;
+    const int64_t H = pl->cfg.hidden_size;
     pl->maxV = n;
     for (Bucket &b : pl->buckets) {
         pl->n_levels = std::max(pl->n_levels, b.level + 1);
@@ -1089,15 +1153,6 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
         pl->off_roots = push(pl->roots);
         pl->off_lenv = push(pl->vlen);
     }
-    // layout (float offsets; vec and map arenas start on multiples of H so that any [H] row of
-    // either arena has a global row id relative to the workspace base)
-    int64_t o = 0;
-    auto take = [&](int64_t nfloats, int64_t align) {
-        o = align_up(o, align);
-        const int64_t r = o;
-        o += nfloats;
-        return r;
-    };
     std::vector<int32_t *> vec_fix;
     if (pl->train) {
         if (int rc = build_grad_fanin(pl, T, vec_fix)) return rc;
@@ -1130,17 +1185,19 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     std::vector<int32_t> wg_idx[WF_COUNT], wg_rs[WF_COUNT];
     if (pl->train) {
         for (const Bucket &b : pl->buckets) {
-            int w0, w3;
-            bucket_weights(b, w0, w3);
+            const int w0 = bucket_layers(b).w0;
             if (w0 < 0 || b.cnt == 0) continue;
             wg_idx[w0].insert(wg_idx[w0].end(), b.col[0].begin(), b.col[0].end());
             if (b.op == STAIR_OP_TEMPORAL) wg_rs[w0].insert(wg_rs[w0].end(), b.col[3].begin(), b.col[3].end());
         }
         for (int w = 0; w < WF_COUNT; ++w) idx_ints += align_up((int64_t)wg_idx[w].size(), 4) + align_up((int64_t)wg_rs[w].size(), 4);
     }
-    pl->o_idx = take(idx_ints, 64);
-    pl->o_vec = take((int64_t)pl->n_vec * H, H);
-    pl->o_map = take((int64_t)pl->n_map * T * H, H);
+    // layout (float offsets; vec and map arenas start on multiples of H so that any [H] row of
+    // either arena has a global row id relative to the workspace base)
+    pl->regions.reserve(64 + 12 * pl->buckets.size());
+    pl->o_idx = pl->take("idx", idx_ints, 64);
+    pl->o_vec = pl->take("vec", (int64_t)pl->n_vec * H, H);
+    pl->o_map = pl->take("map", (int64_t)pl->n_map * T * H, H);
     // resolve Superlative action row ids into global row ids (units of H floats from workspace base)
     if (pl->train && !vec_fix.empty()) {
         // vec staging rows live behind the map staging tiles: as vec-row indices relative to the gradient block's vec base
@@ -1172,48 +1229,62 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     if (pl->train)
         for (int w = 0; w < WF_COUNT; ++w) { pl->wg_off_idx[w] = push(wg_idx[w]); pl->wg_off_rs[w] = push(wg_rs[w]); }
     STAIR_CHECK((int64_t)pl->idx.size() == idx_ints, "internal: idx size");
-    pl->o_att = take((int64_t)std::max(pl->n_att, 1) * T, 64);
-    pl->o_tok = take((int64_t)pl->rows_q * H, 64);
-    pl->o_qfeat = take((int64_t)n * H, 64);
-    pl->o_vhn = take((int64_t)pl->n_vid * H, 64);
-    {   // input projections of the two encoders: xproj (the gates of a training plan), bias sums, W_ih planes of the video encoder (bf16
-        // features: 2 x [4H, V] bf16), and the text encoder's projection as a plane GEMM (W_ih and the token rows as zero-padded hi / lo
-        // planes, counted in floats) -- one block with the layout of proj_layout, here or in the caller's buffer (ext_proj)
-        const ProjLayout L = proj_layout(ctx->cfg, pl->n_vid, T, pl->rows_q);
-        const int64_t base = pl->ext_proj ? 0 : take(L.total, 64);
-        pl->o_xpv = base + L.xpv; pl->o_xpt = base + L.xpt; pl->o_bias = base + L.bias;
-        pl->o_wplanes = ctx->cfg.video_size % 32 == 0 ? base + L.wplanes : 0;
-        pl->o_wplanes_t = base + L.wplanes_t; pl->o_xplanes_t = base + L.xplanes_t;
+    return 0;
+}
+
+// 3. the rest of the workspace.  Every region is recorded as it is assigned: stair_plan::take for a region of its own, `piece`
+// for a bucket's part of a region that its weight's buckets share.
+int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
+    const int n = pl->n, T = pl->T;
+    const int64_t H = ctx->cfg.hidden_size, A = ctx->cfg.answer_vocab_length;
+    const int nb = (int)pl->buckets.size();
+    auto piece = [&](const char *name, int bi, int64_t beg, int64_t nfloats) {
+        if (nfloats > 0) pl->regions.push_back({name, bi, beg, beg + nfloats});
+        return beg;
+    };
+    pl->o_att = pl->take("att", (int64_t)std::max(pl->n_att, 1) * T, 64);
+    pl->o_tok = pl->take("tok", (int64_t)pl->rows_q * H, 64);
+    pl->o_qfeat = pl->take("qfeat", (int64_t)n * H, 64);
+    pl->o_vhn = pl->take("vhn", (int64_t)pl->n_vid * H, 64);
+    // input projections of the two encoders: xproj (the gates of a training plan), bias sums, W_ih planes of the video encoder (bf16
+    // features: 2 x [4H, V] bf16), and the text encoder's projection as a plane GEMM (W_ih and the token rows as zero-padded hi / lo
+    // planes, counted in floats) -- one block with the layout of proj_layout, here or in the caller's buffer (ext_proj)
+    if (pl->ext_proj) {
+        pl->pj = proj_layout(ctx->cfg, pl->n_vid, T, pl->rows_q);
+    } else {
+        pl->pj = proj_layout(ctx->cfg, pl->n_vid, T, pl->rows_q, align_up(pl->total, 64), &pl->regions);
+        pl->total = align_up(pl->total, 64) + pl->pj.total;
     }
-    pl->o_wpack = take(2 * 2 * H * H, 64);       // 8*Hh*Hh floats per encoder
+    pl->o_wpack = pl->take("wpack", 2 * 2 * H * H, 64);       // 8*Hh*Hh floats per encoder
     pl->coop_bytes = std::max(lstm_coop_ws_bytes(pl->n_vid), lstm_coop_ws_bytes(n));
     if (pl->train) pl->coop_bytes = std::max(pl->coop_bytes, std::max(lstm_coop_bwd_ws_bytes(pl->n_vid), lstm_coop_bwd_ws_bytes(n)));
-    pl->o_coop = take((pl->coop_bytes + 3) / 4, 64);   // exchange slabs + flags of the cooperative recurrence (video encoder)
-    pl->o_coop2 = take((pl->coop_bytes + 3) / 4, 64);  // the text encoder's: the two recurrences share a launch when both fit on the chip
-    pl->o_splitk = take(kSplitKFloats, 64);      // partial sums of split-K launches (<= 64 output tiles x 16 pieces)
-    pl->o_tmpA = take((int64_t)std::max(pl->maxI, 1) * T * H, 64);
-    pl->o_tmpB = take((int64_t)std::max(pl->maxI, 1) * T * H, 64);
-    pl->o_kbuf = take((int64_t)std::max(pl->maxK, 1) * H, 64);
-    pl->o_cat = take((int64_t)pl->maxV * 3 * H, 64);
-    pl->o_hid = take((int64_t)pl->maxV * 2 * H, 64);
-    pl->o_rs = take((int64_t)std::max(pl->maxI, 1) * T, 64);
-    pl->o_sup = take((int64_t)std::max(pl->maxSupRows, 1) * T, 64);
-    pl->o_extra = take(std::max(pl->maxI, 1), 64);
-    pl->o_logits = take((int64_t)n * A, 64);
-    pl->o_wfrag = (H == 512 && T <= 64) ? take((int64_t)WV_END * H * H, 64) : 0;     // bf16 hi/lo fragment-order planes of the fused tile operators' weights
-    pl->o_status = take(128, 64);                // word 0: sticky "a cooperative hand-off timed out" flag of this plan's passes; words 16, 17
+    pl->o_coop = pl->take("coop", (pl->coop_bytes + 3) / 4, 64);   // exchange slabs + flags of the cooperative recurrence (video encoder)
+    pl->o_coop2 = pl->take("coop2", (pl->coop_bytes + 3) / 4, 64); // the text encoder's: the two recurrences share a launch when both fit on the chip
+    pl->o_splitk = pl->take("splitk", kSplitKFloats, 64);      // partial sums of split-K launches (<= 64 output tiles x 16 pieces)
+    pl->o_tmpA = pl->take("tmpA", (int64_t)std::max(pl->maxI, 1) * T * H, 64);
+    pl->o_tmpB = pl->take("tmpB", (int64_t)std::max(pl->maxI, 1) * T * H, 64);
+    pl->o_kbuf = pl->take("kbuf", (int64_t)std::max(pl->maxK, 1) * H, 64);
+    pl->o_cat = pl->take("cat", (int64_t)pl->maxV * 3 * H, 64);
+    pl->o_hid = pl->take("hid", (int64_t)pl->maxV * 2 * H, 64);
+    pl->o_rs = pl->take("rs", (int64_t)std::max(pl->maxI, 1) * T, 64);
+    pl->o_sup = pl->take("sup", (int64_t)std::max(pl->maxSupRows, 1) * T, 64);
+    pl->o_extra = pl->take("extra", std::max(pl->maxI, 1), 64);
+    pl->o_logits = pl->take("logits", (int64_t)n * A, 64);
+    pl->o_wfrag = (H == 512 && T <= 64) ? pl->take("wfrag", (int64_t)WV_END * H * H, 64) : 0;     // bf16 hi/lo fragment-order planes of the fused tile operators' weights
+    pl->o_status = pl->take("status", 128, 64);  // word 0: sticky "a cooperative hand-off timed out" flag of this plan's passes; words 16, 17
                                                  // and 18, 19: the self-resetting work queues of the fused forward / backward tile launches
-    for (Bucket &b : pl->buckets) {
+    for (int bi = 0; bi < nb; ++bi) {
+        Bucket &b = pl->buckets[bi];
         b.svA = pl->o_tmpA; b.svB = pl->o_tmpB; b.svK = pl->o_kbuf; b.svCat = pl->o_cat; b.svHid = pl->o_hid;
         b.svRs = pl->o_rs; b.svSup = pl->o_sup; b.svExtra = pl->o_extra;
         if (!pl->train) {
             // inference: the tile operators of one level run in ONE launch (fused path), so what a bucket's tile operator
             // writes for its own later launches must not be shared with the level's other buckets
             if (pl->o_wfrag > 0 && b.cnt > 0) {
-                if (b.op == STAIR_OP_FILTER) b.svCat = take((int64_t)b.cnt * H, 64);
-                if (b.op == STAIR_OP_SUPERLATIVE) b.svB = take((int64_t)b.cnt * T * H, 64);
+                if (b.op == STAIR_OP_FILTER) b.svCat = pl->take(".svCat", (int64_t)b.cnt * H, 64, bi);
+                if (b.op == STAIR_OP_SUPERLATIVE) b.svB = pl->take(".svB", (int64_t)b.cnt * T * H, 64, bi);
                 // the grouped vector-level launches: a two-layer module's hidden rows live from the level's first launch to its second
-                if (b.op == STAIR_OP_EXISTS || b.op == STAIR_OP_TOACTION) b.svHid = take((int64_t)b.cnt * H, 64);
+                if (b.op == STAIR_OP_EXISTS || b.op == STAIR_OP_TOACTION) b.svHid = pl->take(".svHid", (int64_t)b.cnt * H, 64, bi);
             }
             continue;
         }
@@ -1221,123 +1292,126 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
         switch (b.op) {
             // (svA of Filter / FilterFrame / Localize / Superlative lives in the per-weight region wg_sx, assigned below)
             case STAIR_OP_FILTER:            // (svCat, the pooled rows = the dense layer's input, lives in the per-weight region vd_x)
-                b.svB = take(c * T * H, 64); break;
+                b.svB = pl->take(".svB", c * T * H, 64, bi); break;
             case STAIR_OP_FILTERFRAME:
-                b.svB = take(c * T * H, 64); b.svRs = take(c * T, 64); b.svExtra = take(c, 64); break;
+                b.svB = pl->take(".svB", c * T * H, 64, bi); b.svRs = pl->take(".svRs", c * T, 64, bi); b.svExtra = pl->take(".svExtra", c, 64, bi); break;
             case STAIR_OP_HASITEM:
             case STAIR_OP_TEMPORAL:
-                b.svA = take(c * T * H, 64); break;
+                b.svA = pl->take(".svA", c * T * H, 64, bi); break;
             case STAIR_OP_LOCALIZE:
-                b.svB = take(c * T * H, 64); b.svK = take((int64_t)b.nrows * H, 64); break;
+                b.svB = pl->take(".svB", c * T * H, 64, bi); b.svK = pl->take(".svK", (int64_t)b.nrows * H, 64, bi); break;
             case STAIR_OP_SUPERLATIVE:
-                b.svB = take(c * T * H, 64); b.svK = take((int64_t)b.nrows * H, 64);
-                b.svSup = take((int64_t)b.nrows * T, 64); b.svCat = take(c * H, 64); break;
+                b.svB = pl->take(".svB", c * T * H, 64, bi); b.svK = pl->take(".svK", (int64_t)b.nrows * H, 64, bi);
+                b.svSup = pl->take(".svSup", (int64_t)b.nrows * T, 64, bi); b.svCat = pl->take(".svCat", c * H, 64, bi); break;
             default: break;                  // (the vector-level modules' packed inputs and hidden rows: per-weight regions vd_x)
         }
     }
     if (pl->train) {
         // per-weight regions: dZ blocks (and, for second-layer weights, the saved first activations) of all buckets of a weight
         // lie back to back in bucket order
+        std::vector<BucketLayers> layers(nb);
         int64_t rows0[WF_COUNT] = {}, rows3[WF_COUNT] = {};
-        for (const Bucket &b : pl->buckets) {
-            int w0, w3;
-            bucket_weights(b, w0, w3);
-            if (w0 >= 0) rows0[w0] += b.cnt;
-            if (w3 >= 0) rows3[w3] += b.cnt;
+        for (int bi = 0; bi < nb; ++bi) {
+            const BucketLayers u = layers[bi] = bucket_layers(pl->buckets[bi]);
+            if (u.w0 >= 0) rows0[u.w0] += pl->buckets[bi].cnt;
+            if (u.w3 >= 0) rows3[u.w3] += pl->buckets[bi].cnt;
+            if (u.v0 >= 0) pl->vd_rows[u.v0] += pl->buckets[bi].cnt;
+            if (u.v3 >= 0) pl->vd_rows[u.v3] += pl->buckets[bi].cnt;
         }
         for (int w = 0; w < WF_COUNT; ++w) {
             STAIR_CHECK(!(rows0[w] && rows3[w]), "internal: a weight is either a first or a second layer");
             pl->wg_rows[w] = rows0[w] + rows3[w];
-            if (pl->wg_rows[w]) pl->wg_dz[w] = take(pl->wg_rows[w] * T * H, 64);
-            if (rows3[w]) pl->wg_sx[w] = take(rows3[w] * T * H, 64);
+            if (pl->wg_rows[w]) pl->wg_dz[w] = pl->take("wg_dz", pl->wg_rows[w] * T * H, 64, w);
+            if (rows3[w]) pl->wg_sx[w] = pl->take(nullptr, rows3[w] * T * H, 64);       // (reported as the buckets' svA pieces)
             // slab partials of the weight's one long weight-gradient reduction (csrc/gemm_tn_x3tr.hip: stored, then added in fixed order)
             if (pl->wg_rows[w] && H % 256 == 0 && T % 32 == 0)
-                pl->wg_part[w] = take(tn_x3tr_scratch_floats(pl->wg_rows[w] * T, H, H), 64);
+                pl->wg_part[w] = pl->take("wg_part", tn_x3tr_scratch_floats(pl->wg_rows[w] * T, H, H), 64, w);
         }
         if (H % 256 == 0) {
             // scratch of the other slab-reduced products: a ring for the map-level layers outside the per-weight regions (two of the
             // largest in flight), and one piece per encoder weight (dW_ih on fp32 rows, dW_hh; two directions)
             const int64_t most_rows = std::max<int64_t>((int64_t)std::max(pl->maxI, 1) * T, 64);
             pl->tnring_floats = 2 * align_up(tn_x3tr_scratch_floats(most_rows & ~31ll, H, 3 * H), 64);
-            pl->o_tnring = take(pl->tnring_floats, 64);
+            pl->o_tnring = pl->take("tnring", pl->tnring_floats, 64);
             const int64_t rv = ((int64_t)pl->n_vid * T) & ~31ll, rq = (int64_t)pl->rows_q & ~31ll;
             const int E4 = ctx->cfg.text_size, V4 = ctx->cfg.video_size;
             pl->tnenc_floats[0] = 2 * (align_up(tn_x3tr_scratch_floats(std::max<int64_t>(rv, 64), 2 * H, H / 2), 64) +
                                        align_up(tn_x3tr_scratch_floats(std::max<int64_t>(rv, 64), 2 * H, V4), 64));
             pl->tnenc_floats[1] = 2 * (align_up(tn_x3tr_scratch_floats(std::max<int64_t>(rq, 64), 2 * H, H / 2), 64) +
                                        align_up(tn_x3tr_scratch_floats(std::max<int64_t>(rq, 64), 2 * H, E4), 64));
-            pl->o_tnenc[0] = take(pl->tnenc_floats[0], 64);
-            pl->o_tnenc[1] = take(pl->tnenc_floats[1], 64);
+            pl->o_tnenc[0] = pl->take("tnenc", pl->tnenc_floats[0], 64, 0);
+            pl->o_tnenc[1] = pl->take("tnenc", pl->tnenc_floats[1], 64, 1);
         }
         {   // vector-level weights: per-weight dZ and input regions, the buckets' rows back to back in bucket order
-            for (const Bucket &b : pl->buckets) {
-                int v0, v3;
-                bucket_vec_weights(b.op, v0, v3);
-                if (v0 >= 0) pl->vd_rows[v0] += b.cnt;
-                if (v3 >= 0) pl->vd_rows[v3] += b.cnt;
-            }
             for (int w = 0; w < VD_COUNT; ++w)
-                if (pl->vd_rows[w]) { pl->vd_dz[w] = take(pl->vd_rows[w] * H, 64); pl->vd_x[w] = take(pl->vd_rows[w] * vd_cols(w, H), 64); }
+                if (pl->vd_rows[w]) { pl->vd_dz[w] = pl->take(nullptr, pl->vd_rows[w] * H, 64); pl->vd_x[w] = pl->take(nullptr, pl->vd_rows[w] * vd_cols(w, H), 64); }
             int64_t vat[VD_COUNT] = {};
-            for (Bucket &b : pl->buckets) {
-                int v0, v3;
-                bucket_vec_weights(b.op, v0, v3);
-                if (v0 >= 0) { b.dzV0 = pl->vd_dz[v0] + vat[v0] * H; b.svCat = pl->vd_x[v0] + vat[v0] * vd_cols(v0, H); vat[v0] += b.cnt; }
-                if (v3 >= 0) { b.dzV3 = pl->vd_dz[v3] + vat[v3] * H; b.svHid = pl->vd_x[v3] + vat[v3] * H; vat[v3] += b.cnt; }
+            for (int bi = 0; bi < nb; ++bi) {
+                Bucket &b = pl->buckets[bi];
+                const int v0 = layers[bi].v0, v3 = layers[bi].v3;
+                if (v0 >= 0) {
+                    b.dzV0 = piece(".dzV0", bi, pl->vd_dz[v0] + vat[v0] * H, b.cnt * H);
+                    b.svCat = piece(".svCat", bi, pl->vd_x[v0] + vat[v0] * vd_cols(v0, H), (int64_t)b.cnt * vd_cols(v0, H));
+                    vat[v0] += b.cnt;
+                }
+                if (v3 >= 0) {
+                    b.dzV3 = piece(".dzV3", bi, pl->vd_dz[v3] + vat[v3] * H, b.cnt * H);
+                    b.svHid = piece(".svHid", bi, pl->vd_x[v3] + vat[v3] * H, b.cnt * H);
+                    vat[v3] += b.cnt;
+                }
             }
         }
         int64_t at[WF_COUNT] = {};
-        for (Bucket &b : pl->buckets) {
-            int w0, w3;
-            bucket_weights(b, w0, w3);
+        for (int bi = 0; bi < nb; ++bi) {
+            Bucket &b = pl->buckets[bi];
+            const int w0 = layers[bi].w0, w3 = layers[bi].w3;
             if (pl->o_wfrag > 0 && b.cnt > 0) {          // the level's backward chains share a launch: no scratch in common
-                if (b.op == STAIR_OP_FILTER) b.gRow = take((int64_t)b.cnt * H, 64);
-                if (b.op == STAIR_OP_FILTERFRAME && b.variant != 0) b.dzC = take((int64_t)b.cnt * T * H, 64);
+                if (b.op == STAIR_OP_FILTER) b.gRow = pl->take("gRow", (int64_t)b.cnt * H, 64);
+                if (b.op == STAIR_OP_FILTERFRAME && b.variant != 0) b.dzC = pl->take("dzC", (int64_t)b.cnt * T * H, 64);
                 const int64_t words = (int64_t)b.cnt * 512 * 2;          // 64-bit words, counted in floats
                 switch (b.op) {
-                    case STAIR_OP_FILTER: b.bitA = take(words, 64); b.bitB = take(words, 64); break;
-                    case STAIR_OP_FILTERFRAME: b.bitA = take(words, 64); b.bitB = take(words, 64); b.bitC = take(words, 64); break;
-                    case STAIR_OP_HASITEM: case STAIR_OP_LOCALIZE: case STAIR_OP_SUPERLATIVE: b.bitA = take(words, 64); break;
+                    case STAIR_OP_FILTER: b.bitA = pl->take(".bitA", words, 64, bi); b.bitB = pl->take(".bitB", words, 64, bi); break;
+                    case STAIR_OP_FILTERFRAME:
+                        b.bitA = pl->take(".bitA", words, 64, bi); b.bitB = pl->take(".bitB", words, 64, bi); b.bitC = pl->take(".bitC", words, 64, bi); break;
+                    case STAIR_OP_HASITEM: case STAIR_OP_LOCALIZE: case STAIR_OP_SUPERLATIVE: b.bitA = pl->take(".bitA", words, 64, bi); break;
                     default: break;
                 }
             }
             if (w0 >= 0) { b.dzA = pl->wg_dz[w0] + at[w0] * T * H; at[w0] += b.cnt; }
-            if (w3 >= 0) { b.dzB = pl->wg_dz[w3] + at[w3] * T * H; b.svA = pl->wg_sx[w3] + at[w3] * T * H; at[w3] += b.cnt; }
+            if (w3 >= 0) { b.dzB = pl->wg_dz[w3] + at[w3] * T * H; b.svA = piece(".svA", bi, pl->wg_sx[w3] + at[w3] * T * H, (int64_t)b.cnt * T * H); at[w3] += b.cnt; }
         }
         const int64_t I = std::max(pl->maxI, 1), Vv = pl->maxV;
-        pl->o_cv = take((int64_t)pl->n_vid * T * H, 64);
-        pl->o_ct = take((int64_t)pl->rows_q * H, 64);
-        pl->o_hprev = take(((int64_t)pl->n_vid * T + pl->rows_q) * H, 64);        // video rows, then text rows: the two backward passes may run side by side
-        pl->o_wt = take(ctx_weight_floats(ctx), 64);
-        pl->o_gA = take(I * T * H, 64);
-        pl->o_gB = take(I * T * H, 64);
-        if (pl->o_wfrag > 0) pl->o_wfragT = take((int64_t)WV_END * H * H, 64);     // backward chains of the fused tile operators and the grouped
-                                                                                   // vector-level launches: planes of the transposed weights
-        pl->o_gV0 = take(Vv * 2 * H, 64);
-        pl->o_gV1 = take(Vv * 2 * H, 64);
-        pl->o_gCat = take(Vv * 3 * H, 64);
-        pl->o_gStats = take(I * T * 2, 64);
-        pl->o_gRs2 = take(I * T, 64);
-        pl->o_dlogits = take((int64_t)n * A, 64);
-        pl->o_loss = take(n, 64);
+        pl->o_cv = pl->take("cv", (int64_t)pl->n_vid * T * H, 64);
+        pl->o_ct = pl->take("ct", (int64_t)pl->rows_q * H, 64);
+        pl->o_hprev = pl->take("hprev", ((int64_t)pl->n_vid * T + pl->rows_q) * H, 64);        // video rows, then text rows: the two backward passes may run side by side
+        pl->o_wt = pl->take("wt", ctx_weight_floats(ctx), 64);
+        pl->o_gA = pl->take("gA", I * T * H, 64);
+        pl->o_gB = pl->take("gB", I * T * H, 64);
+        if (pl->o_wfrag > 0) pl->o_wfragT = pl->take("wfragT", (int64_t)WV_END * H * H, 64);   // backward chains of the fused tile operators and the grouped
+                                                                                               // vector-level launches: planes of the transposed weights
+        pl->o_gV0 = pl->take("gV0", Vv * 2 * H, 64);
+        pl->o_gV1 = pl->take("gV1", Vv * 2 * H, 64);
+        pl->o_gCat = pl->take("gCat", Vv * 3 * H, 64);
+        pl->o_gStats = pl->take("gStats", I * T * 2, 64);
+        pl->o_gRs2 = pl->take("gRs2", I * T, 64);
+        pl->o_dlogits = pl->take("dlogits", (int64_t)n * A, 64);
+        pl->o_loss = pl->take("loss", n, 64);
         // everything from here to o_zero_end is cleared at the start of every backward pass
-        pl->o_zero_beg = align_up(o, 64);
-        o = pl->o_zero_beg;
+        pl->o_zero_beg = pl->total = align_up(pl->total, 64);
         // mirrors [vec arena .. map arena]; behind it the staging tiles and rows of the deterministic fan-in (build_grad_fanin)
-        pl->o_gblock = take(pl->o_map + (int64_t)(pl->n_map + pl->n_map_stage) * T * H - pl->o_vec + (int64_t)pl->n_vec_stage * H, H);
-        pl->o_gatt = take((int64_t)std::max(pl->n_att + pl->n_att_stage, 1) * T, 64);
-        pl->o_gtok = take((int64_t)pl->rows_q * H, 64);
-        pl->o_gqfeat = take((int64_t)n * H, 64);
-        pl->o_zero_end = align_up(o, 64);
-        o = pl->o_zero_end;
+        pl->o_gblock = pl->take("gblock", pl->o_map + (int64_t)(pl->n_map + pl->n_map_stage) * T * H - pl->o_vec + (int64_t)pl->n_vec_stage * H, H);
+        pl->o_gatt = pl->take("gatt", (int64_t)std::max(pl->n_att + pl->n_att_stage, 1) * T, 64);
+        pl->o_gtok = pl->take("gtok", (int64_t)pl->rows_q * H, 64);
+        pl->o_gqfeat = pl->take("gqfeat", (int64_t)n * H, 64);
+        pl->o_zero_end = pl->total = align_up(pl->total, 64);
         pl->o_gshadow = 1;            // (training plans use the context's fixed-point gradient shadows, stair_ctx::gshadow)
         // scratch that individual buckets clear themselves before accumulating into it
-        pl->o_gK = take((int64_t)std::max(pl->maxK, 1) * H, 64);
-        pl->o_gS = take((int64_t)std::max(pl->maxSupRows, 1) * T, 64);
-        pl->o_gRs = take(I * T, 64);
-        pl->o_gExtra = take(I, 64);
+        pl->o_gK = pl->take("gK", (int64_t)std::max(pl->maxK, 1) * H, 64);
+        pl->o_gS = pl->take("gS", (int64_t)std::max(pl->maxSupRows, 1) * T, 64);
+        pl->o_gRs = pl->take("gRs", I * T, 64);
+        pl->o_gExtra = pl->take("gExtra", I, 64);
     }
-    pl->total = align_up(o, 64);
+    pl->total = align_up(pl->total, 64);
     if (pl->train) {
         // the marks hold for a pass that runs the fused chains (their transposed planes are laid out), whose every marked writer IS a chain
         // (Temporal's needs its dZ region) and whose indices leave the bit free
@@ -1346,12 +1420,67 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
             if (b.op == STAIR_OP_TEMPORAL && b.cnt > 0 && b.dzA < 0) ok = false;
         pl->store_first_ok = ok;
     }
-    if (debug && pl->train) {
+    if (plan_debug() && pl->train) {
         fprintf(stderr, "weight-gradient regions (instances of T rows):");
         for (int w = 0; w < WF_COUNT; ++w) fprintf(stderr, " %ld", (long)pl->wg_rows[w]);
         fprintf(stderr, "\n");
     }
-    if (debug)
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int stair_plan_build(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
+                                const int32_t *span_lo, const int32_t *span_hi, const int32_t *q_off, int32_t T,
+                                int32_t flags, stair_plan **out) {
+    return stair_plan_build_shared(ctx, n, prog_off, tokens, span_lo, span_hi, q_off, n, nullptr, T, flags, out);
+}
+
+extern "C" int stair_plan_build_shared(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
+                                       const int32_t *span_lo, const int32_t *span_hi, const int32_t *q_off,
+                                       int32_t n_videos, const int32_t *video_of_question, int32_t T,
+                                       int32_t flags, stair_plan **out) {
+    return stair_plan_build_ragged(ctx, n, prog_off, tokens, span_lo, span_hi, q_off, n_videos, video_of_question, nullptr, T, flags, out);
+}
+
+extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
+                                       const int32_t *span_lo, const int32_t *span_hi, const int32_t *q_off,
+                                       int32_t n_videos, const int32_t *video_of_question, const int32_t *video_len, int32_t T,
+                                       int32_t flags, stair_plan **out) {
+    STAIR_CHECK(ctx && prog_off && tokens && span_lo && span_hi && q_off && out, "null argument");
+    STAIR_CHECK(n > 0 && T > 0, "n and T must be positive");
+    STAIR_CHECK(n_videos > 0 && (video_of_question || n_videos == n), "video_of_question is required when n_videos != n");
+    if (video_of_question)
+        for (int q = 0; q < n; ++q)
+            STAIR_CHECK(video_of_question[q] >= 0 && video_of_question[q] < n_videos,
+                        "video_of_question[" + std::to_string(q) + "] out of range");
+    STAIR_CHECK(ctx->conv || T == ctx->cfg.max_video_length,
+                "Linear(T,T) Temporal nets need T == max_video_length (modules.py:266-277)");
+    auto plp = std::make_unique<stair_plan>();
+    stair_plan *pl = plp.get();
+    pl->cfg = ctx->cfg;
+    pl->n = n;
+    pl->T = T;
+    pl->train = (flags & STAIR_PLAN_TRAIN) != 0;
+    pl->ext_proj = (flags & STAIR_PLAN_EXT_PROJECTION) != 0;
+    const int ntok = prog_off[n];
+    pl->nodes.assign(ntok, Node());
+    pl->roots.assign(n, -1);
+    pl->n_vid = n_videos;
+    pl->n_map = n_videos;   // map slot v = encoded video v
+    pl->vlen.assign(n_videos, T);
+    if (video_len)
+        for (int v = 0; v < n_videos; ++v) {
+            STAIR_CHECK(video_len[v] >= 1 && video_len[v] <= T, "video_len[" + std::to_string(v) + "] must be in 1..T");
+            pl->vlen[v] = video_len[v];
+            if (video_len[v] != T) pl->ragged = true;
+        }
+    STAIR_CHECK(!pl->ragged || ctx->conv, "clips of different lengths need the Conv1d Temporal nets (Linear(T,T) fixes T, modules.py:266-277)");
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (int rc = interpret_programs(pl, prog_off, tokens, span_lo, span_hi, q_off, video_of_question, !(flags & STAIR_PLAN_NO_CSE))) return rc;
+    if (int rc = build_index_image(pl, q_off)) return rc;
+    if (int rc = layout_workspace(pl, ctx)) return rc;
+    if (plan_debug())
         fprintf(stderr, "plan build total %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
     *out = plp.release();
     return 0;
@@ -1469,18 +1598,6 @@ extern "C" int stair_plan_nodes(const stair_plan *pl, int32_t *kind, int32_t *sl
 // =============================================================================================
 namespace {
 
-struct Lin { const float *w = nullptr, *b = nullptr; float *dw = nullptr, *db = nullptr; int id = -1; };
-struct Weights {
-    Lin compare, equals, exists0, exists3, f0[4], f3[4], fdense, ff0[3], ff3[3], ffatt, ffdense, hi0, hi3, lv0, lv3,
-        lk, supdense, tdense, ta0, ta3, xorl, dec0, dec3;
-    const float *beta = nullptr, *ln_w = nullptr, *ln_b = nullptr;
-    float *dbeta = nullptr, *dln_w = nullptr, *dln_b = nullptr;
-    const float *relate[3][6] = {};
-    float *drelate[3][6] = {};
-    const float *enc[2][8] = {};   // [video|text][w_ih, w_hh, b_ih, b_hh, then reverse]
-    float *denc[2][8] = {};
-};
-
 int resolve(const stair_ctx *ctx, Weights &W, bool grads) {
     const std::string p = "submodules.";
     auto get = [&](const std::string &name, const float *&dst, float **gdst) {
@@ -1503,30 +1620,10 @@ int resolve(const stair_ctx *ctx, Weights &W, bool grads) {
         return get(prefix + ".weight", l.w, &l.dw) || get(prefix + ".bias", l.b, &l.db);
     };
 #define R(x) if (x) return 1
-    R(lin(p + "Compare.param.0", W.compare));
-    R(lin(p + "Equals.param.0", W.equals));
-    R(lin(p + "Exists.param.0", W.exists0));
-    R(lin(p + "Exists.param.3", W.exists3));
-    const char *fk[4] = {"representation", "actions", "objects", "relations"};
-    for (int i = 0; i < 4; ++i) {
-        R(lin(p + "Filter.param." + fk[i] + ".0", W.f0[i]));
-        R(lin(p + "Filter.param." + fk[i] + ".3", W.f3[i]));
-    }
-    R(lin(p + "Filter.dense.0", W.fdense));
-    const char *ffk[3] = {"representation", "relations", "actions"};
-    for (int i = 0; i < 3; ++i) {
-        R(lin(p + "FilterFrame.param." + ffk[i] + ".0", W.ff0[i]));
-        R(lin(p + "FilterFrame.param." + ffk[i] + ".3", W.ff3[i]));
-    }
+    for (const WeightRow &r : kWeightRows) R(lin(p + r.prefix, r.lin(W)));
     R(lin(p + "FilterFrame.attention.0", W.ffatt));
-    R(lin(p + "FilterFrame.dense.0", W.ffdense));
-    R(lin(p + "HasItem.param.0", W.hi0));
     R(lin(p + "HasItem.param.3", W.hi3));
-    R(lin(p + "Localize.video_linear.0", W.lv0));
-    R(lin(p + "Localize.video_linear.3", W.lv3));
-    R(lin(p + "Localize.keyword_linear.0", W.lk));
     R(get(p + "Relate.beta", W.beta, &W.dbeta));
-    R(lin(p + "Superlative.dense.0", W.supdense));
     const char *modes[3] = {"before", "after", "between"};
     for (int m = 0; m < 3; ++m)
         for (int l = 0; l < 3; ++l) {
@@ -1534,12 +1631,8 @@ int resolve(const stair_ctx *ctx, Weights &W, bool grads) {
             R(get(pre + ".weight", W.relate[m][2 * l], &W.drelate[m][2 * l]));
             R(get(pre + ".bias", W.relate[m][2 * l + 1], &W.drelate[m][2 * l + 1]));
         }
-    R(lin(p + "Temporal.dense.0", W.tdense));
     R(get(p + "Temporal.layer_norm.weight", W.ln_w, &W.dln_w));
     R(get(p + "Temporal.layer_norm.bias", W.ln_b, &W.dln_b));
-    R(lin(p + "ToAction.param.0", W.ta0));
-    R(lin(p + "ToAction.param.3", W.ta3));
-    R(lin(p + "Xor.param.0", W.xorl));
     for (int e = 0; e < 2; ++e) {
         const std::string enc = p + (e == 0 ? "video_encoder" : "text_encoder");
         const char *sfx[2] = {"", "_reverse"};
@@ -1550,8 +1643,6 @@ int resolve(const stair_ctx *ctx, Weights &W, bool grads) {
             R(get(enc + ".bias_hh_l0" + sfx[d], W.enc[e][4 * d + 3], &W.denc[e][4 * d + 3]));
         }
     }
-    R(lin(p + "decoder.0", W.dec0));
-    R(lin(p + "decoder.3", W.dec3));
 #undef R
     return 0;
 }
@@ -1592,10 +1683,35 @@ VgProblem vg_fwd(int rows, const float *a, const int32_t *ia, int64_t lda, const
 // buckets)
 bool vec_group_on() { return policy_or(STAIR_OPT_VEC_GROUP, 1) != 0; }
 
-struct Ptrs {     // workspace views shared by forward and backward
-    float *ws, *vec, *map, *att, *tok, *qfeat;
-    int32_t *didx;
-};
+// ---- the argument blocks of encoder e (0: video, 1: text), filled in one place for stair_encoders_project, the forward run and the
+// backward pass.  The input rows and the geometry (x: fp32 rows, or bf16 ones when `bf16`) ...
+template <class Args> void enc_input(Args &a, const stair_config &g, int e, const void *x, bool bf16, int rows, int n, int max_len) {
+    a.I = e == 0 ? g.video_size : g.text_size; a.ldx = a.I; a.Hh = g.hidden_size / 2;
+    a.rows = rows; a.n = n; a.max_len = max_len;
+    if (bf16) a.x_bf16 = x; else a.x = static_cast<const float *>(x);
+}
+// ... what the input projection reads and writes: W_ih, the biases and the regions of L behind `pb` (a plan's workspace or the caller's buffer) ...
+void enc_projection(stair_lstm_args &a, const stair_config &g, const Weights &W, int e, float *pb, const ProjLayout &L) {
+    for (int d = 0; d < 2; ++d) { a.w_ih[d] = W.enc[e][4 * d]; a.b_ih[d] = W.enc[e][4 * d + 2]; a.b_hh[d] = W.enc[e][4 * d + 3]; }
+    if (e == 0) {
+        if (a.x_bf16) a.wih_planes_ws = pb + L.wplanes;
+        a.xproj_ws = pb + L.xpv; a.bias_ws = pb + L.bias;
+    } else {
+        a.wih_planes_ws = pb + L.wplanes_t; a.x_planes_ws = pb + L.xplanes_t;
+        a.xproj_ws = pb + L.xpt; a.bias_ws = pb + L.bias + 4 * g.hidden_size;
+    }
+}
+// ... and what a plan's recurrence and its reverse pass share: sequence index, W_hh and its packed image, cooperative workspace, status word
+template <class Args> void enc_recurrence(Args &a, const stair_plan *pl, const Weights &W, int e, float *ws, const int32_t *didx) {
+    const int64_t H = pl->cfg.hidden_size;
+    a.seq_off = didx + (e == 0 ? pl->off_seqv : pl->off_seqt);
+    if (e == 0 && pl->ragged) a.seq_len = didx + pl->off_lenv;
+    for (int d = 0; d < 2; ++d) a.w_hh[d] = W.enc[e][4 * d + 1];
+    a.whh_pack_ws = ws + pl->o_wpack + (e == 0 ? 0 : 2 * H * H);
+    a.coop_ws = ws + (e == 0 ? pl->o_coop : pl->o_coop2); a.coop_ws_bytes = pl->coop_bytes;
+    a.status = reinterpret_cast<uint32_t *>(ws + pl->o_status);
+    a.ldo = H;
+}
 
 }  // namespace
 
@@ -1660,21 +1776,12 @@ extern "C" int stair_encoders_project(stair_ctx *ctx, const void *video, int32_t
     hipStream_t s = static_cast<hipStream_t>(stream);
     Weights W;
     if (resolve(ctx, W, false)) return 1;
-    const int H = g.hidden_size, Hh = H / 2, V = g.video_size, E = g.text_size;
+    STAIR_CHECK(!video_is_bf16 || g.video_size % 32 == 0, "bf16 clip features need video_size % 32 == 0");
     stair_lstm_args a = {}, t = {};
-    a.x = static_cast<const float *>(video); a.ldx = V; a.rows = n_videos * T; a.n = n_videos; a.max_len = T; a.I = V; a.Hh = Hh;
-    if (video_is_bf16) {
-        STAIR_CHECK(V % 32 == 0, "bf16 clip features need video_size % 32 == 0");
-        a.x = nullptr; a.x_bf16 = video; a.wih_planes_ws = buf + L.wplanes;
-    }
-    for (int d = 0; d < 2; ++d) {
-        a.w_ih[d] = W.enc[0][4 * d]; a.b_ih[d] = W.enc[0][4 * d + 2]; a.b_hh[d] = W.enc[0][4 * d + 3];
-        t.w_ih[d] = W.enc[1][4 * d]; t.b_ih[d] = W.enc[1][4 * d + 2]; t.b_hh[d] = W.enc[1][4 * d + 3];
-    }
-    a.xproj_ws = buf + L.xpv; a.bias_ws = buf + L.bias;
-    t.x = question; t.ldx = E; t.rows = (int32_t)question_rows; t.n = 1; t.max_len = (int32_t)question_rows; t.I = E; t.Hh = Hh;
-    t.wih_planes_ws = buf + L.wplanes_t; t.x_planes_ws = buf + L.xplanes_t;
-    t.xproj_ws = buf + L.xpt; t.bias_ws = buf + L.bias + 4 * H;
+    enc_input(a, g, 0, video, video_is_bf16 != 0, n_videos * T, n_videos, T);
+    enc_input(t, g, 1, question, false, (int32_t)question_rows, 1, (int32_t)question_rows);     // (no plan: ONE sequence of all token rows; a run
+    enc_projection(a, g, W, 0, buf, L);                                                           // has n of at most max_q rows)
+    enc_projection(t, g, W, 1, buf, L);
     if (int rc = launch_lstm_project(a, s)) return rc;
     return launch_lstm_project(t, s);
 }
@@ -1709,7 +1816,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
     if (resolve(ctx, W, false)) return 1;
 
     const stair_config &g = ctx->cfg;
-    const int H = g.hidden_size, Hh = H / 2, V = g.video_size, E = g.text_size, A = g.answer_vocab_length;
+    const int H = g.hidden_size, V = g.video_size, A = g.answer_vocab_length;
     const int n = pl->n, T = pl->T;
     const int64_t TH = (int64_t)T * H;
     float *ws = static_cast<float *>(workspace);
@@ -1748,34 +1855,15 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
         // says they already hold this batch's projections (stair_encoders_project, enqueued before the plan was built)
         STAIR_CHECK(!pl->ext_proj || pl->proj, "plan built with STAIR_PLAN_EXT_PROJECTION: call stair_plan_set_projection first");
         STAIR_CHECK(!(flags & STAIR_RUN_PROJECTED) || pl->ext_proj, "STAIR_RUN_PROJECTED needs a STAIR_PLAN_EXT_PROJECTION plan");
-        float *pb = pl->ext_proj ? pl->proj : ws;
-        a.x = video; a.ldx = V; a.rows = pl->n_vid * T; a.n = pl->n_vid; a.max_len = T; a.I = V; a.Hh = Hh;
-        if (flags & STAIR_RUN_VIDEO_BF16) {
-            STAIR_CHECK(V % 32 == 0, "bf16 clip features need video_size % 32 == 0");
-            a.x = nullptr; a.x_bf16 = video; a.wih_planes_ws = pb + pl->o_wplanes;
+        STAIR_CHECK(!(flags & STAIR_RUN_VIDEO_BF16) || V % 32 == 0, "bf16 clip features need video_size % 32 == 0");
+        enc_input(a, g, 0, video, (flags & STAIR_RUN_VIDEO_BF16) != 0, pl->n_vid * T, pl->n_vid, T);
+        enc_input(t, g, 1, question, false, pl->rows_q, n, pl->max_q);
+        for (int e = 0; e < 2; ++e) {
+            enc_projection(e == 0 ? a : t, g, W, e, pl->proj_base(ws), pl->pj);
+            enc_recurrence(e == 0 ? a : t, pl, W, e, ws, didx);
         }
-        a.seq_off = didx + pl->off_seqv;
-        if (pl->ragged) a.seq_len = didx + pl->off_lenv;
-        for (int d = 0; d < 2; ++d) {
-            a.w_ih[d] = W.enc[0][4 * d]; a.w_hh[d] = W.enc[0][4 * d + 1];
-            a.b_ih[d] = W.enc[0][4 * d + 2]; a.b_hh[d] = W.enc[0][4 * d + 3];
-        }
-        a.xproj_ws = pb + pl->o_xpv; a.bias_ws = pb + pl->o_bias; a.whh_pack_ws = ws + pl->o_wpack;
-        a.out = map; a.ldo = H; a.h_n = ws + pl->o_vhn;
-        a.coop_ws = ws + pl->o_coop; a.coop_ws_bytes = pl->coop_bytes; a.status = status;
-        a.cbuf = pl->train ? ws + pl->o_cv : nullptr;
-
-        t.x = question; t.ldx = E; t.rows = pl->rows_q; t.n = n; t.max_len = pl->max_q; t.I = E; t.Hh = Hh;
-        t.seq_off = didx + pl->off_seqt;
-        for (int d = 0; d < 2; ++d) {
-            t.w_ih[d] = W.enc[1][4 * d]; t.w_hh[d] = W.enc[1][4 * d + 1];
-            t.b_ih[d] = W.enc[1][4 * d + 2]; t.b_hh[d] = W.enc[1][4 * d + 3];
-        }
-        t.wih_planes_ws = pb + pl->o_wplanes_t; t.x_planes_ws = pb + pl->o_xplanes_t;
-        t.xproj_ws = pb + pl->o_xpt; t.bias_ws = pb + pl->o_bias + 4 * H; t.whh_pack_ws = ws + pl->o_wpack + 2 * (int64_t)H * H;
-        t.out = tok; t.ldo = H; t.h_n = qfeat;
-        t.coop_ws = ws + pl->o_coop2; t.coop_ws_bytes = pl->coop_bytes; t.status = status;
-        t.cbuf = pl->train ? ws + pl->o_ct : nullptr;
+        a.out = map; a.h_n = ws + pl->o_vhn; a.cbuf = pl->train ? ws + pl->o_cv : nullptr;
+        t.out = tok; t.h_n = qfeat; t.cbuf = pl->train ? ws + pl->o_ct : nullptr;
 
         // both input projections, then the two recurrences -- in ONE launch while all their workgroups fit on the chip
         // (csrc/lstm_coop.hip, lstm_rec_coop_pair_kernel), else one after the other
@@ -1799,26 +1887,15 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
     const bool fused = pl->o_wfrag > 0 && tile_mlp_usable(H, T);
     pl->bits_written = fused && pl->train;
     auto WF = [&](int slot) { return static_cast<const void *>(ws + pl->o_wfrag + (int64_t)slot * H * H); };
+    const WeightIndex &WIX = weight_index();
     if (fused) {
-        const Lin *lin_of[WF_COUNT] = {&W.f0[0], &W.f0[1], &W.f0[2], &W.f0[3], &W.f3[0], &W.f3[1], &W.f3[2], &W.f3[3], &W.ff0[0], &W.ff0[1], &W.ff0[2],
-                                       &W.ff3[0], &W.ff3[1], &W.ff3[2], &W.ffdense, &W.hi0, &W.lv0, &W.lv3, &W.tdense};
-        bool need[WF_COUNT] = {};
-        for (const Bucket &b : pl->buckets) {
-            if (b.cnt == 0) continue;
-            switch (b.op) {
-                case STAIR_OP_FILTER: need[WF_F0 + b.variant] = need[WF_F3 + b.variant] = true; break;
-                case STAIR_OP_FILTERFRAME: need[WF_FF0 + b.variant] = need[WF_FF3 + b.variant] = need[WF_FFD] = true; break;
-                case STAIR_OP_HASITEM: need[WF_HI0] = true; break;
-                case STAIR_OP_LOCALIZE: case STAIR_OP_SUPERLATIVE: need[WF_LV0] = need[WF_LV3] = true; break;
-                case STAIR_OP_TEMPORAL: need[WF_TD] = true; break;
-                default: break;
-            }
-        }
+        bool need[WF_COUNT];
+        tile_weights_in_use(pl, need, [](const Bucket &) { return false; });
         const float *src[WF_COUNT];
         void *dst[WF_COUNT];
         int cnt_w = 0;
         for (int i = 0; i < WF_COUNT; ++i)
-            if (need[i]) { src[cnt_w] = lin_of[i]->w; dst[cnt_w] = const_cast<void *>(WF(i)); ++cnt_w; }
+            if (need[i]) { src[cnt_w] = WIX.wf[i]->lin(W).w; dst[cnt_w] = const_cast<void *>(WF(i)); ++cnt_w; }
         if (cnt_w) RUN(launch_pack_wfrag_many(src, dst, cnt_w, H, H, s));
     }
     // vector-level modules on the tile operator (64 instances per tile; STAIR_TILE_VEC=0: the pack -> GEMM -> reduction sequences)
@@ -1833,40 +1910,35 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
     const bool grouped = fused && vec_group_usable(H) && vec_group_on();
     std::vector<VgProblem> vg1, vg2;
     // [512 x 512] blocks of a row-wise weight as planes: slot + (output block) * nseg + (input segment); blocks of a [N, nseg * 512] matrix
-    struct VgW { int slot, nblk, nseg; const Lin *l; int op; };
-    const VgW vgw[10] = {{WV_CMP, 1, 2, &W.compare, STAIR_OP_COMPARE}, {WV_EQ, 1, 2, &W.equals, STAIR_OP_EQUALS}, {WV_XOR, 1, 3, &W.xorl, STAIR_OP_XOR},
-                         {WV_TA0, 1, 2, &W.ta0, STAIR_OP_TOACTION}, {WV_TA3, 1, 1, &W.ta3, STAIR_OP_TOACTION}, {WV_EX0, 1, 3, &W.exists0, STAIR_OP_EXISTS},
-                         {WV_EX3, 1, 1, &W.exists3, STAIR_OP_EXISTS}, {WV_FD, 1, 1, &W.fdense, STAIR_OP_FILTER}, {WV_LK, 1, 1, &W.lk, STAIR_OP_LOCALIZE},
-                         {WV_DEC0, 2, 2, &W.dec0, -1}};
+    // (packed for the module whose grouped launch reads them: WeightRow::op.  Superlative reads Localize's keyword layer through the GEMM)
     if (grouped) {
         bool has[32] = {};
         for (const Bucket &b : pl->buckets) if (b.cnt > 0 && b.op >= 0 && b.op < 32) has[b.op] = true;
         const float *src[32];
         void *dst[32];
         int ld[32], cnt_w = 0;
-        for (const VgW &v : vgw)
-            if (v.op < 0 || has[v.op])
-                for (int jb = 0; jb < v.nblk; ++jb)
-                    for (int sg = 0; sg < v.nseg; ++sg) {
-                        src[cnt_w] = v.l->w + ((int64_t)jb * H * v.nseg + sg) * H; dst[cnt_w] = const_cast<void *>(WF(v.slot + jb * v.nseg + sg));
-                        ld[cnt_w] = v.nseg * H; ++cnt_w;
-                    }
+        for (int slot = WF_COUNT; slot < WV_END; ++slot)
+            if (const WeightRow *v = WIX.wv[slot])
+                if (v->op < 0 || has[v->op])
+                    for (int jb = 0; jb < v->nblk; ++jb)
+                        for (int sg = 0; sg < v->nseg; ++sg) {
+                            src[cnt_w] = v->lin(W).w + ((int64_t)jb * H * v->nseg + sg) * H; dst[cnt_w] = const_cast<void *>(WF(slot + jb * v->nseg + sg));
+                            ld[cnt_w] = v->nseg * H; ++cnt_w;
+                        }
         if (cnt_w) RUN(launch_pack_wfrag_many(src, dst, cnt_w, H, H, s, false, ld));
     }
     auto fused_vec_for = [&](const Bucket &b) { return !grouped && fused && dp <= 0.0f && vec_min > 0 && b.cnt >= vec_min; };
     const bool fused_vec = !grouped && fused && dp <= 0.0f && vec_min > 0;
     if (fused_vec) {
-        struct { int slot, nseg; const Lin *l; int op; } vw[7] = {{WV_CMP, 2, &W.compare, STAIR_OP_COMPARE}, {WV_EQ, 2, &W.equals, STAIR_OP_EQUALS},
-            {WV_XOR, 3, &W.xorl, STAIR_OP_XOR}, {WV_TA0, 2, &W.ta0, STAIR_OP_TOACTION}, {WV_TA3, 1, &W.ta3, STAIR_OP_TOACTION},
-            {WV_EX0, 3, &W.exists0, STAIR_OP_EXISTS}, {WV_EX3, 1, &W.exists3, STAIR_OP_EXISTS}};
         bool has[32] = {};
         for (const Bucket &b : pl->buckets) if (fused_vec_for(b) && b.op >= 0 && b.op < 32) has[b.op] = true;
         const float *src[16];
         void *dst[16];
         int ld[16], cnt_w = 0;
-        for (const auto &v : vw)
-            if (has[v.op])
-                for (int j = 0; j < v.nseg; ++j) { src[cnt_w] = v.l->w + (int64_t)j * H; dst[cnt_w] = const_cast<void *>(WF(v.slot + j)); ld[cnt_w] = v.nseg * H; ++cnt_w; }
+        for (int slot = WF_COUNT; slot < WV_FD; ++slot)          // (the slots below WV_FD: the vector-level modules' own layers)
+            if (const WeightRow *v = WIX.wv[slot])
+                if (has[v->op])
+                    for (int j = 0; j < v->nseg; ++j) { src[cnt_w] = v->lin(W).w + (int64_t)j * H; dst[cnt_w] = const_cast<void *>(WF(slot + j)); ld[cnt_w] = v->nseg * H; ++cnt_w; }
         if (cnt_w) RUN(launch_pack_wfrag_many(src, dst, cnt_w, H, H, s, false, ld));
     }
     // a vector-level module as queued tile work: first layer over the never-materialised concatenation of the operand rows
@@ -2302,6 +2374,15 @@ struct BwdCtx {
     // takes the next piece; when the ring wraps, the pending sums are added first (tn_x3tr_flush)
     float *tn_ring = nullptr; int64_t tn_ring_floats = 0;
     mutable int64_t tn_ring_at = 0;
+    int ring_take(int64_t need, float **piece) const {
+        if (tn_ring_at + need > tn_ring_floats) {
+            if (int rc = tn_x3tr_flush(s)) return rc;
+            tn_ring_at = 0;
+        }
+        *piece = tn_ring + tn_ring_at;
+        tn_ring_at += need;
+        return 0;
+    }
 };
 
 // rows from which a per-bucket weight-gradient product takes the slab-reduced kernel (below it the atomic kernel's single pass is
@@ -2323,12 +2404,9 @@ int dense_bwd(const BwdCtx &B, const float *dZ, int groups, int R, int N, int K,
     if (!(l.id >= 0 && l.id < (int)B.deferred.size() && B.deferred[l.id])) {
         const int64_t need = M >= policy_or(STAIR_OPT_TN_SLAB_MIN_ROWS, g_tn_slab_min_rows) && B.tn_ring && tn_x3tr_takes(t) ? align_up(tn_x3tr_scratch_floats(M, N, K), 64) : 0;
         if (need && need <= B.tn_ring_floats) {
-            if (B.tn_ring_at + need > B.tn_ring_floats) {
-                if (int rc = tn_x3tr_flush(B.s)) return rc;
-                B.tn_ring_at = 0;
-            }
-            if (int rc = launch_gemm_tn_x3tr(t, B.tn_ring + B.tn_ring_at, B.s)) return rc;
-            B.tn_ring_at += need;
+            float *piece;
+            if (int rc = B.ring_take(need, &piece)) return rc;
+            if (int rc = launch_gemm_tn_x3tr(t, piece, B.s)) return rc;
         } else if (int rc = launch_gemm_tn(t, B.s)) return rc;
     }
     if (dX) {
@@ -2443,25 +2521,19 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     }
     // weight-gradient products of the tile-level layers run ONCE per weight, after all buckets (FilterFrame's dense layer keeps
     // its per-bucket product: its X operand carries the attention scale only in the tensor-keyword variant)
-    const Lin *lin_of[WF_COUNT] = {&W.f0[0], &W.f0[1], &W.f0[2], &W.f0[3], &W.f3[0], &W.f3[1], &W.f3[2], &W.f3[3], &W.ff0[0], &W.ff0[1], &W.ff0[2],
-                                   &W.ff3[0], &W.ff3[1], &W.ff3[2], &W.ffdense, &W.hi0, &W.lv0, &W.lv3, &W.tdense};
+    const WeightIndex &WIX = weight_index();
     B.deferred.assign(ctx->names.size(), 0);
     for (int w = 0; w < WF_COUNT; ++w)
-        if (w != WF_FFD) B.deferred[lin_of[w]->id] = 1;
-    const Lin *vlin_of[VD_COUNT] = {&W.compare, &W.equals, &W.xorl, &W.ta0, &W.ta3, &W.exists0, &W.exists3, &W.fdense};
-    for (int w = 0; w < VD_COUNT; ++w) B.deferred[vlin_of[w]->id] = 1;
+        if (w != WF_FFD) B.deferred[WIX.wf[w]->lin(W).id] = 1;
+    for (int w = 0; w < VD_COUNT; ++w) B.deferred[WIX.vd[w]->lin(W).id] = 1;
     {
         int64_t o = 0;
         for (size_t i = 0; i < ctx->names.size(); ++i) { B.wt_off[i] = o; o += align_up(ctx->numel[i], 64); }
-        const Lin *lins[] = {&W.compare, &W.equals, &W.exists0, &W.exists3, &W.f0[0], &W.f0[1], &W.f0[2], &W.f0[3], &W.f3[0],
-                             &W.f3[1], &W.f3[2], &W.f3[3], &W.fdense, &W.ff0[0], &W.ff0[1], &W.ff0[2], &W.ff3[0], &W.ff3[1],
-                             &W.ff3[2], &W.ffdense, &W.hi0, &W.lv0, &W.lv3, &W.lk, &W.supdense, &W.tdense, &W.ta0, &W.ta3,
-                             &W.xorl, &W.dec0, &W.dec3};
         TransposeBatch tb;
         tb.count = 0;
         int tiles = 0;
-        static_assert(sizeof(lins) / sizeof(lins[0]) <= 32, "TransposeBatch holds 32 matrices");
-        for (const Lin *l : lins) {
+        for (const WeightRow &r : kWeightRows) {            // (in table order)
+            const Lin *l = &r.lin(W);
             const int64_t rows = ctx->numel[l->id + 1];                 // bias length = out features
             const int64_t cols = ctx->numel[l->id] / rows;
             const int m = tb.count++;
@@ -2469,7 +2541,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
             tb.rows[m] = (int)rows; tb.cols[m] = (int)cols; tb.first_tile[m] = tiles;
             tiles += (int)(((rows + 31) / 32) * ((cols + 31) / 32));
         }
-        RUN(launch_transpose_many(tb, tiles, s));       // one launch for all 31 images
+        RUN(launch_transpose_many(tb, tiles, s));       // one launch for all images
     }
     // ---- backward chains of the fused tile operators (csrc/tile_mlp.hip): dX = (dZ2 W2 * relu'(Z1)) W1 stays on the tile ----
     const bool fused = pl->o_wfragT > 0 && tile_mlp_usable(H, T);
@@ -2479,29 +2551,24 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     const bool grouped = fused && vec_group_usable(H) && vec_group_on();
     std::vector<VgProblem> bvg1, bvg2;
     if (grouped) {      // planes of the transposed images (already there as fp32): block (j, s) of W^T = slot + j * nin + s
-        struct VgWT { int slot, nblk, nin; const Lin *l; int op; };        // W^T is [nblk * 512, nin * 512]
-        const VgWT vgw[10] = {{WV_CMP, 2, 1, &W.compare, STAIR_OP_COMPARE}, {WV_EQ, 2, 1, &W.equals, STAIR_OP_EQUALS}, {WV_XOR, 3, 1, &W.xorl, STAIR_OP_XOR},
-                              {WV_TA0, 2, 1, &W.ta0, STAIR_OP_TOACTION}, {WV_TA3, 1, 1, &W.ta3, STAIR_OP_TOACTION}, {WV_EX0, 3, 1, &W.exists0, STAIR_OP_EXISTS},
-                              {WV_EX3, 1, 1, &W.exists3, STAIR_OP_EXISTS}, {WV_FD, 1, 1, &W.fdense, STAIR_OP_FILTER}, {WV_LK, 1, 1, &W.lk, STAIR_OP_LOCALIZE},
-                              {WV_DEC0, 2, 2, &W.dec0, -1}};
-        bool has[32] = {};
+        bool has[32] = {};                          // (W^T is [nseg * 512, nblk * 512]: the forward blocks with the two counts exchanged)
         for (const Bucket &b : pl->buckets) if (b.cnt > 0 && b.op >= 0 && b.op < 32) has[b.op] = true;
         const float *src[32];
         void *dst[32];
         int ld[32], cnt_w = 0;
-        for (const VgWT &v : vgw)
-            if (v.op < 0 || has[v.op])
-                for (int jb = 0; jb < v.nblk; ++jb)
-                    for (int sg = 0; sg < v.nin; ++sg) {
-                        src[cnt_w] = B.wt + B.wt_off[v.l->id] + ((int64_t)jb * H * v.nin + sg) * H; dst[cnt_w] = const_cast<void *>(WFT(v.slot + jb * v.nin + sg));
-                        ld[cnt_w] = v.nin * H; ++cnt_w;
-                    }
+        for (int slot = WF_COUNT; slot < WV_END; ++slot)
+            if (const WeightRow *v = WIX.wv[slot])
+                if (v->op < 0 || has[v->op])
+                    for (int jb = 0; jb < v->nseg; ++jb)
+                        for (int sg = 0; sg < v->nblk; ++sg) {
+                            src[cnt_w] = B.wt + B.wt_off[v->lin(W).id] + ((int64_t)jb * H * v->nblk + sg) * H; dst[cnt_w] = const_cast<void *>(WFT(slot + jb * v->nblk + sg));
+                            ld[cnt_w] = v->nblk * H; ++cnt_w;
+                        }
         if (cnt_w) RUN(launch_pack_wfrag_many(src, dst, cnt_w, H, H, s, false, ld));
     }
-    auto vslot = [&](const Lin &l) {
-        const Lin *ls[10] = {&W.compare, &W.equals, &W.xorl, &W.ta0, &W.ta3, &W.exists0, &W.exists3, &W.fdense, &W.lk, &W.dec0};
-        const int slots[10] = {WV_CMP, WV_EQ, WV_XOR, WV_TA0, WV_TA3, WV_EX0, WV_EX3, WV_FD, WV_LK, WV_DEC0};
-        for (int i = 0; i < 10; ++i) if (ls[i]->id == l.id) return WFT(slots[i]);
+    auto vslot = [&](const Lin &l) {                // the transposed planes of a row-wise weight
+        for (const WeightRow &r : kWeightRows)
+            if (r.wv >= 0 && r.lin(W).id == l.id) return WFT(r.wv);
         return static_cast<const void *>(nullptr);
     };
     auto vg_adj = [&](int rows, const float *a, const int32_t *ia, const float *bmask, int pack, float in_scale, float *in_save, const Lin &l, int nseg,
@@ -2514,23 +2581,14 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         return q;
     };
     if (fused) {
-        bool need[WF_COUNT] = {};
-        for (const Bucket &b : pl->buckets) {
-            if (b.cnt == 0) continue;
-            switch (b.op) {
-                case STAIR_OP_FILTER: need[WF_F0 + b.variant] = need[WF_F3 + b.variant] = true; break;
-                case STAIR_OP_FILTERFRAME: if (b.variant) need[WF_FF0 + b.variant] = need[WF_FF3 + b.variant] = need[WF_FFD] = true; break;
-                case STAIR_OP_HASITEM: need[WF_HI0] = true; break;
-                case STAIR_OP_LOCALIZE: case STAIR_OP_SUPERLATIVE: need[WF_LV0] = need[WF_LV3] = true; break;
-                case STAIR_OP_TEMPORAL: need[WF_TD] = true; break;
-                default: break;
-            }
-        }
+        bool need[WF_COUNT];
+        // (FilterFrame variant 0 needs no transposed planes: its backward is not a chain)
+        tile_weights_in_use(pl, need, [](const Bucket &b) { return b.op == STAIR_OP_FILTERFRAME && b.variant == 0; });
         const float *src[WF_COUNT];
         void *dst[WF_COUNT];
         int cnt_w = 0;
         for (int i = 0; i < WF_COUNT; ++i)          // the transposed fp32 images are there already: their planes are those of W^T
-            if (need[i]) { src[cnt_w] = B.wt + B.wt_off[lin_of[i]->id]; dst[cnt_w] = const_cast<void *>(WFT(i)); ++cnt_w; }
+            if (need[i]) { src[cnt_w] = B.wt + B.wt_off[WIX.wf[i]->lin(W).id]; dst[cnt_w] = const_cast<void *>(WFT(i)); ++cnt_w; }
         if (cnt_w) RUN(launch_pack_wfrag_many(src, dst, cnt_w, H, H, s));
     }
 
@@ -2862,7 +2920,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     // questions -- the two streams contend for the same LDS / L2 / HBM paths.
     for (int w = 0; w < WF_COUNT; ++w) {
         if (w == WF_FFD || pl->wg_rows[w] == 0) continue;
-        const Lin &l = *lin_of[w];
+        const Lin &l = WIX.wf[w]->lin(W);
         stair_gemm_tn_args t = {};
         t.A = ws + pl->wg_dz[w]; t.lda = H;
         t.C = l.dw; t.ldc = H; t.colsum = l.db;
@@ -2883,7 +2941,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     std::vector<stair_gemm_tn_args> small_tn;
     for (int w = 0; w < VD_COUNT; ++w) {
         if (pl->vd_rows[w] == 0) continue;
-        const Lin &l = *vlin_of[w];
+        const Lin &l = WIX.vd[w]->lin(W);
         const int Kw = vd_cols(w, H);
         stair_gemm_tn_args t = {};
         t.A = ws + pl->vd_dz[w]; t.lda = H;
@@ -2894,9 +2952,9 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         h.M = t.M & ~31;
         const int64_t need = h.M >= 2048 && B.tn_ring && tn_x3tr_takes(h) ? align_up(tn_x3tr_scratch_floats(h.M, H, Kw), 64) : 0;
         if (need && need <= B.tn_ring_floats) {
-            if (B.tn_ring_at + need > B.tn_ring_floats) { RUN(tn_x3tr_flush(s)); B.tn_ring_at = 0; }
-            RUN(launch_gemm_tn_x3tr(h, B.tn_ring + B.tn_ring_at, s));
-            B.tn_ring_at += need;
+            float *piece;
+            RUN(B.ring_take(need, &piece));
+            RUN(launch_gemm_tn_x3tr(h, piece, s));
             if (t.M == h.M) continue;
             t.A += (int64_t)h.M * t.lda; t.B += (int64_t)h.M * t.ldb; t.M -= h.M;
         }
@@ -2914,26 +2972,15 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         stair_lstm_bwd_args enc[2] = {};
         for (int e = 0; e < 2; ++e) {
             stair_lstm_bwd_args &a = enc[e];
-            if (e == 0) {
-                a.x = video; a.ldx = V; a.rows = pl->n_vid * T; a.max_len = T; a.I = V; a.seq_off = didx + pl->off_seqv;
-                if (pl->ragged) a.seq_len = didx + pl->off_lenv;
-                if (flags & STAIR_RUN_VIDEO_BF16) { a.x = nullptr; a.x_bf16 = video; }
-                a.gates = (pl->ext_proj ? pl->proj : ws) + pl->o_xpv; a.cbuf = ws + pl->o_cv; a.out = map; a.d_out = g_map; a.d_hn = nullptr;
-                a.whh_pack_ws = ws + pl->o_wpack;
-                a.coop_ws = ws + pl->o_coop;
-            } else {
-                a.x = question; a.ldx = E; a.rows = pl->rows_q; a.max_len = pl->max_q; a.I = E; a.seq_off = didx + pl->off_seqt;
-                a.gates = (pl->ext_proj ? pl->proj : ws) + pl->o_xpt; a.cbuf = ws + pl->o_ct; a.out = ws + pl->o_tok; a.d_out = g_tok; a.d_hn = g_qfeat;
-                a.whh_pack_ws = ws + pl->o_wpack + 2 * (int64_t)H * H;
-                a.coop_ws = ws + pl->o_coop2;
-            }
-            a.n = e == 0 ? pl->n_vid : n; a.Hh = Hh; a.ldo = H; a.ldd = H;
+            if (e == 0) enc_input(a, g, 0, video, (flags & STAIR_RUN_VIDEO_BF16) != 0, pl->n_vid * T, pl->n_vid, T);
+            else enc_input(a, g, 1, question, false, pl->rows_q, n, pl->max_q);
+            enc_recurrence(a, pl, W, e, ws, didx);
+            a.gates = pl->proj_base(ws) + (e == 0 ? pl->pj.xpv : pl->pj.xpt);
+            a.cbuf = ws + (e == 0 ? pl->o_cv : pl->o_ct); a.out = e == 0 ? map : ws + pl->o_tok;
+            a.d_out = e == 0 ? g_map : g_tok; a.d_hn = e == 0 ? nullptr : g_qfeat; a.ldd = H;
             a.hprev_ws = ws + pl->o_hprev + (e == 0 ? 0 : (int64_t)pl->n_vid * T * H);
-            a.coop_ws_bytes = pl->coop_bytes;
-            a.status = reinterpret_cast<uint32_t *>(ws + pl->o_status);
             if (pl->o_tnenc[e]) { a.tn_ws = ws + pl->o_tnenc[e]; a.tn_ws_floats = pl->tnenc_floats[e]; }
             for (int d = 0; d < 2; ++d) {
-                a.w_hh[d] = W.enc[e][4 * d + 1];
                 a.dw_ih[d] = W.denc[e][4 * d]; a.dw_hh[d] = W.denc[e][4 * d + 1];
                 a.db_ih[d] = W.denc[e][4 * d + 2]; a.db_hh[d] = W.denc[e][4 * d + 3];
             }
@@ -2963,10 +3010,10 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     // The transposed module-weight images of the wt region were consumed by the level walk above; the region holds every weight of the
     // context (ctx_weight_floats), so it fits the transposed [8 Hh, I] image of either encoder's two W_ih.
     if (d_question)
-        RUN(launch_enc_input_grad((pl->ext_proj ? pl->proj : ws) + pl->o_xpt, pl->rows_q, Hh, W.enc[1][0], W.enc[1][4], E, ws + pl->o_wt,
+        RUN(launch_enc_input_grad(pl->proj_base(ws) + pl->pj.xpt, pl->rows_q, Hh, W.enc[1][0], W.enc[1][4], E, ws + pl->o_wt,
                                   d_question, s));
     if (d_video)
-        RUN(launch_enc_input_grad((pl->ext_proj ? pl->proj : ws) + pl->o_xpv, (int64_t)pl->n_vid * T, Hh, W.enc[0][0], W.enc[0][4], V,
+        RUN(launch_enc_input_grad(pl->proj_base(ws) + pl->pj.xpv, (int64_t)pl->n_vid * T, Hh, W.enc[0][0], W.enc[0][4], V,
                                   ws + pl->o_wt, d_video, s));
 #undef RUN
     return 0;
@@ -3011,36 +3058,18 @@ extern "C" int stair_plan_touched(const stair_ctx *ctx, const stair_plan *pl, in
         for (const char *sfx : {"", "_reverse"})
             for (const char *w : {"weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"}) mark(std::string(enc) + "." + w + sfx);
     lin("decoder.0"); lin("decoder.3");
-    const char *fk[4] = {"representation", "actions", "objects", "relations"};
-    const char *ffk[3] = {"representation", "relations", "actions"};
     const char *modes[4] = {"", "before", "after", "between"};
     for (const Bucket &b : pl->buckets) {
         if (b.cnt == 0) continue;
-        switch (b.op) {
-            case STAIR_OP_COMPARE: lin("Compare.param.0"); break;
-            case STAIR_OP_EQUALS: lin("Equals.param.0"); break;
-            case STAIR_OP_XOR: lin("Xor.param.0"); break;
-            case STAIR_OP_TOACTION: lin("ToAction.param.0"); lin("ToAction.param.3"); break;
-            case STAIR_OP_EXISTS: lin("Exists.param.0"); lin("Exists.param.3"); break;
-            case STAIR_OP_FILTER:
-                lin(std::string("Filter.param.") + fk[b.variant] + ".0"); lin(std::string("Filter.param.") + fk[b.variant] + ".3");
-                lin("Filter.dense.0");
-                if (b.variant == 0) lin("Filter.attention.0");     // receives an all-zero gradient (softmax over one element)
-                break;
-            case STAIR_OP_FILTERFRAME:
-                lin(std::string("FilterFrame.param.") + ffk[b.variant] + ".0"); lin(std::string("FilterFrame.param.") + ffk[b.variant] + ".3");
-                lin("FilterFrame.dense.0");
-                if (b.variant == 0) lin("FilterFrame.attention.0");
-                break;
-            case STAIR_OP_HASITEM: lin("HasItem.param.0"); lin("HasItem.param.3"); break;
-            case STAIR_OP_LOCALIZE: lin("Localize.video_linear.0"); lin("Localize.video_linear.3"); lin("Localize.keyword_linear.0"); break;
-            case STAIR_OP_SUPERLATIVE:
-                lin("Localize.video_linear.0"); lin("Localize.video_linear.3"); lin("Localize.keyword_linear.0");
-                lin("Superlative.dense.0");
-                break;
+        for (const WeightRow &r : kWeightRows)
+            if (r.used_by(b.op, b.variant)) lin(r.prefix);
+        switch (b.op) {         // what the weight table does not hold
+            case STAIR_OP_FILTER: if (b.variant == 0) lin("Filter.attention.0"); break;     // receives an all-zero gradient (softmax over one element)
+            case STAIR_OP_FILTERFRAME: if (b.variant == 0) lin("FilterFrame.attention.0"); break;
+            case STAIR_OP_HASITEM: lin("HasItem.param.3"); break;
             case STAIR_OP_RELATE: mark("Relate.beta"); break;
             case STAIR_OP_TEMPORAL:
-                lin("Temporal.dense.0"); mark("Temporal.layer_norm.weight"); mark("Temporal.layer_norm.bias");
+                mark("Temporal.layer_norm.weight"); mark("Temporal.layer_norm.bias");
                 if (b.variant)
                     for (int l : {0, 2, 4}) lin(std::string("Temporal.relate.") + modes[b.variant] + "." + std::to_string(l));
                 break;
@@ -3059,106 +3088,29 @@ extern "C" int stair_adam_step(float *params, const float *grads, float *exp_avg
                        guard, static_cast<hipStream_t>(stream));
 }
 
-// Layout introspection for tests: every workspace region as (name, begin, end) in floats.
+// Layout introspection for tests: every workspace region as (name, begin, end) in floats, as the builder assigned them (a region
+// that is handed out whole to buckets appears as those buckets' pieces), then END = (total, total + 1).
 // Returns the number of regions; fills up to `cap` entries.  `names` receives pointers to static strings
 // or to strings owned by the plan (valid until the plan is destroyed).
 extern "C" int stair_plan_regions(stair_plan *pl, const stair_ctx *ctx, const char **names, int64_t *beg, int64_t *end, int32_t cap) {
     if (!pl || !ctx) return -1;
-    static thread_local std::vector<std::string> store;
+    (void)ctx;
+    static thread_local std::vector<std::string> store;     // the formatted names (Region: what the builder recorded)
     store.clear();
-    std::vector<std::tuple<std::string, int64_t, int64_t>> r;
-    const int64_t H = ctx->cfg.hidden_size, A = ctx->cfg.answer_vocab_length, T = pl->T, n = pl->n;
-    auto add = [&](const std::string &nm, int64_t b, int64_t len) { if (len > 0) r.emplace_back(nm, b, b + len); };
-    add("idx", pl->o_idx, (int64_t)pl->idx.size());
-    add("vec", pl->o_vec, (int64_t)pl->n_vec * H);
-    add("map", pl->o_map, (int64_t)pl->n_map * T * H);
-    add("att", pl->o_att, (int64_t)std::max(pl->n_att, 1) * T);
-    add("tok", pl->o_tok, (int64_t)pl->rows_q * H);
-    add("qfeat", pl->o_qfeat, n * H);
-    add("vhn", pl->o_vhn, (int64_t)pl->n_vid * H);
-    if (!pl->ext_proj) {
-    add("xpv", pl->o_xpv, (int64_t)pl->n_vid * T * 4 * H);
-    add("xpt", pl->o_xpt, (int64_t)pl->rows_q * 4 * H);
+    for (const Region &g : pl->regions) {
+        if (g.name[0] == '.') {
+            const Bucket &b = pl->buckets[g.index];
+            store.push_back("b" + std::to_string(g.index) + "(op" + std::to_string(b.op) + "v" + std::to_string(b.variant) + ")" + g.name);
+        } else store.push_back(g.index >= 0 ? g.name + std::to_string(g.index) : std::string(g.name));
     }
-    if (!pl->ext_proj) add("bias", pl->o_bias, 8 * H);
-    add("wpack", pl->o_wpack, 4 * H * H);
-    if (!pl->ext_proj) {
-    if (ctx->cfg.video_size % 32 == 0) add("wplanes", pl->o_wplanes, 4 * H * ctx->cfg.video_size);
-    add("wplanes_t", pl->o_wplanes_t, 4 * H * ((ctx->cfg.text_size + 31) / 32 * 32));
-    add("xplanes_t", pl->o_xplanes_t, (int64_t)std::max(pl->rows_q, 1) * ((ctx->cfg.text_size + 31) / 32 * 32));
+    const int count = (int)pl->regions.size() + 1;
+    for (int i = 0; i < count && i < cap; ++i) {
+        const bool last = i == count - 1;
+        names[i] = last ? "END" : store[i].c_str();
+        beg[i] = last ? pl->total : pl->regions[i].beg;
+        end[i] = last ? pl->total + 1 : pl->regions[i].end;
     }
-    add("coop", pl->o_coop, (pl->coop_bytes + 3) / 4);
-    add("coop2", pl->o_coop2, (pl->coop_bytes + 3) / 4);
-    add("splitk", pl->o_splitk, kSplitKFloats);
-    add("tmpA", pl->o_tmpA, (int64_t)std::max(pl->maxI, 1) * T * H);
-    add("tmpB", pl->o_tmpB, (int64_t)std::max(pl->maxI, 1) * T * H);
-    add("kbuf", pl->o_kbuf, (int64_t)std::max(pl->maxK, 1) * H);
-    add("cat", pl->o_cat, (int64_t)pl->maxV * 3 * H);
-    add("hid", pl->o_hid, (int64_t)pl->maxV * 2 * H);
-    add("rs", pl->o_rs, (int64_t)std::max(pl->maxI, 1) * T);
-    add("sup", pl->o_sup, (int64_t)std::max(pl->maxSupRows, 1) * T);
-    add("extra", pl->o_extra, std::max(pl->maxI, 1));
-    add("logits", pl->o_logits, n * A);
-    add("status", pl->o_status, 128);
-    if (H == 512 && T <= 64) add("wfrag", pl->o_wfrag, 19 * H * H);
-    if (pl->train) {
-        int bi = 0;
-        for (const Bucket &b : pl->buckets) {
-            const std::string p = "b" + std::to_string(bi++) + "(op" + std::to_string(b.op) + "v" + std::to_string(b.variant) + ").";
-            const int64_t c = b.cnt;
-            if (b.svA != pl->o_tmpA) add(p + "svA", b.svA, c * T * H);
-            if (b.svB != pl->o_tmpB) add(p + "svB", b.svB, c * T * H);
-            if (b.svK != pl->o_kbuf) add(p + "svK", b.svK, (int64_t)b.nrows * H);
-            int v0, v3;
-            bucket_vec_weights(b.op, v0, v3);
-            if (b.svCat != pl->o_cat) add(p + "svCat", b.svCat, v0 >= 0 ? c * vd_cols(v0, H) : c * H);
-            if (b.dzV0 >= 0) add(p + "dzV0", b.dzV0, c * H);
-            if (b.dzV3 >= 0) add(p + "dzV3", b.dzV3, c * H);
-            if (b.svHid != pl->o_hid) add(p + "svHid", b.svHid, c * H);
-            if (b.svRs != pl->o_rs) add(p + "svRs", b.svRs, c * T);
-            if (b.svSup != pl->o_sup) add(p + "svSup", b.svSup, (int64_t)b.nrows * T);
-            if (b.svExtra != pl->o_extra) add(p + "svExtra", b.svExtra, c);
-        }
-        const int64_t I = std::max(pl->maxI, 1), Vv = pl->maxV;
-        add("cv", pl->o_cv, (int64_t)pl->n_vid * T * H);
-        add("ct", pl->o_ct, (int64_t)pl->rows_q * H);
-        add("hprev", pl->o_hprev, ((int64_t)pl->n_vid * T + pl->rows_q) * H);
-        add("wt", pl->o_wt, ctx_weight_floats(ctx));
-        add("gA", pl->o_gA, I * T * H);
-        add("gB", pl->o_gB, I * T * H);
-        if (pl->o_wfragT > 0) add("wfragT", pl->o_wfragT, (int64_t)WV_END * H * H);
-        for (const Bucket &b : pl->buckets) {
-            if (b.dzC >= 0) add("dzC", b.dzC, (int64_t)b.cnt * T * H);
-            if (b.gRow >= 0) add("gRow", b.gRow, (int64_t)b.cnt * H);
-        }
-        for (int w = 0; w < WF_COUNT; ++w) {
-            if (pl->wg_rows[w]) add("wg_dz" + std::to_string(w), pl->wg_dz[w], pl->wg_rows[w] * T * H);
-            if (pl->wg_part[w]) add("wg_part" + std::to_string(w), pl->wg_part[w], tn_x3tr_scratch_floats(pl->wg_rows[w] * T, H, H));
-        }
-        add("gV0", pl->o_gV0, Vv * 2 * H);
-        add("gV1", pl->o_gV1, Vv * 2 * H);
-        add("gCat", pl->o_gCat, Vv * 3 * H);
-        add("gStats", pl->o_gStats, I * T * 2);
-        add("gRs2", pl->o_gRs2, I * T);
-        add("dlogits", pl->o_dlogits, n * A);
-        add("loss", pl->o_loss, n);
-        add("gblock", pl->o_gblock, pl->o_map + (int64_t)pl->n_map * T * H - pl->o_vec);
-        add("gatt", pl->o_gatt, (int64_t)std::max(pl->n_att, 1) * T);
-        add("gtok", pl->o_gtok, (int64_t)pl->rows_q * H);
-        add("gqfeat", pl->o_gqfeat, n * H);
-        add("gK", pl->o_gK, (int64_t)std::max(pl->maxK, 1) * H);
-        add("gS", pl->o_gS, (int64_t)std::max(pl->maxSupRows, 1) * T);
-        add("gRs", pl->o_gRs, I * T);
-        add("gExtra", pl->o_gExtra, I);
-    }
-    add("END", pl->total, 1);
-    for (auto &t : r) store.push_back(std::get<0>(t));
-    for (int i = 0; i < (int)r.size() && i < cap; ++i) {
-        names[i] = store[i].c_str();
-        beg[i] = std::get<1>(r[i]);
-        end[i] = std::get<2>(r[i]);
-    }
-    return (int)r.size();
+    return count;
 }
 
 extern "C" int stair_plan_zero_grads(stair_plan *pl, void *workspace, stair_stream stream) {

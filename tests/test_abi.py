@@ -176,7 +176,10 @@ def test_linear_temporal_requires_full_length():
 @pytest.mark.parametrize('train', [False, True])
 def test_workspace_regions_are_disjoint(train):
     """Every region of the plan's workspace layout (arenas, per-bucket saves, gradient arenas, scratch) must be
-    disjoint from every other one, for all 12 program forms in one batch."""
+    disjoint from every other one, for all 12 program forms in one batch -- and together they must cover the workspace:
+    the list is what the builder recorded while it assigned the offsets, so a region that is missing from it shows as a
+    hole.  The only holes allowed are alignment padding: every region is aligned to 64 or to H floats (H = 512 here, a
+    multiple of 64), and empty regions in between add no more than one such alignment."""
     config = dict(spec.DEFAULT_CONFIG)
     names = sorted(synth.CORPUS)
     qs = [synth.make_question(config, 0, i, form=name, with_video=False) for i, name in enumerate(names)]
@@ -204,6 +207,11 @@ def test_workspace_regions_are_disjoint(train):
     info = PlanInfo()
     check(lib.stair_plan_get_info(plan, C.byref(info)))
     assert regs[-1][2] == 'END' and regs[-1][0] * 4 == info.workspace_bytes
+    assert nm[k - 1] == b'END'
+    assert regs[0][0] == 0, regs[0]
+    bound = max(64, config['hidden_size'])
+    for a, b in zip(regs, regs[1:]):
+        assert b[0] - a[1] < bound, ('hole of %d floats' % (b[0] - a[1]), a, b)
     lib.stair_plan_destroy(plan)
     lib.stair_ctx_destroy(h)
 
