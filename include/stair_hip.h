@@ -788,6 +788,34 @@ int stair_adam_step(float *params, const float *grads, float *exp_avg, float *ex
                     float beta1, float beta2, float eps, float weight_decay, int64_t n, const uint32_t *guard,
                     stair_stream stream);
 
+/* stair_adam_step with a gradient scale: when grad_scale (a device float, 4-byte aligned) is non-null, every gradient element
+ * is multiplied by *grad_scale -- read at execution time -- BEFORE the weight decay is added: torch's order, clip_grad_norm_
+ * then Adam.step.  `grads` is not written back (it keeps the unscaled gradient).  With grad_scale == NULL this is
+ * stair_adam_step, bit for bit (stair_adam_step is this call with a null scale).  Pass &out[1] of stair_grad_norm. */
+int stair_adam_step_scaled(float *params, const float *grads, float *exp_avg, float *exp_avg_sq,
+                           const int32_t *seg_of_block, const int32_t *touched, const float *step_of_seg, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, int64_t n, const uint32_t *guard,
+                           const float *grad_scale, stair_stream stream);
+
+/* Gradient norms of the flat fp32 gradient buffer that stair_adam_step reads (n floats, n % 256 == 0, 16-byte aligned), for
+ * clipping by global norm and for refusing a step whose gradients are not finite -- on the device, no host read-back.
+ * Segment `seg` (a parameter tensor) holds seg_numel[seg] floats from float 256 * seg_first_block[seg] on; segment index order
+ * need not be memory order.  What lies between a segment's last element and the end of its last block is never looked at.
+ *   seg_norm[seg] = L2 norm of the segment (fp32, n_seg entries);
+ *   out[0]        = global L2 norm: the 2-norm of the per-segment 2-norms, what torch.nn.utils.clip_grad_norm_ computes;
+ *   out[1]        = min(1, max_norm / (out[0] + 1e-6)) evaluated in fp32 as torch evaluates it on an fp32 tensor (scalar / tensor
+ *                   is tensor.reciprocal() * scalar there), so it equals clip_grad_norm_'s coefficient for the same norm bit
+ *                   for bit; max_norm = +inf gives exactly 1.0f ("measure, never scale"); max_norm must be > 0;
+ *   *guard |= 2     when the global sum of squares is not finite (a gradient element is inf or NaN, or its square overflows
+ *                   fp32); the other bits of the word stay as they are.  guard may be NULL.  Hand the same word to
+ *                   stair_adam_step_scaled and the non-finite step changes nothing.
+ * block_scratch: n / 256 floats, overwritten.  Two launches on `stream`: one wave per 256-float block stores the block's sum
+ * of squares (fp32, fixed order); one workgroup then sums each segment's block sums in fp64 in a fixed order and the segment
+ * sums in fp64 in segment-index order.  No atomics: the outputs are a pure function of the inputs, bit for bit, whatever the
+ * placement of the grid -- ranks that hold the same reduced buffer reach the same coefficient and the same decision. */
+int stair_grad_norm(const float *grads, int64_t n, const int32_t *seg_first_block, const int64_t *seg_numel, int32_t n_seg,
+                    float max_norm, float *block_scratch, float *seg_norm, float *out, uint32_t *guard, stair_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,7 +118,12 @@ int launch_scale_rows(float *G, const float *rs, int64_t rows, int H, hipStream_
 int launch_ce_loss(const float *logits, const int32_t *answers, float scale, float *loss, float *dlogits, int n, int A,
                    hipStream_t s);
 int launch_adam(float *p, const float *g, float *m, float *v, const int32_t *seg_of_block, const int32_t *touched,
-                const float *step_of_seg, float lr, float b1, float b2, float eps, float wd, int64_t n, const uint32_t *guard, hipStream_t s);
+                const float *step_of_seg, float lr, float b1, float b2, float eps, float wd, int64_t n, const uint32_t *guard, hipStream_t s,
+                const float *grad_scale = nullptr);     // device scalar: every gradient element times *grad_scale before weight decay
+// csrc/grad_norm.hip: seg_norm[seg] and out = {global L2 norm, min(1, max_norm / (norm + 1e-6))} of the flat gradient buffer;
+// *guard |= 2 when the norm is not finite.  block_scratch: n / 256 floats
+int launch_grad_norm(const float *g, int64_t n, const int32_t *seg_first_block, const int64_t *seg_numel, int n_seg, float max_norm,
+                     float *block_scratch, float *seg_norm, float *out, uint32_t *guard, hipStream_t s);
 int launch_argmax(const float *logits, int32_t *out, int n, int A, hipStream_t s);
 
 }  // namespace stair

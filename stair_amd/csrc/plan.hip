@@ -3088,6 +3088,17 @@ extern "C" int stair_adam_step(float *params, const float *grads, float *exp_avg
                        guard, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int stair_adam_step_scaled(float *params, const float *grads, float *exp_avg, float *exp_avg_sq,
+                                      const int32_t *seg_of_block, const int32_t *touched, const float *step_of_seg, float lr,
+                                      float beta1, float beta2, float eps, float weight_decay, int64_t n, const uint32_t *guard,
+                                      const float *grad_scale, stair_stream stream) {
+    STAIR_CHECK(params && grads && exp_avg && exp_avg_sq && seg_of_block && touched && step_of_seg, "null argument");
+    STAIR_CHECK(n >= 0 && n % 256 == 0, "the flat parameter buffer is made of whole 256-float blocks");
+    STAIR_CHECK(reinterpret_cast<uintptr_t>(grad_scale) % 4 == 0, "grad_scale must be 4-byte aligned");
+    return launch_adam(params, grads, exp_avg, exp_avg_sq, seg_of_block, touched, step_of_seg, lr, beta1, beta2, eps, weight_decay, n,
+                       guard, static_cast<hipStream_t>(stream), grad_scale);
+}
+
 // Layout introspection for tests: every workspace region as (name, begin, end) in floats, as the builder assigned them (a region
 // that is handed out whole to buckets appears as those buckets' pieces), then END = (total, total + 1).
 // Returns the number of regions; fills up to `cap` entries.  `names` receives pointers to static strings

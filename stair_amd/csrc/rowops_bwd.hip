@@ -1104,9 +1104,12 @@ int launch_ce_loss(const float *logits, const int32_t *answers, float scale, flo
 // this window; untouched tensors are skipped entirely, which is what torch does for grad == None
 // (modules that no program of the window used) -- their moments and step count do not advance.
 // one workgroup of 64 threads per 256-float block (= one segment granule), 16 bytes per thread
+// SCALED: every gradient element is multiplied by the device scalar *grad_scale first (the clip coefficient of stair_grad_norm:
+// torch's order is clip_grad_norm_, then Adam.step, which adds the weight decay to the clipped gradient); g is not written back
+template <bool SCALED>
 __global__ void adam_kernel(float *p, const float *g, float *m, float *v, const int32_t *seg_of_block, const int32_t *touched,
                             const float *step_of_seg, float lr, float b1, float b2, float eps, float wd, int64_t n,
-                            const uint32_t *guard) {
+                            const uint32_t *guard, const float *grad_scale) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
     if (guard && *guard) return;                      // the pass that produced g reported a failure: leave p, m, v untouched
@@ -1115,11 +1118,13 @@ __global__ void adam_kernel(float *p, const float *g, float *m, float *v, const 
     const float t = step_of_seg[seg];                 // already incremented for this step
     const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
     const float a = lr / bc1, rb2 = 1.0f / sqrtf(bc2);
+    const float gs = SCALED ? *grad_scale : 1.f;
     const v4f gv = *reinterpret_cast<const v4f *>(g + i);
     v4f pv = *reinterpret_cast<v4f *>(p + i), mv = *reinterpret_cast<v4f *>(m + i), vv = *reinterpret_cast<v4f *>(v + i);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float grad = gv[j];
+        if (SCALED) grad *= gs;
         if (wd != 0.f) grad += wd * pv[j];
         mv[j] = b1 * mv[j] + (1.f - b1) * grad;
         vv[j] = b2 * vv[j] + (1.f - b2) * grad * grad;
@@ -1129,12 +1134,16 @@ __global__ void adam_kernel(float *p, const float *g, float *m, float *v, const 
 }
 int launch_adam(float *p, const float *g, float *m, float *v, const int32_t *seg_of_block, const int32_t *touched,
                 const float *step_of_seg, float lr, float b1, float b2, float eps, float wd, int64_t n, const uint32_t *guard,
-                hipStream_t s) {
+                hipStream_t s, const float *grad_scale) {
     if (n == 0) return 0;
     STAIR_ACCT("adam_kernel", 7ll * n * 4);
     STAIR_CHECK(n % 256 == 0, "the flat parameter buffer is made of whole 256-float blocks");
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)(n / 256)), dim3(64), 0, s, p, g, m, v, seg_of_block, touched,
-                       step_of_seg, lr, b1, b2, eps, wd, n, guard);
+    if (grad_scale)
+        hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)(n / 256)), dim3(64), 0, s, p, g, m, v, seg_of_block, touched,
+                           step_of_seg, lr, b1, b2, eps, wd, n, guard, grad_scale);
+    else
+        hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)(n / 256)), dim3(64), 0, s, p, g, m, v, seg_of_block, touched,
+                           step_of_seg, lr, b1, b2, eps, wd, n, guard, grad_scale);
     STAIR_LAUNCH_CHECK();
     return 0;
 }

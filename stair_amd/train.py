@@ -125,10 +125,21 @@ class Trainer:
                  module_loss_weight=1.0, contrastive_window=32, no_intermediate=('FilterFrame',),
                  scheduler_start_factor=1.0, scheduler_end_factor=0.1, scheduler_total_iters=200000, world=1,
                  skip_untouched='ever', train_module_before_iters=1e10, train_decoder_after_iters=0, rank=0,
-                 dropout=None, dropout_seed=0, native_allreduce=False, class_table=None, global_batch=None, overlap_allreduce=None):
+                 dropout=None, dropout_seed=0, native_allreduce=False, class_table=None, global_batch=None, overlap_allreduce=None,
+                 max_grad_norm=None):
         """skip_untouched: 'ever'   -- a parameter is skipped by Adam until the first window that sends it a gradient
                                       (torch 1.13, which the reference pins: zero_grad() keeps zero tensors afterwards);
-                           'window' -- skipped in every window that does not touch it (torch >= 2.0, set_to_none=True)."""
+                           'window' -- skipped in every window that does not touch it (torch >= 2.0, set_to_none=True).
+        max_grad_norm: None (default) -- the step is the reference's, which has no clipping: nothing extra is launched;
+                       a positive float -- torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) between the gradient
+                                      exchange and Adam, on the device (stair_grad_norm + stair_adam_step_scaled, no host
+                                      read-back), and a step whose gradient norm is not finite is REFUSED: weights, moments
+                                      and step counts stay those of the last good step and check() raises;
+                       float('inf') -- measure and refuse non-finite steps, never scale (the coefficient is exactly 1).
+                       The clip coefficient is applied inside the Adam kernel: `p.grad` (views of flat_g) keeps the UNCLIPPED
+                       reduced gradient.  At world > 1 the norm is that of the summed bucket, the same bits on every rank, so
+                       coefficient, decision and update are the same everywhere with no second collective.
+                       Telemetry: grad_norm, seg_grad_norm, grad_norms_by_name(), finished_grad_norms()."""
         # train_module.py:350,376 gate the two loss families by the reference's global_steps (one per QUESTION there):
         # intermediate losses while global_steps < train_module_before_iters, decoder loss once global_steps >
         # train_decoder_after_iters.  Question i of a rank's shard has global step seen + 1 + rank + i * world.
@@ -142,6 +153,12 @@ class Trainer:
         self.global_batch = global_batch
         self.overlap_allreduce = (world > 1) if overlap_allreduce is None else bool(overlap_allreduce)
         self.inject_failure = False                          # test hook: set this rank's status word after the backward pass
+        self.inject_nonfinite = False                        # test hook: +inf into this rank's first gradient element after the backward pass
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not max_grad_norm > 0:
+                raise ValueError('max_grad_norm must be None or a positive number (float("inf"): measure only), got %r' % (max_grad_norm,))
+            max_grad_norm = float(max_grad_norm)
+        self.max_grad_norm = max_grad_norm
         self.class_table = class_table
         self.allreduce_events = None                        # set to [] to collect (start, end) events around the step's collective
         self.before_iters, self.after_iters, self.rank = train_module_before_iters, train_decoder_after_iters, rank
@@ -207,6 +224,17 @@ class Trainer:
             from .comm import NativeComm
             self.comm = NativeComm(rank, world)
         self.offsets = offs
+        self.grad_norm = self.seg_grad_norm = None
+        if max_grad_norm is not None:
+            # [global L2 norm, clip coefficient] and the per-tensor norms (weight-table order) of the last step: device tensors,
+            # written by the step's stair_grad_norm -- reading them synchronises, step() does not
+            self.grad_norm = torch.zeros(2, device=dev)
+            self.seg_grad_norm = torch.zeros(len(names), device=dev)
+            self._seg_first_block = torch.tensor([o // SEG for o in offs], dtype=torch.int32, device=dev)
+            self._seg_numel = torch.tensor([params[nme].numel() for nme in names], dtype=torch.int64, device=dev)
+            self._norm_scratch = torch.empty(total // SEG, device=dev)
+            self._norms = []                                 # (step, pinned copy of grad_norm, event) per step not yet handed out
+            self._norm_free = []                             # pinned buffers to reuse
 
     def lr_factor(self):
         """train_module.py:328-331."""
@@ -265,6 +293,8 @@ class Trainer:
                             ready_event=self._ev_ready if overlap else None)
         if self.inject_failure:
             res.status_word().fill_(1)
+        if self.inject_nonfinite:
+            self.flat_g[:1].fill_(float('inf'))
         self.guard.copy_(res.status_word())
         late_ev = None
         if self.allreduce_late_events is not None and self.world > 1:
@@ -276,10 +306,21 @@ class Trainer:
             e0.record()
         # the exchange: gradients summed, mask OR-ed, status OR-ed -- over RCCL / xGMI; in two pieces when overlapped
         reduce_gradients(self.flat_g, t, self.world, self.bucket, self.comm, status=self.guard,
-                         split=self.split if overlap else None, side_stream=self._side, ready_event=self._ev_ready, late_events=late_ev)
+                         split=self.split if overlap else None, side_stream=self._side,
+                         # (the injected inf is written after the pass: the early piece then waits for the whole stream)
+                         ready_event=None if self.inject_nonfinite else self._ev_ready, late_events=late_ev)
         if e0 is not None:
             e1.record()
             self.allreduce_events.append((e0, e1))
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        clip = self.max_grad_norm is not None
+        if clip:
+            # norms of the REDUCED bucket (identical on every rank), the clip coefficient, and bit 1 of the guard when the
+            # norm is not finite -- before the bookkeeping below reads the guard
+            check(lib.stair_grad_norm(C.c_void_p(self.flat_g.data_ptr()), self.n, C.c_void_p(self._seg_first_block.data_ptr()),
+                                      C.c_void_p(self._seg_numel.data_ptr()), self.seg_grad_norm.numel(), C.c_float(self.max_grad_norm),
+                                      C.c_void_p(self._norm_scratch.data_ptr()), C.c_void_p(self.seg_grad_norm.data_ptr()),
+                                      C.c_void_p(self.grad_norm.data_ptr()), C.c_void_p(self.guard.data_ptr()), stream))
         # bookkeeping of a step the guard refuses stays that of the last good step (on the device: the host does not wait)
         ok = (self.guard == 0).to(torch.int32)
         if self.skip_untouched == 'ever':
@@ -288,13 +329,16 @@ class Trainer:
             self.touched.copy_(t)
         self.steps += (self.touched * ok).to(torch.float32)
         lr = self.lr * self.lr_factor()
-        check(lib.stair_adam_step(C.c_void_p(self.flat_p.data_ptr()), C.c_void_p(self.flat_g.data_ptr()),
-                                  C.c_void_p(self.exp_avg.data_ptr()), C.c_void_p(self.exp_avg_sq.data_ptr()),
-                                  C.c_void_p(self.seg_of_block.data_ptr()), C.c_void_p(self.touched.data_ptr()),
-                                  C.c_void_p(self.steps.data_ptr()), C.c_float(lr), C.c_float(self.betas[0]),
-                                  C.c_float(self.betas[1]), C.c_float(self.eps), C.c_float(self.wd), self.n,
-                                  C.c_void_p(self.guard.data_ptr()),          # guard: no update when ANY rank's pass failed
-                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        adam_args = (C.c_void_p(self.flat_p.data_ptr()), C.c_void_p(self.flat_g.data_ptr()),
+                     C.c_void_p(self.exp_avg.data_ptr()), C.c_void_p(self.exp_avg_sq.data_ptr()),
+                     C.c_void_p(self.seg_of_block.data_ptr()), C.c_void_p(self.touched.data_ptr()),
+                     C.c_void_p(self.steps.data_ptr()), C.c_float(lr), C.c_float(self.betas[0]),
+                     C.c_float(self.betas[1]), C.c_float(self.eps), C.c_float(self.wd), self.n,
+                     C.c_void_p(self.guard.data_ptr()))           # guard: no update when ANY rank's pass failed
+        if clip:       # gradient times the coefficient inside the kernel: flat_g keeps the unclipped gradient
+            check(lib.stair_adam_step_scaled(*adam_args, C.c_void_p(self.grad_norm.data_ptr() + 4), stream))
+        else:
+            check(lib.stair_adam_step(*adam_args, stream))
         if len(self._status) < 16:
             host = torch.empty(1, dtype=torch.int32).pin_memory()
         else:                                                 # the oldest entry's buffer is reused: look at it first
@@ -304,12 +348,26 @@ class Trainer:
         ev = torch.cuda.Event()
         ev.record()
         self._status.append((self.iters, host, ev))
+        if clip:
+            if len(self._norms) >= 16:                        # nobody collects them: the oldest step's figures make room
+                _, old, old_ev = self._norms.pop(0)
+                old_ev.synchronize()
+                self._norm_free.append(old)
+            nhost = self._norm_free.pop() if self._norm_free else torch.empty(2, dtype=torch.float32).pin_memory()
+            nhost.copy_(self.grad_norm, non_blocking=True)
+            nev = torch.cuda.Event()
+            nev.record()
+            self._norms.append((self.iters, nhost, nev))
         self.iters += 1                                       # scheduler.step()
         return loss, res
 
     def _raise_if_failed(self, step, host, ev):
         from ._lib import StairError
         ev.synchronize()
+        if int(host[0]) == 2:                                 # bit 1 alone: stair_grad_norm found the reduced bucket's norm inf or NaN
+            self._status = []
+            raise StairError('non-finite gradient norm in optimizer step %d; weights, moments and step counts are those of the last '
+                             'good step' % step)
         if int(host[0]) != 0:
             self._status = []
             raise StairError('optimizer step %d was skipped on every rank: a cooperative LSTM recurrence timed out on at least one of '
@@ -318,8 +376,9 @@ class Trainer:
                              'one-workgroup kernels' % step)
 
     def check(self, wait=True):
-        """Raises StairError if a step reported a failed pass (a cooperative LSTM hand-off that timed out: the gradients of
-        that step held NaN).  The word it reads is the step's status summed over all ranks -- the one Adam's guard read -- so at
+        """Raises StairError if a step reported a failed pass (bit 0: a cooperative LSTM hand-off that timed out, the gradients of
+        that step held NaN; bit 1, with max_grad_norm: the norm of the reduced gradients was inf or NaN).  A caller may catch
+        the error and go on with the next window.  The word it reads is the step's status summed over all ranks -- the one Adam's guard read -- so at
         world > 1 every rank raises for the same step, whichever rank failed, and none of them has applied the update:
         parameters, moments and per-tensor step counts are those of the last good step.  The host-side counters (`iters`, the
         LambdaLR position, and `questions_seen`) have advanced past the refused window, as the data loader has.
@@ -331,3 +390,23 @@ class Trainer:
                 continue
             self._raise_if_failed(*entry)
         self._status = keep[-16:]
+
+    def grad_norms_by_name(self):
+        """{weight name: L2 norm of its reduced, unclipped gradient in the last step} -- 0.0 for tensors no program of the
+        window touched.  Needs max_grad_norm; synchronises (a device -> host copy)."""
+        if self.seg_grad_norm is None:
+            raise RuntimeError('gradient norms are measured only with max_grad_norm (float("inf") measures without clipping)')
+        return dict(zip(self.model._weight_names, self.seg_grad_norm.cpu().tolist()))
+
+    def finished_grad_norms(self):
+        """[(step, global gradient norm, clip coefficient)] of the steps the GPU has finished since the last call, oldest first;
+        never waits.  The figures travel through a ring of page-locked buffers beside the status words: a caller that does
+        not collect them loses all but the latest 16."""
+        if self.seg_grad_norm is None:
+            raise RuntimeError('gradient norms are measured only with max_grad_norm (float("inf") measures without clipping)')
+        out = []
+        while self._norms and self._norms[0][2].query():
+            step, host, _ = self._norms.pop(0)
+            out.append((step, float(host[0]), float(host[1])))
+            self._norm_free.append(host)
+        return out
