@@ -45,7 +45,10 @@ typedef struct stair_config {
     int32_t video_size;          /* V, multiple of 4 */
     int32_t text_size;           /* E (300), multiple of 4 */
     int32_t answer_vocab_length; /* A */
-    int32_t max_video_length;    /* selects Conv1d (>32) or Linear(T,T) Temporal nets, modules.py:255 */
+    int32_t max_video_length;    /* selects Conv1d (>32) or Linear(T,T) Temporal nets, modules.py:255.  No upper bound for inference.
+                                    TRAINING plans (STAIR_PLAN_TRAIN) are bounded by two backward kernels, see stair_plan_build:
+                                    <= 141 where a program has a Temporal before/after/between node (Conv1d filters of
+                                    k = round(max_video_length / 4) <= 35), and T <= 113 frames where it has a Superlative node */
     int32_t object_types;        /* O, FilterFrame pretrain head width */
     int32_t have_pretrain_head;  /* 0/1 */
 } stair_config;
@@ -507,7 +510,14 @@ int stair_cosine_topk(const float *queries, int64_t ldq, const int32_t *q_idx, c
  *   q_off    [n+1]      row range of question q in the packed question embedding matrix
  *   T                   frames per video in this batch (<= max_video_length; == for Linear Temporal)
  * Errors (non-zero) mirror the reference's failures: invalid program (assert len(stack)==1,
- * module_net.py:135), operand of the wrong kind, span outside the question. */
+ * module_net.py:135), operand of the wrong kind, span outside the question.
+ * Limits of a STAIR_PLAN_TRAIN plan (every stair_plan_build* function; the message states the limit; inference plans of the same
+ * shapes are accepted and run):
+ *   - a Superlative node needs T <= 113: its backward kernel keeps the T x T scores and their gradients, plus 64-column slices of
+ *     the T frames and T action rows, in LDS -- (2 T^2 + 132 T) * 4 bytes of the 160 KB a workgroup can have (161 816 B at 113);
+ *   - a Temporal before/after/between node needs Conv1d filters of k = round(max_video_length / 4) <= 35 (the third layer's
+ *     2 k + 1 = 71 taps and a bias fill the 72 floats its backward kernel stages per filter), i.e. max_video_length <= 141
+ *     (round half to even: 142 / 4 = 35.5 -> 36).  Linear(T,T) nets (max_video_length <= 32) and Temporal `while` have no such bound. */
 #define STAIR_PLAN_TRAIN 1 /* flags: keep every intermediate and lay out gradient arenas for stair_plan_backward */
 #define STAIR_PLAN_NO_CSE 2 /* flags: compute every node of every question, as module_net.py:100-106 does.  By default a node whose
                                operands are the encoded clip, keyword strings, identical question spans or other such nodes is

@@ -82,6 +82,21 @@ int launch_cosine_attn_bwd_grouped(const float *F, const float *Kmat, const floa
                                    const float *dscore, const int32_t *dscore_idx, const int32_t *pair_start,
                                    const int32_t *pair_cnt, float *dF, float *dK, float *nf_ws, float *nk_ws, int n, int npairs,
                                    int T, int H, int ka_max, hipStream_t s);
+// The two shape limits of the backward kernels, stated once: the launchers check them, and the plan builder refuses a
+// STAIR_PLAN_TRAIN plan that would run into either (stair_plan_build*), before any pass has run.
+// Dynamic LDS of one cosine_attn_bwd_grouped_kernel block; mfma = its MFMA form (images padded to multiples of 32), else the scalar one.
+constexpr size_t kCosineBwdLdsLimit = 160 * 1024;
+struct CosineBwdLds { size_t bytes; bool mfma; };
+inline CosineBwdLds cosine_attn_bwd_grouped_lds(int T, int ka_max) {
+    const int TP = (T + 31) / 32 * 32, KP = (ka_max + 31) / 32 * 32;
+    const size_t shmem_mf = (2 * (size_t)KP * (TP + 1) + (size_t)KP * 64 + (size_t)TP * 64 + TP + KP + 2 * ka_max) * sizeof(float);
+    const size_t shmem_sc = (2 * (size_t)ka_max * T + (size_t)ka_max * 64 + (size_t)T * 64 + T + ka_max + 2 * ka_max) * sizeof(float);
+    const bool mf = ka_max > 8 && shmem_mf <= 80 * 1024;     // many pairs per instance (Superlative); Localize (1-2 pairs) is bound by its F and dF rows, not by the products; at least two blocks per CU
+    return {mf ? shmem_mf : shmem_sc, mf};
+}
+// temporal_relate_bwd_kernel stages each Conv1d filter in kRelateTapStride LDS floats: up to 71 taps (2 k + 1 with k <= 35) + the bias
+constexpr int kRelateTapStride = 72;
+constexpr int kRelateMaxKsize = (kRelateTapStride - 2) / 2;
 int launch_temporal_relate_bwd(const float *att, const int32_t *att_idx, const int32_t *att_k, const float *drel,
                                const int32_t *rel_idx, float *datt, int n, int T, int mode, int conv, int ksize,
                                const float *const w[6], float *const dw[6], hipStream_t s, const int32_t *len = nullptr,

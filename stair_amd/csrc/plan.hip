@@ -1428,6 +1428,38 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
     return 0;
 }
 
+// largest T at which Superlative's backward kernel fits its LDS images (it scores T action rows against T frames: ka_max = T)
+int superlative_train_max_frames() {
+    int t = 0;
+    while (cosine_attn_bwd_grouped_lds(t + 1, t + 1).bytes <= kCosineBwdLdsLimit) ++t;
+    return t;
+}
+// largest max_video_length whose Conv1d filters, k = round(L / 4), the backward relate kernel stages
+int relate_train_max_video_length() {
+    int l = 1;
+    while (py_round((l + 1) / 4.0) <= kRelateMaxKsize) ++l;
+    return l;
+}
+
+// A training plan whose reverse pass a launcher would refuse is refused here, before a forward pass has been spent on it.  Both
+// bounds are the launchers' own (csrc/ops.h); inference plans of these shapes run.
+int check_backward_limits(const stair_plan *pl, const stair_ctx *ctx) {
+    const int T = pl->T;
+    for (const Bucket &b : pl->buckets) {
+        if (b.cnt == 0) continue;
+        if (b.op == STAIR_OP_SUPERLATIVE && cosine_attn_bwd_grouped_lds(T, T).bytes > kCosineBwdLdsLimit) {
+            STAIR_FAIL("stair_plan_build: a STAIR_PLAN_TRAIN plan with a Superlative node takes T <= " + std::to_string(superlative_train_max_frames()) +
+                       " frames (the backward pass keeps its T x T scores in " + std::to_string(kCosineBwdLdsLimit / 1024) +
+                       " KB of LDS); T = " + std::to_string(T));
+        }
+        if (b.op == STAIR_OP_TEMPORAL && b.variant != 0 && ctx->conv && ctx->ksize > kRelateMaxKsize)
+            STAIR_FAIL("stair_plan_build: a STAIR_PLAN_TRAIN plan with a Temporal before/after/between node takes Conv1d filters of k <= " +
+                       std::to_string(kRelateMaxKsize) + " (max_video_length <= " + std::to_string(relate_train_max_video_length()) +
+                       "); k = round(max_video_length / 4) = " + std::to_string(ctx->ksize));
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int stair_plan_build(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
@@ -1478,6 +1510,8 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     STAIR_CHECK(!pl->ragged || ctx->conv, "clips of different lengths need the Conv1d Temporal nets (Linear(T,T) fixes T, modules.py:266-277)");
     const auto t_begin = std::chrono::steady_clock::now();
     if (int rc = interpret_programs(pl, prog_off, tokens, span_lo, span_hi, q_off, video_of_question, !(flags & STAIR_PLAN_NO_CSE))) return rc;
+    if (pl->train)
+        if (int rc = check_backward_limits(pl, ctx)) return rc;
     if (int rc = build_index_image(pl, q_off)) return rc;
     if (int rc = layout_workspace(pl, ctx)) return rc;
     if (plan_debug())

@@ -434,12 +434,10 @@ int launch_cosine_attn_bwd_grouped(const float *F, const float *Kmat, const floa
     hipLaunchKernelGGL(rownorm_kernel, dim3((unsigned)((frows + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s, F, frows, H, nf_ws);
     hipLaunchKernelGGL(rownorm_kernel, dim3((npairs + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, s, Kmat, (int64_t)npairs, H, nk_ws);
     STAIR_LAUNCH_CHECK();
-    const int TP = (T + 31) / 32 * 32, KP = (ka_max + 31) / 32 * 32;
-    const size_t shmem_mf = (2 * (size_t)KP * (TP + 1) + (size_t)KP * 64 + (size_t)TP * 64 + TP + KP + 2 * ka_max) * sizeof(float);
-    const size_t shmem_sc = (2 * (size_t)ka_max * T + (size_t)ka_max * 64 + (size_t)T * 64 + T + ka_max + 2 * ka_max) * sizeof(float);
-    const bool mf = ka_max > 8 && shmem_mf <= 80 * 1024;     // many pairs per instance (Superlative); Localize (1-2 pairs) is bound by its F and dF rows, not by the products; at least two blocks per CU
-    const size_t shmem = mf ? shmem_mf : shmem_sc;
-    STAIR_CHECK(shmem <= 160 * 1024, "cosine backward: Ka*T too large for LDS");
+    const CosineBwdLds lds = cosine_attn_bwd_grouped_lds(T, ka_max);      // csrc/ops.h: the plan builder asks the same function
+    const bool mf = lds.mfma;
+    const size_t shmem = lds.bytes;
+    STAIR_CHECK(shmem <= kCosineBwdLdsLimit, "cosine backward: Ka*T too large for LDS");
     if (shmem > 48 * 1024) {   // e.g. Superlative at T = 64: 16 + 16 + 16 KB; at max_video_length = 150 (args.py:29): 165 KB
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&cosine_attn_bwd_grouped_kernel<true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
@@ -457,7 +455,6 @@ int launch_cosine_attn_bwd_grouped(const float *F, const float *Kmat, const floa
 // ---------------------------------------------------------------------------------------------
 // Temporal relate nets backward (recomputes the three layers in LDS).  dw[6] accumulate with atomics.
 struct RelateWB { const float *w[6]; float *dw[6]; long long *dw64[6]; };      // dw64: fixed-point shadows (det_shadow) or NULL
-constexpr int kRelateTapStride = 72;      // LDS floats per staged Conv1d filter: up to 71 taps (2 k + 1 with k <= 35) + the bias
 __global__ void temporal_relate_bwd_kernel(const float *att, const int32_t *att_idx, const int32_t *att_k,
                                            const float *drel, const int32_t *rel_idx, float *datt, int n, int T, int mode,
                                            int conv, int ksize, RelateWB W, const int32_t *len, const int32_t *gatt_idx) {
@@ -567,7 +564,7 @@ int launch_temporal_relate_bwd(const float *att, const int32_t *att_idx, const i
         W.w[i] = (mode && w) ? w[i] : nullptr; W.dw[i] = (mode && dw) ? dw[i] : nullptr;
         W.dw64[i] = W.dw[i] ? det_shadow(W.dw[i]) : nullptr;
     }
-    STAIR_CHECK(!(mode && conv) || 2 * ksize + 1 < kRelateTapStride, "Conv1d relate nets: kernel size <= 35");
+    STAIR_CHECK(!(mode && conv) || ksize <= kRelateMaxKsize, "Conv1d relate nets: kernel size <= 35");
     hipLaunchKernelGGL(temporal_relate_bwd_kernel, dim3(n), dim3(64), (6 * T + 3 * kRelateTapStride) * sizeof(float), s, att, att_idx, att_k, drel,
                        rel_idx, datt, n, T, mode, conv, ksize, W, len, gatt_idx);
     STAIR_LAUNCH_CHECK();
@@ -697,16 +694,17 @@ int launch_layernorm_bwd(const float *dOut, int64_t g_gs, const int32_t *g_idx, 
                          const float *gamma, float eps, float *dZ, float *stats, float *dgamma, float *dbeta, hipStream_t s,
                          float scale) {
     if (n == 0) return 0;
-    STAIR_ACCT("layernorm_bwd_kernel+param_grad", (3ll * n * T * H + 2ll * n * T) * 4);
     const int64_t rows = (int64_t)n * T;
     const bool al = ((reinterpret_cast<uintptr_t>(dOut) | reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(dZ) | reinterpret_cast<uintptr_t>(gamma)) & 15) == 0;
     if (al && (H == 256 || H == 512) && g_gs % 4 == 0) {
+        STAIR_ACCT("layernorm_bwd_fused_kernel", (3ll * n * T * H) * 4);        // the accounting says which form ran
         const unsigned blocks = (unsigned)std::min<int64_t>((rows + kWavesPerBlock - 1) / kWavesPerBlock, 256 * 4);
         if (H == 512) hipLaunchKernelGGL(layernorm_bwd_fused_kernel<2>, dim3(blocks), dim3(kBlock), 0, s, dOut, g_gs, g_idx, Y, n, T, gamma, eps, dZ, dgamma, dbeta, scale, det_shadow(dgamma), det_shadow(dbeta));
         else hipLaunchKernelGGL(layernorm_bwd_fused_kernel<1>, dim3(blocks), dim3(kBlock), 0, s, dOut, g_gs, g_idx, Y, n, T, gamma, eps, dZ, dgamma, dbeta, scale, det_shadow(dgamma), det_shadow(dbeta));
         STAIR_LAUNCH_CHECK();
         return 0;
     }
+    STAIR_ACCT("layernorm_bwd_kernel+param_grad", (3ll * n * T * H + 2ll * n * T) * 4);
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)((rows + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0,
                        s, dOut, g_gs, g_idx, Y, n, T, H, gamma, eps, dZ, stats, scale);
     STAIR_LAUNCH_CHECK();

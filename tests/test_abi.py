@@ -104,7 +104,7 @@ def test_videonmn_state_dict_layout(heads):
     assert np.array_equal(m.state_dict()['submodules.decoder.3.bias'].numpy(), w['submodules.decoder.3.bias'])
 
 
-def _build(config, programs, spans, q_lens, T):
+def _build(config, programs, spans, q_lens, T, flags=0):
     h = _ctx(config)
     enc = [np.asarray(spec.encode_program(p), dtype=np.int32) for p in programs]
     n = len(programs)
@@ -118,7 +118,7 @@ def _build(config, programs, spans, q_lens, T):
     q_off = np.zeros(n + 1, np.int32); np.cumsum(q_lens, out=q_off[1:])
     ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
     plan = C.c_void_p()
-    rc = lib.stair_plan_build(h, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), T, 0, C.byref(plan))
+    rc = lib.stair_plan_build(h, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), T, flags, C.byref(plan))
     return h, plan, rc, prog_off
 
 
@@ -171,6 +171,40 @@ def test_linear_temporal_requires_full_length():
     h, plan, rc, _ = _build(config, [['Filter', 'video', 'objects']], [{}], [8], 6)
     assert rc != 0 and b'max_video_length' in lib.stair_last_error()
     lib.stair_ctx_destroy(h)
+
+
+def _build_forms(L, T, forms, flags):
+    """rc and message of stair_plan_build for one question per form at max_video_length L, T frames (tiny configuration)"""
+    config = dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, answer_vocab_length=16, max_video_length=L, object_types=10)
+    qs = [synth.make_question(config, 0, i, form=f, with_video=False) for i, f in enumerate(forms)]
+    h, plan, rc, _ = _build(config, [q['nmn_program_list'] for q in qs], [q['prog_str_to_question_tokens'] for q in qs],
+                            [q['question'].shape[0] for q in qs], T, flags)
+    msg = lib.stair_last_error().decode() if rc else ''
+    if rc == 0:
+        lib.stair_plan_destroy(plan)
+    lib.stair_ctx_destroy(h)
+    return rc, msg
+
+
+def test_training_plans_beyond_the_backward_limits_are_refused_at_build():
+    """include/stair_hip.h, stair_plan_build: a STAIR_PLAN_TRAIN plan whose reverse pass a launcher would refuse -- Superlative beyond
+    T = 113 (the T x T score images of its backward kernel in 160 KB of LDS), Temporal before/after/between beyond Conv1d filters of
+    k = 35 (max_video_length 141; round half to even makes 142 -> 36) -- is refused when it is built, with the limit in the message;
+    the last admitted sizes build, and so do inference plans of the refused ones.  P3 = Superlative(max, ..), P5 = Temporal before and
+    after, P6 = Temporal while (no relate nets: no bound)."""
+    TRAIN = 1
+    assert _build_forms(141, 113, ['P3', 'P5', 'C1'], TRAIN)[0] == 0
+    rc, msg = _build_forms(141, 114, ['P1', 'P3'], TRAIN)
+    assert rc != 0 and 'Superlative' in msg and 'T <= 113' in msg and 'T = 114' in msg, msg
+    assert _build_forms(141, 114, ['P1', 'P5', 'P6'], TRAIN)[0] == 0            # no Superlative node: T = 114 trains
+    assert _build_forms(141, 114, ['P1', 'P3'], 0)[0] == 0
+    assert _build_forms(141, 141, ['P3', 'P5', 'C1'], 0)[0] == 0
+    assert _build_forms(141, 64, ['P5'], TRAIN)[0] == 0
+    rc, msg = _build_forms(142, 64, ['P1', 'P5'], TRAIN)
+    assert rc != 0 and 'Temporal before/after/between' in msg and 'k <= 35' in msg and 'max_video_length <= 141' in msg and '= 36' in msg, msg
+    assert _build_forms(142, 64, ['P1', 'P6'], TRAIN)[0] == 0                   # `while` has no relate nets
+    assert _build_forms(142, 64, ['P1', 'P5'], 0)[0] == 0
+    assert _build_forms(150, 150, ['P3', 'P5', 'C1'], 0)[0] == 0                # args.py:29's default stays an inference size
 
 
 @pytest.mark.parametrize('train', [False, True])

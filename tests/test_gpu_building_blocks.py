@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
 
-@pytest.mark.parametrize('G,T,H,npairs', [(3, 8, 64, 5), (4, 64, 512, 9), (1, 33, 128, 1)])
+@pytest.mark.parametrize('G,T,H,npairs', [(3, 8, 64, 5), (4, 64, 512, 9), (1, 33, 128, 1), (3, 33, 192, 5), (2, 40, 320, 4)])
 def test_cosine_attn_backward_matches_autograd(G, T, H, npairs):
     from stair_amd import ops
     g = torch.Generator().manual_seed(G + T + H)

@@ -565,9 +565,9 @@ def filterframe_case(rng, T, O, H, lens, slots, n_slots):
     return xmap, gold, W, b
 
 
-@pytest.mark.parametrize('T,O,H', [(102, 150, 512), (426, 36, 64), (15360, 1, 64), (40, 36, 512), (24, 150, 64)])
+@pytest.mark.parametrize('T,O,H', [(102, 150, 512), (426, 36, 64), (15360, 1, 64), (40, 36, 512), (24, 150, 64), (40, 36, 192), (24, 36, 448)])
 def test_filterframe_kernel_vs_fp64(T, O, H):
-    """T * O up to the LDS limit, O in {1, 36, 150}, H in {64, 512}, all-zero gold rows, saturated softmax frames, clips
+    """T * O up to the LDS limit, O in {1, 36, 150}, H in {64, 192, 448, 512}, all-zero gold rows, saturated softmax frames, clips
     shorter than T; two items share a tile (atomic adds); d_map, dW, db vs fp64 autograd."""
     rng = np.random.default_rng(T * O + H)
     lens, slots = [T, max(1, T // 2), max(1, T // 2)], [1, 3, 3]     # items 1 and 2 share a tile (one clip)

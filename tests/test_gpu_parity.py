@@ -249,11 +249,12 @@ def test_two_contexts_keep_their_own_options():
 
 def test_l2normalize_and_zero_vector():
     from stair_amd import ops
-    x = torch.randn(9, 64)
-    x[4] = 0
-    y = ops.l2normalize(x.to(DEV))
-    ref = x / x.norm(dim=1, keepdim=True).clamp_min(1e-12)
-    assert _maxerr(y, ref) < 1e-6
+    for H in (64, 320):                 # 320: a whole trip of the row walk and a partial one
+        x = torch.randn(9, H)
+        x[4] = 0
+        y = ops.l2normalize(x.to(DEV))
+        ref = x.double() / x.double().norm(dim=1, keepdim=True).clamp_min(1e-12)
+        assert _maxerr(y, ref) < 1e-6, H
 
 
 # ---------------------------------------------------------------------------------------------
@@ -450,7 +451,8 @@ def test_larger_batch_against_oracle(matmul):
         assert int(res.pred[qi]) == int(torch.argmax(r['logits']))
 
 
-@pytest.mark.parametrize('n,C,H,k', [(1, 5, 64, 5), (37, 214, 512, 10), (300, 1024, 256, 3), (9, 70, 96, 10)])
+@pytest.mark.parametrize('n,C,H,k', [(1, 5, 64, 5), (37, 214, 512, 10), (300, 1024, 256, 3), (9, 70, 96, 10), (9, 70, 192, 10),
+                                     (9, 70, 320, 10), (9, 70, 448, 10)])
 def test_cosine_topk_matches_torch(n, C, H, k):
     """stair_cosine_topk == argsort(CosineSimilarity) (evaluate.py:95-97): indices exact, similarities to 2e-6;
     row gather through q_idx; exact ties keep the lower index."""

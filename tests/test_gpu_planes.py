@@ -127,7 +127,8 @@ def test_gemm_planes_rejects_bad_shapes():
 # stored bf16 clip features (BASELINE.json configs[1]): the oracle is fed the SAME rounded values (exact in fp32), so the
 # 1e-4 logit bar of north_star applies unchanged
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('M,N,K', [(64, 16, 64), (4096, 512, 512), (1001, 1024, 320), (333, 36, 512), (16384, 1024, 2048)])
+@pytest.mark.parametrize('M,N,K', [(64, 16, 64), (4096, 512, 512), (1001, 1024, 320), (333, 36, 512), (16384, 1024, 2048),
+                                   (4096, 1024, 1024)])         # the last one: dW_ih of the I3D shape (V = 1024)
 def test_gemm_tn_with_exact_bf16_rows(M, N, K):
     """dW = dZ^T X with X stored as bf16 (two products per pair, no lo image of X), plus the bias gradient riding along."""
     from stair_amd import ops
@@ -142,7 +143,7 @@ def test_gemm_tn_with_exact_bf16_rows(M, N, K):
     assert _maxerr(b1, dZ.double().sum(0)) < 4e-5 * max(1.0, (M / 100) ** 0.5)
 
 
-@pytest.mark.parametrize('M,N,K,wide', [(2048, 256, 256, False), (8192, 1024, 2048, True), (16384, 256, 256, False), (16384, 1024, 2048, True), (32768, 512, 256, True), (17408, 256, 512, False),
+@pytest.mark.parametrize('M,N,K,wide', [(2048, 256, 256, False), (8192, 1024, 2048, True), (4096, 1024, 1024, True), (16384, 256, 256, False), (16384, 1024, 2048, True), (32768, 512, 256, True), (17408, 256, 512, False),
                                         (131072, 1024, 2048, True)])       # the last one is the bench shape: 512 stages per slab
 def test_gemm_tn_transposed_read_kernel(M, N, K, wide):
     """The dW_ih shapes (M a multiple of 512 and >= 2048, N and K multiples of 256, no bias sum riding along) go to

@@ -15,7 +15,7 @@ HBM_PEAK_GBS = 8000.0
 ALIASES = {'mask_relu_kernel': ('mask_relu_kernel', 'mask_relu_v4_kernel'),
            'bcast_mask_relu_kernel': ('bcast_mask_relu_kernel', 'bcast_mask_relu_v4_kernel'),
            'sum_rows_kernel': ('sum_rows_kernel', 'sum_rows_v4_kernel'),
-           'layernorm_bwd_kernel+param_grad': ('layernorm_bwd_kernel', 'layernorm_param_grad_kernel', 'layernorm_bwd_fused_kernel')}
+           'layernorm_bwd_kernel+param_grad': ('layernorm_bwd_kernel', 'layernorm_param_grad_kernel')}       # (H = 256, 512: layernorm_bwd_fused_kernel, under its own name)
 
 
 def run(out):
