@@ -548,8 +548,10 @@ int stair_plan_build_shared(stair_ctx *ctx, int32_t n, const int32_t *prog_off, 
  * padding behind; every [T,H] map and [T] attention row keeps the stride T.  Each question is computed as the reference
  * computes a clip of ITS length: the LSTM runs video_len steps, Filter sums, Relate's softmax, Superlative's pooling (and
  * its action count when the actions are a map), the Conv1d Temporal nets ('same' zero padding at the clip's own end) and
- * the attention criterion see exactly video_len frames; padded frames of map outputs hold finite don't-care values and
- * padded attention frames of Temporal / Relate outputs are zero.  Needs the Conv1d Temporal configuration
+ * the attention criterion see exactly video_len frames.  The operators compute whole [T,H] tiles and [T] rows; when the
+ * program levels have run, the padded frames of every node's map / attention output are set to zero (they hold finite
+ * don't-care values while the levels run; those of Temporal's related attention and of Relate are zero throughout).
+ * Needs the Conv1d Temporal configuration
  * (max_video_length > 32).  video_len == NULL: every clip has T frames (== stair_plan_build_shared). */
 int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
                             const int32_t *span_lo, const int32_t *span_hi, const int32_t *q_off,

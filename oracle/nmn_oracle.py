@@ -6,7 +6,23 @@ product path (stair_amd/) never does and fails loudly when the HIP library is mi
 What it restates: the stack interpreter of /root/reference/video_nmn/module_net.py:65-145 and the
 eighteen operators of /root/reference/video_nmn/modules.py, as plain functions over a
 {state_dict_key: tensor} weight dict, batch-1, fp32, same operation order as the reference, dropout
-in eval mode (identity).  Each function cites the reference lines it follows.
+in eval mode (identity) unless a ``dropout=`` callable is given: it is then called as ``dropout(site, y)``
+at every position where the reference has an nn.Dropout in a module that VideoNMN registers, and its
+return value replaces y (the caller decides the mask and the 1 / (1 - p) factor; ``site`` names the Linear
+the Dropout follows, e.g. 'Filter.param.objects.3', 'Temporal.dense.0', 'decoder.0').  The positions:
+
+    ToAction     param.0                        modules.py:106
+    HasItem      param.0, param.3 (sigmoid)     modules.py:127-128
+    Exists       param.0, param.3               modules.py:145-146
+    Localize     video_linear.0                 modules.py:188   (Superlative runs the same Localize: :226, :243)
+    Temporal     dense.0, before the LayerNorm  modules.py:281, :326-327
+    Filter       param.<kw>.0, .3               modules.py:348-349
+    FilterFrame  param.<kw>.0, .3, dense.0      modules.py:385-386, :393
+    decoder      decoder.0                      module_net.py:51
+
+and none at Superlative.dense (:229) or Filter.dense (:357), whose Dropout is commented out, nor in Compare,
+Equals, Xor (:18, :27, :62).  QueryModule (:83-99) has one but VideoNMN never registers it (NAME_TO_MODULE).
+Each function cites the reference lines it follows.
 
 Pinning: tests/golden/*.npz hold outputs of the reference itself (imported on CPU in the build
 container by tests/golden/make_golden.py, which is committed); tests/test_oracle_golden.py checks
@@ -112,10 +128,21 @@ def cos_rows(a, b, eps=1e-8):
     return (an * bn).sum(-1)
 
 
-def _mlp2(w, prefix, x, relu_last=True):
-    """Lin . ReLU . (Dropout) . Lin [. ReLU . (Dropout)] -- the '.0' / '.3' Sequential pattern."""
-    y = _lin(w, prefix + '.3', torch.relu(_lin(w, prefix + '.0', x)))
-    return torch.relu(y) if relu_last else y
+def _drop(dropout, site, y):
+    """nn.Dropout at `site` (the state_dict prefix of the Linear it follows, without 'submodules.'): identity in
+    eval mode (dropout=None), else whatever the caller's hook makes of y."""
+    return y if dropout is None else dropout(site[len(P):] if site.startswith(P) else site, y)
+
+
+def _mlp2(w, prefix, x, relu_last=True, dropout=None, drop_last=False):
+    """Lin . ReLU . Dropout . Lin [. ReLU [. Dropout]] -- the '.0' / '.3' Sequential pattern; drop_last: the
+    Sequential ends in a Dropout (Exists, Filter.param, FilterFrame.param), else it does not (ToAction, Localize)."""
+    h = _drop(dropout, prefix + '.0', torch.relu(_lin(w, prefix + '.0', x)))
+    y = _lin(w, prefix + '.3', h)
+    if not relu_last:
+        return y
+    y = torch.relu(y)
+    return _drop(dropout, prefix + '.3', y) if drop_last else y
 
 
 def op_and(a, b):                      # modules.py:7-12
@@ -144,33 +171,34 @@ def op_xor(w, a, b):                   # modules.py:59-72
     return torch.relu(_lin(w, P + 'Xor.param.0', torch.cat([(a - b).abs(), a, b])))
 
 
-def op_toaction(w, action, kw):        # modules.py:102-120
-    return _mlp2(w, P + 'ToAction.param', torch.cat([action, kw]))
+def op_toaction(w, action, kw, dropout=None):        # modules.py:102-120 (D behind param.0 only: :106-107)
+    return _mlp2(w, P + 'ToAction.param', torch.cat([action, kw]), dropout=dropout)
 
 
-def op_hasitem(w, feat):               # modules.py:123-138
-    y = _lin(w, P + 'HasItem.param.3', torch.relu(_lin(w, P + 'HasItem.param.0', feat)))
-    return torch.sigmoid(y).squeeze()
+def op_hasitem(w, feat, dropout=None):               # modules.py:123-138 (D behind the ReLU :127 and behind the Sigmoid :128)
+    h = _drop(dropout, P + 'HasItem.param.0', torch.relu(_lin(w, P + 'HasItem.param.0', feat)))
+    y = _lin(w, P + 'HasItem.param.3', h)
+    return _drop(dropout, P + 'HasItem.param.3', torch.sigmoid(y)).squeeze()
 
 
-def op_exists(w, kw, feat):            # modules.py:141-159
-    return _mlp2(w, P + 'Exists.param', torch.cat([feat, kw, feat * kw]))
+def op_exists(w, kw, feat, dropout=None):            # modules.py:141-159 (D behind both ReLUs: :145-146)
+    return _mlp2(w, P + 'Exists.param', torch.cat([feat, kw, feat * kw]), dropout=dropout, drop_last=True)
 
 
 def op_existsframe(kw, feat):          # modules.py:162-178
     return (cos_rows(feat, kw.unsqueeze(0)) + 1) * 0.49
 
 
-def op_localize(w, feat, kw):          # modules.py:181-217
-    f = _mlp2(w, P + 'Localize.video_linear', feat, relu_last=False)          # [T,H]
+def op_localize(w, feat, kw, dropout=None):          # modules.py:181-217 (D behind video_linear.0's ReLU: :188)
+    f = _mlp2(w, P + 'Localize.video_linear', feat, relu_last=False, dropout=dropout)          # [T,H]
     if kw.dim() == 1:
         kw = kw.unsqueeze(0)
     k = _lin(w, P + 'Localize.keyword_linear.0', kw)                          # [K,H]
     return (cos_rows(f.unsqueeze(0), k.unsqueeze(1)) + 1) * 0.49              # [K,T]
 
 
-def op_superlative(w, mode, actions, feat):        # modules.py:220-248
-    s = op_localize(w, feat, actions)                                         # [Ka,T]
+def op_superlative(w, mode, actions, feat, dropout=None):        # modules.py:220-248 (no D behind dense.0: commented out at :229)
+    s = op_localize(w, feat, actions, dropout)                                # [Ka,T]  (:243: Localize with its own D)
     wt = torch.softmax(s.sum(dim=1), dim=0)
     if mode == 'min':
         wt = 1 - wt
@@ -200,9 +228,9 @@ def temporal_relate(w, mode, a):
     return torch.sigmoid(_lin(w, pre + '4', y))
 
 
-def op_temporal(w, mode, feat, attn):              # modules.py:310-327
+def op_temporal(w, mode, feat, attn, dropout=None):              # modules.py:310-327 (D behind dense.0's ReLU, :281, before the LayerNorm :327)
     r = temporal_relate(w, mode, attn.mean(dim=0))
-    y = torch.relu(_lin(w, P + 'Temporal.dense.0', r.unsqueeze(-1) * feat))
+    y = _drop(dropout, P + 'Temporal.dense.0', torch.relu(_lin(w, P + 'Temporal.dense.0', r.unsqueeze(-1) * feat)))
     out = F.layer_norm(y, (y.shape[-1],), w[P + 'Temporal.layer_norm.weight'],
                        w[P + 'Temporal.layer_norm.bias'], 1e-5)
     return out, r
@@ -212,26 +240,26 @@ def op_attnvideo(feat, attn):          # modules.py:330-340
     return attn.unsqueeze(1) * feat
 
 
-def op_filter(w, feat, kw):            # modules.py:343-378
+def op_filter(w, feat, kw, dropout=None):            # modules.py:343-378 (D behind param.<kw>.0 and .3, :348-349; none behind dense.0, :357)
     if isinstance(kw, torch.Tensor):
-        f = _mlp2(w, P + 'Filter.param.representation', feat)
+        f = _mlp2(w, P + 'Filter.param.representation', feat, dropout=dropout, drop_last=True)
         fk = torch.cat([f, kw.unsqueeze(0).expand(f.shape[0], -1)], dim=1)
         # nn.Softmax() with no dim on a [T,1] tensor resolves to dim=1 -> every score is exactly 1
         a = torch.softmax(_lin(w, P + 'Filter.attention.0', fk), dim=1)
         agg = (a * f).sum(0)
     else:
-        agg = _mlp2(w, P + 'Filter.param.' + kw, feat).sum(0)
+        agg = _mlp2(w, P + 'Filter.param.' + kw, feat, dropout=dropout, drop_last=True).sum(0)
     return torch.relu(_lin(w, P + 'Filter.dense.0', agg))
 
 
-def op_filterframe(w, feat, kw):       # modules.py:381-414
+def op_filterframe(w, feat, kw, dropout=None):       # modules.py:381-414 (D behind param.<kw>.0 and .3, :385-386, and behind dense.0, :393)
     if isinstance(kw, torch.Tensor):
-        f = _mlp2(w, P + 'FilterFrame.param.representation', feat)
+        f = _mlp2(w, P + 'FilterFrame.param.representation', feat, dropout=dropout, drop_last=True)
         fk = torch.cat([f, kw.unsqueeze(0).expand(f.shape[0], -1)], dim=1)
         agg = torch.sigmoid(_lin(w, P + 'FilterFrame.attention.0', fk)) * f
     else:
-        agg = _mlp2(w, P + 'FilterFrame.param.' + kw, feat)
-    return torch.relu(_lin(w, P + 'FilterFrame.dense.0', agg))
+        agg = _mlp2(w, P + 'FilterFrame.param.' + kw, feat, dropout=dropout, drop_last=True)
+    return _drop(dropout, P + 'FilterFrame.dense.0', torch.relu(_lin(w, P + 'FilterFrame.dense.0', agg)))
 
 
 def op_relate(w, mode, attn):          # modules.py:417-435 (nn.Softmax() on 1-D -> dim 0)
@@ -254,8 +282,8 @@ def pretrain_head(w, prog, result, related_attn=None):
     raise AttributeError('%s has no pretrain_head' % prog)     # torch raises AttributeError too
 
 
-def run_module(w, prog, params):
-    """Dispatch one module call; returns (result, related_attn or None)."""
+def run_module(w, prog, params, dropout=None):
+    """Dispatch one module call; returns (result, related_attn or None).  dropout: see the module docstring."""
     if prog == 'And':
         return op_and(*params), None
     if prog == 'XorFrame':
@@ -269,25 +297,25 @@ def run_module(w, prog, params):
     if prog == 'Xor':
         return op_xor(w, *params), None
     if prog == 'ToAction':
-        return op_toaction(w, *params), None
+        return op_toaction(w, *params, dropout=dropout), None
     if prog == 'HasItem':
-        return op_hasitem(w, *params), None
+        return op_hasitem(w, *params, dropout=dropout), None
     if prog == 'Exists':
-        return op_exists(w, *params), None
+        return op_exists(w, *params, dropout=dropout), None
     if prog == 'ExistsFrame':
         return op_existsframe(*params), None
     if prog == 'Localize':
-        return op_localize(w, *params), None
+        return op_localize(w, *params, dropout=dropout), None
     if prog == 'Superlative':
-        return op_superlative(w, *params), None
+        return op_superlative(w, *params, dropout=dropout), None
     if prog == 'Temporal':
-        return op_temporal(w, *params)
+        return op_temporal(w, *params, dropout=dropout)
     if prog == 'AttnVideo':
         return op_attnvideo(*params), None
     if prog == 'Filter':
-        return op_filter(w, *params), None
+        return op_filter(w, *params, dropout=dropout), None
     if prog == 'FilterFrame':
-        return op_filterframe(w, *params), None
+        return op_filterframe(w, *params, dropout=dropout), None
     if prog == 'Relate':
         return op_relate(w, *params), None
     if prog == 'Array2':
@@ -299,8 +327,9 @@ def run_module(w, prog, params):
 # interpreter  (module_net.py:65-145)
 # ------------------------------------------------------------------------------------------
 def forward(w, config, data, return_res_by_step=True, return_result_of_each_step=False,
-            pretrain_modules=frozenset(), explicit_lstm=False):
-    """VideoNMN.forward restated.  ``data`` as in dataset.py:191-233 (tensors or ndarrays)."""
+            pretrain_modules=frozenset(), explicit_lstm=False, dropout=None):
+    """VideoNMN.forward restated.  ``data`` as in dataset.py:191-233 (tensors or ndarrays).  dropout: None is model.eval();
+    a callable (site, y) -> y stands for every nn.Dropout of model.train() (module docstring)."""
     question = torch.as_tensor(data['question'])
     video = torch.as_tensor(data['video_features'])
     spans = data['prog_str_to_question_tokens']
@@ -319,7 +348,7 @@ def forward(w, config, data, return_res_by_step=True, return_result_of_each_step
                 if isinstance(p, str) and p == 'video':
                     p = video_feat
                 params.append(p)
-            result, rel = run_module(w, prog, params)
+            result, rel = run_module(w, prog, params, dropout=dropout)
             want_head = config['have_pretrain_head'] and prog in pretrain_modules
             if return_res_by_step and program_idx[i] is not None and prog in pretrain_modules and i != 0:
                 res_by_step[program_idx[i]] = (prog, pretrain_head(w, prog, result, rel) if config['have_pretrain_head'] else result)
@@ -339,7 +368,7 @@ def forward(w, config, data, return_res_by_step=True, return_result_of_each_step
     assert len(stack) == 1                                          # module_net.py:135
     hidden = stack[0]
     hq = torch.cat([hidden, question_feature])
-    logits = _lin(w, P + 'decoder.3', torch.relu(_lin(w, P + 'decoder.0', hq)))
+    logits = _lin(w, P + 'decoder.3', _drop(dropout, P + 'decoder.0', torch.relu(_lin(w, P + 'decoder.0', hq))))   # module_net.py:50-53
     ret = {'logits': logits, 'res_by_step': res_by_step,
            'video_feat': video_feat, 'token_feature': token_feature, 'question_feature': question_feature}
     if return_result_of_each_step:

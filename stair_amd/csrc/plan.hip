@@ -244,6 +244,14 @@ __global__ void queue_probe_kernel(unsigned *counter, unsigned *seen, int total,
     }
 }
 
+// Plans with clips of different lengths: the frames behind a clip's end of every [T, H] map and [T] attention row a program node
+// owns are set to zero when the levels have run (the operators compute whole tiles; their consumers read the clip's own frames only).
+// pairs = (row, frames) per entry; a block per entry; the row holds T frames of `rowlen` floats.
+__global__ void zero_pad_frames_kernel(float *base, const int32_t *pairs, int T, int rowlen) {
+    const int row = pairs[2 * blockIdx.x], L = pairs[2 * blockIdx.x + 1];
+    float *p = base + (int64_t)row * T * rowlen;
+    for (int i = L * rowlen + threadIdx.x; i < T * rowlen; i += blockDim.x) p[i] = 0.0f;
+}
 
 constexpr int OP_SPAN = 50;      // pseudo op: span mean (level 0)
 const int kArity[STAIR_OP_COUNT] = {2, 2, 3, 2, 2, 2, 2, 2, 2, 1, 2, 2, 3, 3, 2, 2, 2, 2};
@@ -512,6 +520,8 @@ struct stair_plan {
     bool ragged = false;            // clips of different frame counts in this batch (padded to T; per-instance lengths in col[6])
     bool bits_written = false;      // the last forward run of this (training) plan went through the fused tile operators: Bucket::bit* are valid
     std::vector<int32_t> vlen;      // frames per clip [n_vid]
+    std::vector<int32_t> pad_map, pad_att;      // ragged plans: (map tile | att row, frames) of every node output of a short clip
+    int64_t off_pad_map = 0, off_pad_att = 0;
     int n_vec = 0, n_map = 0, n_att = 0, n_aliased = 0;     // n_aliased: nodes that share another node's value (common subexpressions)
     int maxI = 0, maxV = 0, maxK = 0, maxSupRows = 0, n_levels = 0;
     // deterministic gradient fan-in (training plans): staging slots behind the gradient arenas and, per producer level, the table of
@@ -1152,6 +1162,8 @@ int build_index_image(stair_plan *pl, const int32_t *q_off) {
         pl->off_seqt = push(st);
         pl->off_roots = push(pl->roots);
         pl->off_lenv = push(pl->vlen);
+        pl->off_pad_map = push(pl->pad_map);
+        pl->off_pad_att = push(pl->pad_att);
     }
     std::vector<int32_t *> vec_fix;
     if (pl->train) {
@@ -1512,6 +1524,18 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     if (int rc = interpret_programs(pl, prog_off, tokens, span_lo, span_hi, q_off, video_of_question, !(flags & STAIR_PLAN_NO_CSE))) return rc;
     if (pl->train)
         if (int rc = check_backward_limits(pl, ctx)) return rc;
+    if (pl->ragged)         // the node outputs of questions about a short clip: their frames behind the clip's end are zeroed after the levels
+        for (int q = 0; q < n; ++q) {
+            const int L = pl->vlen[video_of_question ? video_of_question[q] : q];
+            if (L == T) continue;
+            for (int t = prog_off[q]; t < prog_off[q + 1]; ++t) {
+                const Node &nd = pl->nodes[t];
+                if (nd.kind == STAIR_VAL_MAP && nd.slot >= n_videos && nd.slot < pl->n_map) { pl->pad_map.push_back(nd.slot); pl->pad_map.push_back(L); }
+                const int rows = nd.kind == STAIR_VAL_ATT ? nd.aux : nd.kind == STAIR_VAL_FRAME ? 1 : 0;
+                for (int r = 0; r < rows; ++r)
+                    if (nd.slot + r >= 0 && nd.slot + r < pl->n_att) { pl->pad_att.push_back(nd.slot + r); pl->pad_att.push_back(L); }
+            }
+        }
     if (int rc = build_index_image(pl, q_off)) return rc;
     if (int rc = layout_workspace(pl, ctx)) return rc;
     if (plan_debug())
@@ -2289,6 +2313,16 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
             for (size_t k = lo_; k < hi_; ++k) RUN(run_bucket(pl->buckets[k], (int)k, 2));
             lo_ = hi_;
         }
+    }
+
+    // ---- clips of different lengths: zero frames behind a clip's end in every node's map / attention rows ----
+    if (!pl->pad_map.empty()) {
+        hipLaunchKernelGGL(zero_pad_frames_kernel, dim3((unsigned)(pl->pad_map.size() / 2)), dim3(256), 0, s, map, didx + pl->off_pad_map, T, H);
+        STAIR_LAUNCH_CHECK();
+    }
+    if (!pl->pad_att.empty()) {
+        hipLaunchKernelGGL(zero_pad_frames_kernel, dim3((unsigned)(pl->pad_att.size() / 2)), dim3(64), 0, s, att, didx + pl->off_pad_att, T, 1);
+        STAIR_LAUNCH_CHECK();
     }
 
     // ---- decoder (module_net.py:136-138) -----------------------------------------------------

@@ -94,3 +94,191 @@ def window_weights(z, meta, window_no, name, tensor):
         t = t[::meta['stride_large']]
     assert t.shape == ref.shape, (name, t.shape, ref.shape)
     return ref, t
+
+
+class _ForcedMasks:
+    """Runs the oracle with the ReLU masks of ANOTHER implementation in its backward pass.
+
+    A ReLU's derivative is 0 or 1 on either side of a kink; two correct implementations whose pre-activations differ by
+    rounding pick different sides for the few inputs that lie within that rounding of zero, and the gradient is discontinuous
+    there (test_bf16_feature_step_at_full_size_gradients_and_adam counts them).  Here the oracle keeps its own forward values
+    but differentiates every module / decoder ReLU with the mask the HIP pass used (its saved activation > 0,
+    stair_plan_saved_offset) -- a valid sub-gradient of the same function wherever the two agree in sign, i.e. everywhere but
+    at those kinks -- so what is left between the two gradients is arithmetic, and the strict elementwise bound applies.
+    The relus of Temporal's tiny relate nets ([T]-sized, recomputed by the HIP backward kernel, not saved) keep the oracle's
+    own masks.
+
+    Dropout-aware form (p = the nn.Dropout probability of a pass run with dropout=(p, seed)): a dropped element is an exact zero
+    of a tensor the training plan exposes, so the keep mask C the kernels used is read back -- C = (HIP's post-dropout
+    activation != 0) -- and handed to the oracle through its dropout hook (`self.hook`, oracle/nmn_oracle.py `dropout=`).  At a
+    ReLU + Dropout site the oracle then computes clamp_min(z, 0) * C / (1 - p), backward g * C / (1 - p).  Where C comes from:
+    saved(q, i, 0 / 1) for the tile MLP layers, the Exists / ToAction hidden rows and Temporal's pre-LayerNorm rows;
+    saved(q, None) for the decoder's hidden row; node(q, i) where the site is the node's output (Exists .3, FilterFrame's dense
+    layer, HasItem's sigmoid -- never 0 itself, so there the mask is exact).  Clips shorter than the batch's longest: the first
+    rows of a saved tile / attention row are the clip's.  Collected on the way:
+      sites, flips     ReLU sites compared and disagreements.  Plain sites: (z > 0) != mask.  ReLU + Dropout sites: C set where the
+                       oracle's z <= 0 (the other side is what dropout does)
+      kept[kind]       [entries whose oracle pre-activation is positive by more than `bound(ref)`, those of them with C set]
+      plain_zero[kind] exact zeros at outputs the reference does NOT drop, where the oracle's value is positive beyond the bound
+      record[(i, k)]   (C, positive-beyond-bound) of dropout call k of token i ('decoder': the decoder's), for mask statistics"""
+
+    class _Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, z, mask):
+            ctx.save_for_backward(mask)
+            return z.clamp_min(0)
+
+        @staticmethod
+        def backward(ctx, g):
+            (mask,) = ctx.saved_tensors
+            return g * mask, None
+
+    def __init__(self, res, qi, program, p=None):
+        self.res, self.qi, self.program, self.p = res, qi, program, p
+        self.order = [i for i in range(len(program) - 1, -1, -1) if program[i] in O.ARITY]      # the interpreter's module calls
+        self.queue, self.flips, self.sites = [], 0, 0
+        self.dqueue, self.kept, self.plain_zero, self.record = [], {}, {}, {}
+        self.token = None
+
+    @staticmethod
+    def bound(ref):
+        """the forward bound of the node comparisons: 2e-5 * max(1, max|ref|)"""
+        return 2e-5 * max(1.0, float(ref.detach().abs().max())) if ref.numel() else 2e-5
+
+    @staticmethod
+    def _fit(m, shape):
+        """a [T, H] tile or [T] row of the launch batch cut to the clip's own frames"""
+        if m.numel() != int(np.prod(shape)):
+            m = m.reshape(-1, shape[-1])[:shape[0]] if len(shape) == 2 else m.reshape(-1)[:shape[-1]]
+        return m.reshape(shape)
+
+    def _masks_for(self, i):
+        """the ReLU masks of token i's module call in the order the oracle calls torch.relu: None (the oracle's own), a mask, or
+        under dropout (mask, kind) for a ReLU the reference follows with an nn.Dropout; and the dropout calls it must make"""
+        prog, res, qi, drop = self.program[i], self.res, self.qi, self.p is not None
+        sv = lambda which: res.saved(qi, i, which).detach().cpu() > 0
+        out = lambda: res.node(qi, i).detach().cpu() > 0
+        if drop:              # a dropped element is an exact zero; anything else was kept (a negative value would count as a flip)
+            sv = lambda which: res.saved(qi, i, which).detach().cpu() != 0
+            out = lambda: res.node(qi, i).detach().cpu() != 0
+        D = (lambda m, kind: (m, prog + '.' + kind)) if drop else (lambda m, kind: m)
+        plain = (lambda m: (m, None)) if drop else (lambda m: m)
+        if prog == 'Filter':
+            relus, sites = [D(sv(0), 'param.0'), D(sv(1), 'param.3'), plain(out())], ['Filter.param.*.0', 'Filter.param.*.3']
+        elif prog == 'FilterFrame':
+            relus = [D(sv(0), 'param.0'), D(sv(1), 'param.3'), D(out(), 'dense.0')]
+            sites = ['FilterFrame.param.*.0', 'FilterFrame.param.*.3', 'FilterFrame.dense.0']
+        elif prog == 'HasItem':
+            relus, sites = [D(sv(0), 'param.0')], ['HasItem.param.0', 'HasItem.param.3']
+        elif prog == 'Localize':
+            relus, sites = [D(sv(0), 'video_linear.0')], ['Localize.video_linear.0']
+        elif prog == 'Superlative':
+            relus, sites = [D(sv(0), 'localize.0'), plain(out())], ['Localize.video_linear.0']
+        elif prog == 'Temporal':
+            mode = self.program[i + 1]
+            relus, sites = ([None, None] if mode != 'while' else []) + [D(sv(0), 'dense.0')], ['Temporal.dense.0']
+        elif prog == 'Exists':
+            relus, sites = [D(sv(0), 'param.0'), D(out(), 'param.3')], ['Exists.param.0', 'Exists.param.3']
+        elif prog == 'ToAction':
+            relus, sites = [D(sv(0), 'param.0'), plain(out())], ['ToAction.param.0']
+        elif prog in ('Xor', 'Equals', 'Compare'):
+            relus, sites = [plain(out())], []
+        else:
+            relus, sites = [], []
+        return relus, (sites if drop else [])
+
+    def _count(self, kind, pos, m):
+        k = self.kept.setdefault(kind, [0, 0])
+        k[0] += int(pos.sum())
+        k[1] += int((pos & m).sum())
+
+    def __enter__(self):
+        self._relu, self._run = torch.relu, O.run_module
+
+        def relu(z):
+            if not self.queue:
+                return self._relu(z)
+            m = self.queue.pop(0)
+            if m is None:
+                return self._relu(z)
+            kind = plain_site = None
+            if isinstance(m, tuple):                      # dropout-aware form
+                m, kind = m
+                plain_site = kind is None
+            m = self._fit(m, z.shape)
+            self.sites += m.numel()
+            zd = z.detach()
+            if kind is not None:
+                self.flips += int((m & (zd <= 0)).sum())
+                pos = zd > self.bound(zd.clamp_min(0))
+                self._count(kind, pos, m)
+                self._pending = (m, pos, kind)
+            else:
+                self.flips += int(((zd > 0) != m).sum())
+                if plain_site:
+                    name = self.program[self.token] if self.token != 'decoder' else 'decoder'
+                    self.plain_zero[name] = self.plain_zero.get(name, 0) + int((~m & (zd > self.bound(zd.clamp_min(0)))).sum())
+            return self._Fn.apply(z, m.to(z.dtype))
+
+        def run_module(w, prog, params, dropout=None):
+            i = self.order.pop(0)
+            assert self.program[i] == prog
+            self.token, self._ordinal, self._pending = i, 0, None
+            self.queue, self.dqueue = self._masks_for(i)
+            r = self._run(w, prog, params, dropout=dropout)
+            assert not self.queue, (prog, len(self.queue))
+            assert not self.dqueue, (prog, 'the oracle made no dropout call at', self.dqueue)
+            return r
+        torch.relu, O.run_module = relu, run_module
+        return self
+
+    def hook(self, site, y):
+        """the oracle's nn.Dropout: y * C / (1 - p) with the keep mask of the HIP pass"""
+        import fnmatch
+        assert self.dqueue, ('the oracle drops at %s, where the plan of token %s exposes no dropout site' % (site, self.token))
+        want = self.dqueue.pop(0)
+        assert fnmatch.fnmatchcase(site, want), (site, want)
+        if site == 'HasItem.param.3':                     # behind the sigmoid: no ReLU, the node's value itself tells
+            m = self._fit(self.res.node(self.qi, self.token).detach().cpu() != 0, y.shape)
+            pos = y.detach() > self.bound(y)
+            self.sites += m.numel()
+            self._count('HasItem.param.3', pos, m)
+        else:
+            assert self._pending is not None, site       # the ReLU in front of this Dropout took a (mask, kind) entry
+            m, pos, _ = self._pending
+            self._pending = None
+        self.record[(self.token, self._ordinal)] = (m, pos)
+        self._ordinal += 1
+        return y * (m.to(y.dtype) / (1.0 - self.p))
+
+    def decoder(self):
+        m = self.res.saved(self.qi, None).detach().cpu()
+        m = m != 0 if self.p is not None else m > 0
+        self.token, self._ordinal, self._pending = 'decoder', 0, None
+        self.queue = [(m, 'decoder.0')] if self.p is not None else [m]
+        self.dqueue = ['decoder.0'] if self.p is not None else []
+
+    def __exit__(self, *exc):
+        torch.relu, O.run_module = self._relu, self._run
+        return False
+
+    def forward(self, w, config, q, **kwargs):
+        """O.forward of question q inside this context, the decoder's mask queued when the interpreter has run every module
+        (its ReLU is the last one of the pass) and, in the dropout-aware form, the hook in place."""
+        orig_lin = O._lin
+
+        def lin(w_, prefix, x):
+            if prefix.endswith('decoder.0'):
+                assert not self.order, self.order
+                self.decoder()
+            return orig_lin(w_, prefix, x)
+        if self.p is not None:
+            kwargs['dropout'] = self.hook
+        with self:
+            O._lin = lin
+            try:
+                r = O.forward(w, config, q, **kwargs)
+            finally:
+                O._lin = orig_lin
+        assert not self.queue and not self.dqueue, (self.queue, self.dqueue)
+        return r

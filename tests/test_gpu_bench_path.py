@@ -11,6 +11,7 @@ import torch
 
 from oracle import nmn_oracle as O
 from stair_amd import spec, synth
+from helpers import _ForcedMasks
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -192,85 +193,6 @@ def test_benched_training_step_matches_oracle_end_to_end():
     assert worst_l2[0] < 2e-2, worst_l2
     assert worst_abs[0] < 0.1, worst_abs
     assert worst_small[0] < 0.1, worst_small
-
-
-class _ForcedMasks:
-    """Runs the oracle with the ReLU masks of ANOTHER implementation in its backward pass.
-
-    A ReLU's derivative is 0 or 1 on either side of a kink; two correct implementations whose pre-activations differ by
-    rounding pick different sides for the few inputs that lie within that rounding of zero, and the gradient is discontinuous
-    there (test_bf16_feature_step_at_full_size_gradients_and_adam counts them).  Here the oracle keeps its own forward values
-    but differentiates every module / decoder ReLU with the mask the HIP pass used (its saved activation > 0,
-    stair_plan_saved_offset) -- a valid sub-gradient of the same function wherever the two agree in sign, i.e. everywhere but
-    at those kinks -- so what is left between the two gradients is arithmetic, and the strict elementwise bound applies.
-    The relus of Temporal's tiny relate nets ([T]-sized, recomputed by the HIP backward kernel, not saved) keep the oracle's
-    own masks."""
-
-    class _Fn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, z, mask):
-            ctx.save_for_backward(mask)
-            return z.clamp_min(0)
-
-        @staticmethod
-        def backward(ctx, g):
-            (mask,) = ctx.saved_tensors
-            return g * mask, None
-
-    def __init__(self, res, qi, program):
-        self.res, self.qi, self.program = res, qi, program
-        self.order = [i for i in range(len(program) - 1, -1, -1) if program[i] in O.ARITY]      # the interpreter's module calls
-        self.queue, self.flips, self.sites = [], 0, 0
-
-    def _masks_for(self, i):
-        prog, res, qi = self.program[i], self.res, self.qi
-        sv = lambda which: res.saved(qi, i, which).detach().cpu() > 0
-        out = lambda: res.node(qi, i).detach().cpu() > 0
-        if prog in ('Filter', 'FilterFrame'):
-            return [sv(0), sv(1), out()]
-        if prog in ('HasItem', 'Localize'):
-            return [sv(0)]
-        if prog == 'Superlative':
-            return [sv(0), out()]
-        if prog == 'Temporal':
-            mode = self.program[i + 1]
-            return ([None, None] if mode != 'while' else []) + [sv(0)]
-        if prog in ('Exists', 'ToAction'):
-            return [sv(0), out()]
-        if prog in ('Xor', 'Equals', 'Compare'):
-            return [out()]
-        return []
-
-    def __enter__(self):
-        self._relu, self._run = torch.relu, O.run_module
-
-        def relu(z):
-            if not self.queue:
-                return self._relu(z)
-            m = self.queue.pop(0)
-            if m is None:
-                return self._relu(z)
-            m = m.reshape(z.shape)
-            self.sites += m.numel()
-            self.flips += int(((z.detach() > 0) != m).sum())
-            return self._Fn.apply(z, m.to(z.dtype))
-
-        def run_module(w, prog, params):
-            i = self.order.pop(0)
-            assert self.program[i] == prog
-            self.queue = self._masks_for(i)
-            r = self._run(w, prog, params)
-            assert not self.queue, (prog, len(self.queue))
-            return r
-        torch.relu, O.run_module = relu, run_module
-        return self
-
-    def decoder(self):
-        self.queue = [self.res.saved(self.qi, None).detach().cpu() > 0]
-
-    def __exit__(self, *exc):
-        torch.relu, O.run_module = self._relu, self._run
-        return False
 
 
 def test_full_size_gradients_are_strict_given_the_same_relu_masks():

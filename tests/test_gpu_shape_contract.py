@@ -254,9 +254,9 @@ def _strict_misses(names, got, grads):
 
 def _gradients_through_hip_masks(config, qs, res):
     """The oracle's gradients with every module / decoder ReLU differentiated through the mask the HIP forward pass produced
-    (tests/test_gpu_bench_path.py::_ForcedMasks, as test_full_size_gradients_are_strict_given_the_same_relu_masks does), and the
+    (tests/helpers.py::_ForcedMasks, as test_full_size_gradients_are_strict_given_the_same_relu_masks does), and the
     number of sites at which the two implementations' masks differ."""
-    from test_gpu_bench_path import _ForcedMasks
+    from helpers import _ForcedMasks
     res._ws.copy_(res.forward_ws)
     names = [n for n, _ in spec.weight_table(config)]
     weights = synth.make_weights(config, 1)
