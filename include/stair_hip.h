@@ -312,7 +312,14 @@ int stair_lstm_bidir_bwd(const stair_lstm_bwd_args *args, stair_stream stream);
  *     ROWDOT_SIGMOID  out[o * out_gstride + t] = sigmoid(vw . F[t] + vb[0] + (extra ? extra[i] : 0))
  *     LAYERNORM       out + o * out_gstride <- LayerNorm_H(F) * gamma + beta, eps = ln_eps, biased variance
  *     ACCUMULATE      out + o * out_gstride += F (atomic)
- * Rows t >= T of a tile do not exist (nothing is read or written there). */
+ * Rows t >= T of a tile do not exist (nothing is read or written there).
+ * Packed tiles (stair_set_tile_pack, on by default): when T <= 32 a workgroup's 64-row tile holds P = 64 / T instances of the bucket
+ * -- tile w = instances P w .. min(P w + P, cnt) - 1, row R = frame R % T of instance P w + R / T -- and a bucket of cnt instances
+ * is ceil(cnt / P) work items.  The arguments do not change: cnt counts instances, every [cnt, T, H] buffer keeps its layout, every
+ * index array and len / extra / pair_first / pair_cnt / STAIR_TILE_STORE_FIRST stays per instance.  Results are those of the
+ * unpacked launch bit for bit, except dgamma / dbeta of a ln_bwd chain (float sums over a TILE's rows before they reach the
+ * fixed-point accumulators: reproducible from run to run, but grouped differently).  Only save_bits / act_bits / in_bits change
+ * meaning: they are indexed by TILE (see below), so a chain must run with the packing of the forward launch that wrote its bits. */
 enum stair_tile_tail { STAIR_TILE_NONE = 0, STAIR_TILE_STORE = 1, STAIR_TILE_SUM_ROWS = 2, STAIR_TILE_COSINE = 3,
                        STAIR_TILE_ROWDOT_SIGMOID = 4, STAIR_TILE_LAYERNORM = 5, STAIR_TILE_ACCUMULATE = 6,
                        STAIR_TILE_STORE_ROWS = 7, STAIR_TILE_ROWSCALE_ADJ = 8 };
@@ -371,9 +378,10 @@ typedef struct stair_tile_mlp_args {
 #define STAIR_TILE_STORE_FIRST 0x40000000
     /* relu' of a saved activation as ONE bit per element (4 KB per tile instead of a 128 KB read in the backward chain):
      *   save_bits[l]     [cnt][512] 64-bit words, written by a forward launch: word (i, 64 w + c), byte j, bit e = (layer l's
-     *                    activation of tile i, row w + 8 j, column 8 c + e) > 0
+     *                    activation of TILE i, row w + 8 j, column 8 c + e) > 0.  Unpacked, tile i is instance i; a packed launch
+     *                    writes the first ceil(cnt / P) tiles' words and row w + 8 j is a row of the packed tile
      *   act_bits[l]      what a chain uses instead of act_mask[l] (act[l] == 3, act_mask[l] == NULL);  in_bits instead of in_mask
-     *                    (both indexed by the instance number i, never through in_mask_idx) */
+     *                    (both indexed by the tile number, never through in_mask_idx) */
     unsigned long long *save_bits[3]; const unsigned long long *act_bits[3]; const unsigned long long *in_bits;
     /* nn.Dropout behind layer l's activation (the `D` positions of modules.py), forward launches, ABI 6: drop_site[l] = 1 + the site of
      * stair_dropout_fwd (0: none); element e = (instance * T + row) * H + column of the launch draws the same bit as stair_dropout_fwd on
@@ -430,6 +438,18 @@ int stair_set_tile_mlp(int32_t on);
  * words that every launch leaves at zero, so eager runs and hipGraph replays need no reset between launches) or by a static round
  * robin (on = 0); on < 0 restores the default (on).  Results are bit-identical either way. */
 int stair_set_tile_queue(int32_t on);
+/* Short clips share a tile: process-wide, on = 1 (default) packs 64 / T instances into a tile whenever T <= 32, on = 0 never packs,
+ * on < 0 restores the default.  A context may override it (value 0 / 1; -1 inherits the process-wide setting), in force like the
+ * options of stair_ctx_set_option -- a switch of its own because the ids of stair_option are closed.  A plan's backward pass runs
+ * with the packing its last forward pass ran with, whatever the switches say by then.
+ * stair_tile_pack_factor: host only, the P a map-level launch of T frames uses under the process-wide setting.
+ * stair_tile_work_items: host-side count of the tile work items (workgroup tiles) enqueued by tile-operator launches since the last
+ * reset (reset != 0 clears it after reading); summed at launch, nothing runs on the device. */
+int stair_set_tile_pack(int32_t on);
+int stair_ctx_set_tile_pack(stair_ctx *ctx, int32_t value);
+int stair_ctx_get_tile_pack(const stair_ctx *ctx, int32_t *value);
+int32_t stair_tile_pack_factor(int32_t T);
+int stair_tile_work_items(int64_t *items, int32_t reset);
 /* W [N, K] fp32 row-major -> planes: [N/32][K/16][hi, lo][64 lanes][8 bf16] (2 * N * K * 2 bytes, 16-byte aligned);
  * N % 32 == 0, K % 16 == 0.  transpose != 0: W is stored [K, N] and the planes are those of W^T (backward chains). */
 int stair_pack_wfrag(const float *W, void *planes, int32_t N, int32_t K, int32_t transpose, stair_stream stream);

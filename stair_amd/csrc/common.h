@@ -92,7 +92,11 @@ extern bool g_acct_on;
 // stair_set_tile_queue, stair_set_tn_slab_min_rows) and the environment give the DEFAULTS; a context may override each of them, and
 // its values are in force on the calling thread for the duration of stair_plan_run / stair_plan_backward on that context (PolicyScope):
 // two contexts of one process -- two GPUs driven from two threads, or two configurations on one GPU -- do not see each other's settings.
-struct Policy { int v[STAIR_OPT_COUNT]; Policy() { for (int &x : v) x = -1; } };       // -1: inherit the process default
+struct Policy {
+    int v[STAIR_OPT_COUNT];
+    int tile_pack = -1;              // stair_ctx_set_tile_pack (a switch of its own: the option ids of stair_option are closed)
+    Policy() { for (int &x : v) x = -1; }
+};       // -1: inherit the process default
 extern thread_local const Policy *tl_policy;
 inline int policy_or(int opt, int dflt) { return tl_policy && tl_policy->v[opt] >= 0 ? tl_policy->v[opt] : dflt; }
 struct PolicyScope {
@@ -161,6 +165,15 @@ int launch_gemm_tn_batch(const stair_gemm_tn_args *a, int n, hipStream_t s);
 int launch_tile_mlp(const stair_tile_mlp_args &a, hipStream_t s);          // csrc/tile_mlp.hip
 int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *counter, hipStream_t s);   // <= 8 buckets, one launch
 bool tile_mlp_usable(int H, int T);
+// short clips packed into one tile (csrc/tile_mlp.hip): the setting in force on this thread, and a scope that pins it -- a plan's
+// backward chains read the relu' bits by TILE number, so they run with the packing of the forward pass that wrote them
+int tile_pack_setting();
+extern thread_local int tl_tile_pack_force;
+struct TilePackForce {
+    int prev;
+    explicit TilePackForce(int v) : prev(tl_tile_pack_force) { tl_tile_pack_force = v; }
+    ~TilePackForce() { tl_tile_pack_force = prev; }
+};
 // csrc/vec_group.hip: the row-wise Linear layers of a program level as one launch
 using VgProblem = stair_vec_problem;
 constexpr int VG_FWD = STAIR_VEC_FWD, VG_ADJ = STAIR_VEC_ADJ;

@@ -519,6 +519,8 @@ struct stair_plan {
     int64_t off_seqv = 0, off_seqt = 0, off_roots = 0, off_lenv = 0;
     bool ragged = false;            // clips of different frame counts in this batch (padded to T; per-instance lengths in col[6])
     bool bits_written = false;      // the last forward run of this (training) plan went through the fused tile operators: Bucket::bit* are valid
+    int tile_pack = 0;              // ... and whether its map-level tiles were packed (tile_pack_setting() of that run): the relu' bits are
+                                    // indexed by TILE, so the backward chains of the plan run with the same packing, whatever the switches say by then
     std::vector<int32_t> vlen;      // frames per clip [n_vid]
     std::vector<int32_t> pad_map, pad_att;      // ragged plans: (map tile | att row, frames) of every node output of a short clip
     int64_t off_pad_map = 0, off_pad_att = 0;
@@ -1944,6 +1946,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
     // epilogues)
     const bool fused = pl->o_wfrag > 0 && tile_mlp_usable(H, T);
     pl->bits_written = fused && pl->train;
+    pl->tile_pack = tile_pack_setting();
     auto WF = [&](int slot) { return static_cast<const void *>(ws + pl->o_wfrag + (int64_t)slot * H * H); };
     const WeightIndex &WIX = weight_index();
     if (fused) {
@@ -2525,6 +2528,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                          float *d_video, float *d_question, int32_t flags, stair_stream stream) {
     STAIR_CHECK(ctx && pl && video && question && workspace && (answers || d_logits_in), "null argument");
     PolicyScope policy_scope(&ctx->policy);
+    TilePackForce tile_pack_scope(pl->tile_pack);          // the packing of the forward pass that wrote the saves and bits
     STAIR_CHECK(pl->train, "plan was not built with STAIR_PLAN_TRAIN");
     // slab products queued by a pass that failed half-way must not be added into THIS pass's buffers: the queue starts empty and
     // is emptied again however this function returns
@@ -3234,6 +3238,16 @@ extern "C" int stair_ctx_set_option(stair_ctx *ctx, int32_t option, int32_t valu
     STAIR_CHECK(option != STAIR_OPT_MATMUL_MODE || value < 0 || value == STAIR_MATMUL_F32 || value == STAIR_MATMUL_BF16X3 || value == STAIR_MATMUL_BF16,
                 "matmul mode must be STAIR_MATMUL_F32, STAIR_MATMUL_BF16X3 or STAIR_MATMUL_BF16");
     ctx->policy.v[option] = value < 0 ? -1 : value;
+    return 0;
+}
+extern "C" int stair_ctx_set_tile_pack(stair_ctx *ctx, int32_t value) {
+    STAIR_CHECK(ctx, "null context");
+    ctx->policy.tile_pack = value < 0 ? -1 : (value != 0);
+    return 0;
+}
+extern "C" int stair_ctx_get_tile_pack(const stair_ctx *ctx, int32_t *value) {
+    STAIR_CHECK(ctx && value, "null argument");
+    *value = ctx->policy.tile_pack;
     return 0;
 }
 extern "C" int stair_ctx_get_option(const stair_ctx *ctx, int32_t option, int32_t *value) {

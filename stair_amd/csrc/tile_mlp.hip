@@ -1,5 +1,6 @@
 // Fused per-clip tile operators: one workgroup carries one [T, H] tile (T <= 64 frames of one module instance, H = 512)
 // through up to three Linear layers and the module's tile-local tail WITHOUT the intermediates leaving the CU.
+// Clips of T <= 32 frames share a tile, 64 / T instances each (the PACK kernel forms; stair_set_tile_pack).
 //
 // Replaces, per module of /root/reference/video_nmn/modules.py, the launch sequences GEMM -> HBM -> GEMM -> HBM -> row kernel:
 //   Localize   (:199-217)  Lin . ReLU . Lin on the tile, then (cos(f_t, k_j) + 1) * 0.49 against the K keyword rows
@@ -25,6 +26,7 @@
 //   * every tail -- coalesced row stores, the sum over frames, cosine / dot products per row, LayerNorm, atomic accumulation
 //     in 256-byte wave-instructions -- reads the staged rows of the last layer.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <utility>
 #include <vector>
@@ -72,6 +74,7 @@ struct TmArg {
     const float *kb; const int32_t *pair_first, *pair_cnt, *att_idx; float *att;
     const int32_t *len;
     int32_t cnt, T, H;
+    int32_t pack;                // instances per tile (packed launches; 1 otherwise) -- sits in what was padding
     const float *act_mask[3]; float act_scale;
     const float *in_mask; int64_t in_mask_gstride; const int32_t *in_mask_idx; float in_scale; int32_t x_broadcast;
     float *save_in;
@@ -90,8 +93,9 @@ struct TmArg {
         };
     };
 };
-static TmArg tm_arg(const stair_tile_mlp_args &a, int kind) {
+static TmArg tm_arg(const stair_tile_mlp_args &a, int kind, int pack) {
     TmArg t = {};
+    t.pack = pack;
     t.X = a.X; t.x_gstride = a.x_gstride; t.x_idx = a.x_idx; t.row_scale = a.row_scale; t.rs_idx = a.rs_idx;
     for (int l = 0; l < 3; ++l) { t.W[l] = a.W[l]; t.bias[l] = a.bias[l]; t.act[l] = a.act[l]; t.save[l] = a.save[l]; t.act_mask[l] = a.act_mask[l]; }
     t.n_layers = a.n_layers; t.mid_rowdot = a.mid_rowdot; t.vw = a.vw; t.vb = a.vb; t.extra = a.extra; t.rs_out = a.rs_out;
@@ -171,10 +175,28 @@ __device__ __forceinline__ int tm_fresh_v(int v) {
 // adjoint on the way in, the row-scale adjoint on the way out); 3: the map-level backward chains (relu' masks on the way in and
 // between the layers, broadcast input, dZ saves, accumulation).  Kernels of their own: what one form needs in registers and code
 // the others do not pay for (one kernel for everything kept 250+ registers live across the tile loop and spilled).
-template <bool NT, int KIND>
+//
+// PACK (forms 0, 2, 3): a tile holds P = 64 / T instances of a bucket whose clips have T <= 32 frames -- tile w = instances
+// P w .. min(P w + P, cnt) - 1, row R of the tile = frame R % T of instance P w + R / T, and a bucket has ceil(cnt / P) work items.
+// Every [cnt, T, H] buffer (save, save_in, act_mask, rs_out, the dropout element number) is then ONE run of rows for the tile, and
+// the MFMA loop does not know: only the indexed lookups (x_idx, rs_idx, in_mask_idx, out_idx, adj_*_idx, extra, len, pair_*) and
+// the tails that reduce over frames see where one instance ends.  What they need per ROW is looked up once per tile by wave 0
+// (lane R = row R) into small LDS tables (pk_*); a row's entry is wave-uniform (row = wave + 8 j), so it is read back into SGPRs.
+// Rows of instances >= cnt and rows >= P T do not exist: their entries point at row 0 of the tile (read, zeroed, never written).
+// The relu' bit masks stay indexed by TILE number: a packed chain reads what the packed forward launch of the same bucket wrote.
+template <bool NT, int KIND, bool PACK = false>
 __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
+    static_assert(!PACK || KIND != 1, "vector-level tiles hold 64 instances already");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float *F = reinterpret_cast<float *>(lds);
+    // per-row tables of a packed tile.  pk_tf: bits 0..5 the frame to READ for the input row (0 where the row is zeroed), 16..21 the
+    // row's frame, TM_PK_LIVE (not zeroed on input) / TM_PK_FIRST (STAIR_TILE_STORE_FIRST of its instance)
+    constexpr int PKN = PACK ? TM_ROWS : 1;
+    __shared__ int pk_tf[PKN], pk_xi[PKN], pk_oi[PKN], pk_len[PKN], pk_mi[PKN], pk_fi[PKN], pk_ri[PKN], pk_pf[PKN], pk_pc[PKN], pk_allfirst;
+    __shared__ float pk_sc[PKN], pk_ex[PKN];
+#define TM_PK_LIVE 0x200
+#define TM_PK_FIRST 0x400
+#define TM_PK_S(arr_, row_) __builtin_amdgcn_readfirstlane((arr_)[row_])
     // KIND 2: d gamma / d beta of the workgroup's tiles, column tid, as 64-bit fixed point (common.h): integer sums do not depend on
     // which workgroup the queue gave which tile, so the parameter gradients are bit-identical from run to run
     __shared__ long long tb_acc[KIND == 2 ? 2 * TM_H : 2];
@@ -226,16 +248,58 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 
         // rows of this tile: the T frames of a module instance, or (vector-level modules) up to 64 INSTANCES of one row each
         const int vpack = KIND == 1 ? p.vec_pack : 0;    // the vector-level form is a kernel of its own (registers)
-        const int T = vpack ? min(TM_ROWS, p.vec_cnt - TM_ROWS * inst) : p.T;
+        // packed tiles: `inst` is the TILE number, pkI0 its first instance, pkN the instances it holds; T = the rows that exist
+        const int pkI0 = PACK ? inst * p.pack : 0;
+        const int pkN = PACK ? min(p.pack, p.cnt - pkI0) : 1;
+        const int T = PACK ? pkN * p.T : (vpack ? min(TM_ROWS, p.vec_cnt - TM_ROWS * inst) : p.T);
         const int Ts = vpack ? TM_ROWS : p.T;            // rows between two tiles in the [cnt, T, H] save / mask buffers
+        // first row of the tile in the [cnt, T, H] buffers
+#define TM_ROWBASE (PACK ? (int64_t)pkI0 * p.T : (int64_t)inst * Ts)
         const int nseg = vpack == 0 ? 1 : (vpack == 1 ? 2 : 3);
-        // ---- the input tile: fp32 rows -> (row scale) -> bf16 hi / lo image ------------------------------------------
-        const float *x = tm_fresh(p.X + (int64_t)(p.x_idx ? __builtin_amdgcn_readfirstlane(p.x_idx[inst]) : inst) * p.x_gstride);
-        const float *rsrow = KIND == 0 && p.row_scale ? p.row_scale + (int64_t)(p.rs_idx ? __builtin_amdgcn_readfirstlane(p.rs_idx[inst]) : inst) * T : nullptr;
-        // (a NULL must stay a visible NULL: through tm_fresh the forward kernel kept the whole mask path, and its registers)
-        const float *imask = (KIND == 2 || KIND == 3) && p.in_mask ? tm_fresh(p.in_mask + (int64_t)(p.in_mask_idx ? __builtin_amdgcn_readfirstlane(p.in_mask_idx[inst]) : inst) * p.in_mask_gstride) : nullptr;
         const bool xbc = KIND == 3 && p.x_broadcast;
-        const int Lrows = xbc ? (p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T) : T;     // a broadcast row fills the clip's own frames only
+        if (PACK) {
+            if (wave == 0) {                             // lane R looks up what row R needs
+                const int R = TM_LANE();
+                const int Tc = p.T;
+                const bool ex = R < T;
+                const int sg = ex ? R / Tc : 0;
+                const int tt = ex ? R - sg * Tc : 0;
+                const int i = pkI0 + sg;                 // < cnt (row 0 of the tile for rows that do not exist)
+                const int ln = p.len ? p.len[i] : Tc;
+                const bool live = ex && (!xbc || tt < ln);          // a broadcast row fills the clip's own frames only
+                int oraw = p.out_idx ? p.out_idx[i] : i;
+                const bool fst = KIND >= 2 && (oraw & STAIR_TILE_STORE_FIRST) != 0;
+                if (KIND >= 2) oraw &= ~STAIR_TILE_STORE_FIRST;
+                pk_tf[R] = (live ? tt : 0) | (tt << 16) | (live ? TM_PK_LIVE : 0) | (fst ? TM_PK_FIRST : 0);
+                pk_xi[R] = p.x_idx ? p.x_idx[i] : i;
+                pk_oi[R] = oraw;
+                pk_len[R] = ln;
+                if (KIND == 0) {
+                    pk_sc[R] = p.row_scale ? p.row_scale[(int64_t)(p.rs_idx ? p.rs_idx[i] : i) * Tc + tt] : 1.0f;
+                    pk_ex[R] = p.extra ? p.extra[i] : 0.f;
+                    pk_pf[R] = p.tail == STAIR_TILE_COSINE ? p.pair_first[i] : 0;
+                    pk_pc[R] = p.tail == STAIR_TILE_COSINE ? p.pair_cnt[i] : 0;
+                }
+                if (KIND == 2 || KIND == 3) pk_mi[R] = p.in_mask_idx ? p.in_mask_idx[i] : i;
+                if (KIND == 2) {
+                    pk_fi[R] = p.adj_feat_idx ? p.adj_feat_idx[i] : i;
+                    pk_ri[R] = p.adj_rs_idx ? p.adj_rs_idx[i] : i;
+                }
+                if (KIND >= 2) {
+                    const unsigned long long notfirst = __ballot(ex && !fst);
+                    if (R == 0) pk_allfirst = notfirst == 0ull ? 1 : 0;
+                }
+            }
+            TM_SYNC();
+        }
+        // ---- the input tile: fp32 rows -> (row scale) -> bf16 hi / lo image ------------------------------------------
+        const float *x = PACK ? nullptr : tm_fresh(p.X + (int64_t)(p.x_idx ? __builtin_amdgcn_readfirstlane(p.x_idx[inst]) : inst) * p.x_gstride);
+        const float *rsrow = PACK ? nullptr : (KIND == 0 && p.row_scale ? p.row_scale + (int64_t)(p.rs_idx ? __builtin_amdgcn_readfirstlane(p.rs_idx[inst]) : inst) * T : nullptr);
+        const bool has_rs = PACK ? (KIND == 0 && p.row_scale != nullptr) : rsrow != nullptr;
+        // (a NULL must stay a visible NULL: through tm_fresh the forward kernel kept the whole mask path, and its registers)
+        const float *imask = PACK ? ((KIND == 2 || KIND == 3) && p.in_mask ? p.in_mask : nullptr)
+                                  : ((KIND == 2 || KIND == 3) && p.in_mask ? tm_fresh(p.in_mask + (int64_t)(p.in_mask_idx ? __builtin_amdgcn_readfirstlane(p.in_mask_idx[inst]) : inst) * p.in_mask_gstride) : nullptr);
+        const int Lrows = PACK ? T : (xbc ? (p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T) : T);     // a broadcast row fills the clip's own frames only
         // vector-level modules: row t of the tile is H-wide block `seg` of the concatenation built from the two operand rows
         // of instance 64 inst + t (never materialised for the GEMM; cat_save keeps it for the weight gradient)
         auto build_vec_image = [&](const int seg) {
@@ -287,7 +351,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             // image; what is written there (and kept: save_in) is dZ of the dense layer.  Thread (wave, lane) carries columns
             // 8 lane .. +7 of rows wave + 8 j, all loads of four rows first (as below).
             const int c8 = lane;
-            const float *ysv = tm_fresh(imask);
+            const float *ysv = PACK ? nullptr : tm_fresh(imask);
             const v4f gm0 = *reinterpret_cast<const v4f *>(p.gamma + 8 * c8), gm1 = *reinterpret_cast<const v4f *>(p.gamma + 8 * c8 + 4);
             v4f ag0 = {0.f, 0.f, 0.f, 0.f}, ag1 = ag0, ab0 = ag0, ab1 = ag0;
             v4f dz[8][2];
@@ -297,11 +361,13 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int t = wave + 8 * (4 * half + j);
-                    const int ts = t < T ? t : 0;
-                    xa[j] = tm_ld<NT>(x + (int64_t)ts * TM_H + 8 * c8);
-                    xb[j] = tm_ld<NT>(x + (int64_t)ts * TM_H + 8 * c8 + 4);
-                    ya[j] = tm_ld<NT>(ysv + (int64_t)ts * TM_H + 8 * c8);
-                    yb[j] = tm_ld<NT>(ysv + (int64_t)ts * TM_H + 8 * c8 + 4);
+                    const int ts = PACK ? (TM_PK_S(pk_tf, t) & 63) : (t < T ? t : 0);
+                    const float *xrow = PACK ? p.X + (int64_t)TM_PK_S(pk_xi, t) * p.x_gstride : x;
+                    const float *yrow = PACK ? p.in_mask + (int64_t)TM_PK_S(pk_mi, t) * p.in_mask_gstride : ysv;
+                    xa[j] = tm_ld<NT>(xrow + (int64_t)ts * TM_H + 8 * c8);
+                    xb[j] = tm_ld<NT>(xrow + (int64_t)ts * TM_H + 8 * c8 + 4);
+                    ya[j] = tm_ld<NT>(yrow + (int64_t)ts * TM_H + 8 * c8);
+                    yb[j] = tm_ld<NT>(yrow + (int64_t)ts * TM_H + 8 * c8 + 4);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -341,7 +407,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 for (int j = 0; j < 8; ++j) {
                     const int t = wave + 8 * j;
                     if (t < T) {
-                        float *d = p.save_in + ((int64_t)inst * Ts + t) * TM_H + 8 * c8;
+                        float *d = p.save_in + (TM_ROWBASE + t) * TM_H + 8 * c8;
                         tm_st<NT>(d, dz[j][0]); tm_st<NT>(d + 4, dz[j][1]);
                     }
                 }
@@ -385,21 +451,23 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int t = wave + 8 * (4 * half + j);
-                    const int ts = t < Lrows ? t : 0;
-                    const float *xr = x + (xbc ? 0 : (int64_t)ts * TM_H) + 8 * c8;
+                    const int ts = PACK ? (TM_PK_S(pk_tf, t) & 63) : (t < Lrows ? t : 0);
+                    const float *xrow = PACK ? p.X + (int64_t)TM_PK_S(pk_xi, t) * p.x_gstride : x;
+                    const float *xr = xrow + (xbc ? 0 : (int64_t)ts * TM_H) + 8 * c8;
                     xa[j] = tm_ld<NT>(xr);
                     xb[j] = tm_ld<NT>(xr + 4);
-                    sc[j] = rsrow ? rsrow[ts] : 1.0f;
+                    sc[j] = PACK ? (has_rs ? pk_sc[t] : 1.0f) : (rsrow ? rsrow[ts] : 1.0f);
                     if (imask) {
-                        ma[j] = tm_ld<NT>(imask + (int64_t)ts * TM_H + 8 * c8);
-                        mb[j] = tm_ld<NT>(imask + (int64_t)ts * TM_H + 8 * c8 + 4);
+                        const float *mrow = PACK ? p.in_mask + (int64_t)TM_PK_S(pk_mi, t) * p.in_mask_gstride : imask;
+                        ma[j] = tm_ld<NT>(mrow + (int64_t)ts * TM_H + 8 * c8);
+                        mb[j] = tm_ld<NT>(mrow + (int64_t)ts * TM_H + 8 * c8 + 4);
                     }
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int t = wave + 8 * (4 * half + j);
                     v4f a = xa[j], b = xb[j];
-                    if (rsrow) { a *= sc[j]; b *= sc[j]; }
+                    if (has_rs) { a *= sc[j]; b *= sc[j]; }
                     if (imask) {              // backward chains: the incoming gradient times relu'(saved activation) (x in_scale)
 #pragma unroll
                         for (int i = 0; i < 4; ++i) { a[i] = ma[j][i] > 0.f ? a[i] * p.in_scale : 0.f; b[i] = mb[j][i] > 0.f ? b[i] * p.in_scale : 0.f; }
@@ -408,7 +476,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) { a[i] = (m >> i) & 1u ? a[i] * p.in_scale : 0.f; b[i] = (m >> (4 + i)) & 1u ? b[i] * p.in_scale : 0.f; }
                     }
-                    if (t >= Lrows) { a = v4f{0.f, 0.f, 0.f, 0.f}; b = a; }
+                    if (PACK ? !(TM_PK_S(pk_tf, t) & TM_PK_LIVE) : t >= Lrows) { a = v4f{0.f, 0.f, 0.f, 0.f}; b = a; }
                     xa[j] = a; xb[j] = b;
                     bf16x8 hi, lo;
                     tm_split8(a, b, hi, lo);
@@ -421,7 +489,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     for (int j = 0; j < 4; ++j) {
                         const int t = wave + 8 * (4 * half + j);
                         if (t < T) {
-                            float *d = p.save_in + ((int64_t)inst * Ts + t) * TM_H + 8 * c8;
+                            float *d = p.save_in + (TM_ROWBASE + t) * TM_H + 8 * c8;
                             tm_st<NT>(d, xa[j]); tm_st<NT>(d + 4, xb[j]);
                         }
                     }
@@ -527,7 +595,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                             if (act == 1) z[i] = fmaxf(z[i], 0.0f);
                         }
                         if (KIND == 0 && dsite) {       // nn.Dropout behind this activation: the bits stair_dropout_fwd draws for the [cnt, T, H] rows
-                            const unsigned long long e0 = ((unsigned long long)inst * p.T + t) * p.H + (64 * wave + 32 * nt + 8 * q + 4 * h_e);
+                            const unsigned long long e0 = ((PACK ? (unsigned long long)pkI0 : (unsigned long long)inst) * p.T + t) * p.H + (64 * wave + 32 * nt + 8 * q + 4 * h_e);
                             const unsigned long long bits4 = drop_hash4(pp.drop_seed, dsite - 1u, e0 >> 2);      // e0 % 4 == 0 (H % 4 == 0)
 #pragma unroll
                             for (int i = 0; i < 4; ++i) z[i] = drop_keep(bits4, i, pp.drop_thresh) ? z[i] * pp.drop_inv_keep : 0.0f;
@@ -551,7 +619,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 //      need, FilterFrame's attention; then the rows become the next layer's bf16 hi / lo operand image.
                 //      The rows are read into registers first: the image overlays the staging. -----------------------------------
                 float *sv = tm_fresh(p.save[ph]);
-                const float *amask = KIND == 3 && act == 3 && p.act_mask[ph] ? tm_fresh(p.act_mask[ph] + (int64_t)inst * Ts * TM_H) : nullptr;
+                const float *amask = KIND == 3 && act == 3 && p.act_mask[ph] ? tm_fresh(p.act_mask[ph] + TM_ROWBASE * TM_H) : nullptr;
                 const unsigned long long *abits_p = KIND == 3 && act == 3 && !amask ? p.act_bits[ph] : nullptr;
                 const unsigned long long abits = abits_p ? abits_p[(int64_t)inst * TM_H + 64 * wave + lane_e] : 0ull;
                 unsigned long long *svbits = KIND == 0 ? p.save_bits[ph] : nullptr;
@@ -564,7 +632,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 float rd_b = 0.f;
                 if (rowdot) {
                     w0 = *reinterpret_cast<const v4f *>(p.vw + 8 * lane_e); w1 = *reinterpret_cast<const v4f *>(p.vw + 8 * lane_e + 4);
-                    rd_b = p.vb[0] + (p.extra ? p.extra[inst] : 0.f);
+                    rd_b = PACK ? p.vb[0] : p.vb[0] + (p.extra ? p.extra[inst] : 0.f);       // (packed: extra is the ROW's instance's)
                 }
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
@@ -598,15 +666,15 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                                 obits |= (unsigned long long)m << (8 * j);
                             }
                             if (sv) {
-                                float *d = sv + ((int64_t)inst * Ts + t) * TM_H + 8 * lane_e;
+                                float *d = sv + (TM_ROWBASE + t) * TM_H + 8 * lane_e;
                                 tm_st<NT>(d, a); tm_st<NT>(d + 4, b);
                             }
                             if (rowdot) {         // FilterFrame: a_t = sigmoid(w[:H] . f_t + extra + b); the next layer runs on a_t f_t
                                 float d = 0.f;
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) d += a[i] * w0[i] + b[i] * w1[i];
-                                const float at = sigmoid_acc(wave_sum(d) + rd_b);
-                                if (p.rs_out && lane_e == 0) p.rs_out[(int64_t)inst * T + t] = at;
+                                const float at = sigmoid_acc(wave_sum(d) + (PACK ? rd_b + pk_ex[t] : rd_b));
+                                if (p.rs_out && lane_e == 0) p.rs_out[(PACK ? (int64_t)pkI0 * p.T : (int64_t)inst * T) + t] = at;
                                 a *= at; b *= at;
                             }
                         }
@@ -632,7 +700,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
         float *svl = p.save[p.n_layers - 1];
         if (svl)                                      // the last layer's rows for the backward pass (coalesced 2 KB rows)
             for (int t = wave; t < T; t += 8) {
-                float *dst = svl + ((int64_t)inst * Ts + t) * TM_H;
+                float *dst = svl + (TM_ROWBASE + t) * TM_H;
                 tm_st<NT>(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane));
                 tm_st<NT>(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane));
             }
@@ -650,9 +718,240 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             p.save_bits[p.n_layers - 1][(int64_t)inst * TM_H + 64 * wave + lane] = obits;
         }
         // backward chains (forms 2 and 3): bit STAIR_TILE_STORE_FIRST of an out_idx entry marks a target nothing has written yet
-        const int oraw = p.out_idx ? __builtin_amdgcn_readfirstlane(p.out_idx[inst]) : (int)inst;
+        const int oraw = PACK ? 0 : (p.out_idx ? __builtin_amdgcn_readfirstlane(p.out_idx[inst]) : (int)inst);
         const bool ofirst = KIND >= 2 && (oraw & STAIR_TILE_STORE_FIRST) != 0;
         const int64_t oslot = KIND >= 2 ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
+        if (PACK) {
+            // ---- the tails of a packed tile: the same arithmetic per row, every row at its own instance's targets ----------------
+            // (a copy of the unpacked tails below with per-row addresses, so that the unpacked instantiations compile as they did:
+            //  a change to a tail's arithmetic is made in BOTH -- tests/test_gpu_tile_pack.py compares the two bit for bit)
+            const int Tc = p.T;
+            // (row R's frame, and its tile in `out`: the entry of out_idx without the STORE_FIRST bit)
+#define TM_PK_T(row_) ((TM_PK_S(pk_tf, row_) >> 16) & 63)
+#define TM_PK_OUT(row_) (p.out + (int64_t)TM_PK_S(pk_oi, row_) * p.out_gstride)
+            if (KIND == 2) {
+                // ROWSCALE_ADJ (see the unpacked form below): d feat_t += r_t G_t, d r_t += G_t . feat_t, per row
+                __builtin_amdgcn_sched_barrier(0);
+                v4f f0[8], f1[8];
+                float rr[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {           // every global load of the tail first
+                    const int R = wave + 8 * j, ts = TM_PK_S(pk_tf, R) & 63;
+                    const float *feat = p.adj_feat + (int64_t)TM_PK_S(pk_fi, R) * p.adj_feat_gstride + (int64_t)ts * TM_H;
+                    f0[j] = tm_ld<NT>(feat + 4 * lane);
+                    f1[j] = tm_ld<NT>(feat + 256 + 4 * lane);
+                    rr[j] = p.adj_rs[(int64_t)TM_PK_S(pk_ri, R) * Tc + ts];
+                }
+                const bool allfirst = TM_PK_S(&pk_allfirst, 0) != 0;
+                if (allfirst) {                         // every instance of the tile stores the first contribution to its target
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int R = wave + 8 * j;
+                        if (R < T) {
+                            const int t = TM_PK_T(R);
+                            float *dst = TM_PK_OUT(R) + (int64_t)t * TM_H;
+                            float *drs = p.adj_drs + (int64_t)TM_PK_S(pk_ri, R) * Tc + t;
+                            const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                            float d = 0.f;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
+                            d = wave_sum(d);
+                            if (lane == 0) unsafeAtomicAdd(drs, d);
+                            *reinterpret_cast<v4f *>(dst + 4 * lane) = rr[j] * g0;
+                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = rr[j] * g1;
+                        }
+                    }
+                } else if (p.acc_exclusive) {           // read - add - write; a row whose instance stores first discards what it read
+                    v4f o0[8], o1[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int R = wave + 8 * j;
+                        const float *src = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
+                        o0[j] = *reinterpret_cast<const v4f *>(src + 4 * lane);
+                        o1[j] = *reinterpret_cast<const v4f *>(src + 256 + 4 * lane);
+                    }
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int R = wave + 8 * j;
+                        if (R < T) {
+                            const int tf = TM_PK_S(pk_tf, R), t = (tf >> 16) & 63;
+                            float *dst = TM_PK_OUT(R) + (int64_t)t * TM_H;
+                            float *drs = p.adj_drs + (int64_t)TM_PK_S(pk_ri, R) * Tc + t;
+                            const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                            float d = 0.f;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
+                            d = wave_sum(d);
+                            if (lane == 0) unsafeAtomicAdd(drs, d);
+                            const bool fst = (tf & TM_PK_FIRST) != 0;
+                            *reinterpret_cast<v4f *>(dst + 4 * lane) = fst ? rr[j] * g0 : o0[j] + rr[j] * g0;
+                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = fst ? rr[j] * g1 : o1[j] + rr[j] * g1;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int R = wave + 8 * j;
+                        if (R < T) {
+                            const int tf = TM_PK_S(pk_tf, R), t = (tf >> 16) & 63;
+                            float *dst = TM_PK_OUT(R) + (int64_t)t * TM_H;
+                            float *drs = p.adj_drs + (int64_t)TM_PK_S(pk_ri, R) * Tc + t;
+                            const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                            float d = 0.f;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
+                            d = wave_sum(d);
+                            if (lane == 0) unsafeAtomicAdd(drs, d);
+                            if (tf & TM_PK_FIRST) {
+                                *reinterpret_cast<v4f *>(dst + 4 * lane) = rr[j] * g0;
+                                *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = rr[j] * g1;
+                            } else {
+#pragma unroll
+                                for (int c = 0; c < TM_H / 64; ++c) unsafeAtomicAdd(dst + 64 * c + lane, rr[j] * F[R * TM_FLD + 64 * c + lane]);
+                            }
+                        }
+                    }
+                }
+            } else
+            switch (KIND == 3 && p.tail != STAIR_TILE_ACCUMULATE ? (p.tail == STAIR_TILE_STORE ? STAIR_TILE_STORE : STAIR_TILE_NONE)
+                                                                 : (KIND != 3 && p.tail == STAIR_TILE_ACCUMULATE ? STAIR_TILE_NONE : p.tail)) {
+                case STAIR_TILE_STORE:
+                    for (int R = wave; R < T; R += 8) {
+                        float *dst = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
+                        tm_st<NT>(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane));
+                        tm_st<NT>(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane));
+                    }
+                    break;
+                case STAIR_TILE_ACCUMULATE:
+                    if (KIND != 3) break;
+                    if (TM_PK_S(&pk_allfirst, 0) != 0) {        // every instance of the tile stores: no target is read
+                        for (int R = wave; R < T; R += 8) {
+                            float *dst = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
+                            *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane);
+                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                        }
+                        break;
+                    }
+                    if (p.acc_exclusive) {              // whole rows read, added and written back; a storing instance's rows discard the read
+                        __builtin_amdgcn_sched_barrier(0);
+                        v4f o0[8], o1[8];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const int R = wave + 8 * j;
+                            const float *src = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
+                            o0[j] = *reinterpret_cast<const v4f *>(src + 4 * lane);
+                            o1[j] = *reinterpret_cast<const v4f *>(src + 256 + 4 * lane);
+                        }
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const int R = wave + 8 * j;
+                            if (R < T) {
+                                const int tf = TM_PK_S(pk_tf, R);
+                                float *dst = TM_PK_OUT(R) + (int64_t)((tf >> 16) & 63) * TM_H;
+                                const bool fst = (tf & TM_PK_FIRST) != 0;
+                                const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                                *reinterpret_cast<v4f *>(dst + 4 * lane) = fst ? g0 : o0[j] + g0;
+                                *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = fst ? g1 : o1[j] + g1;
+                            }
+                        }
+                        break;
+                    }
+                    for (int R = wave; R < T; R += 8) {
+                        const int tf = TM_PK_S(pk_tf, R);
+                        float *dst = TM_PK_OUT(R) + (int64_t)((tf >> 16) & 63) * TM_H;
+                        if (tf & TM_PK_FIRST) {
+                            *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane);
+                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < TM_H / 64; ++c) unsafeAtomicAdd(dst + 64 * c + lane, F[R * TM_FLD + 64 * c + lane]);
+                        }
+                    }
+                    break;
+                case STAIR_TILE_SUM_ROWS: {               // one sum per instance, over its own frames, in frame order
+                    if (KIND == 3) break;
+                    const int col = tm_fresh_v(TM_TID());
+                    for (int sg = 0; sg < pkN; ++sg) {
+                        const int R0 = sg * Tc;
+                        const int L = TM_PK_S(pk_len, R0);
+                        float s = 0.f;
+                        for (int t = 0; t < L; ++t) s += F[(R0 + t) * TM_FLD + col];
+                        TM_PK_OUT(R0)[col] = s;
+                    }
+                    break;
+                }
+                case STAIR_TILE_COSINE: {                 // every instance against its own keyword rows
+                    if (KIND == 3) break;
+                    for (int sg = 0; sg < pkN; ++sg) {
+                        const int R0 = sg * Tc;
+                        const int first = TM_PK_S(pk_pf, R0), cn = TM_PK_S(pk_pc, R0);
+                        for (int j = 0; j < cn; ++j) {
+                            const float *k = p.kb + (int64_t)(first + j) * TM_H;
+                            const v4f k0 = *reinterpret_cast<const v4f *>(k + 4 * lane), k1 = *reinterpret_cast<const v4f *>(k + 256 + 4 * lane);
+                            float *arow = p.att + (int64_t)p.att_idx[first + j] * Tc;
+                            float nk = 0.f;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) nk += k0[i] * k0[i] + k1[i] * k1[i];
+                            nk = wave_sum(nk);
+                            for (int t = wave; t < Tc; t += 8) {
+                                const float *fr = F + (R0 + t) * TM_FLD;
+                                const v4f f0 = *reinterpret_cast<const v4f *>(fr + 4 * lane), f1 = *reinterpret_cast<const v4f *>(fr + 256 + 4 * lane);
+                                float nf = 0.f, d = 0.f;
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) { nf += f0[i] * f0[i] + f1[i] * f1[i]; d += f0[i] * k0[i] + f1[i] * k1[i]; }
+                                nf = wave_sum(nf); d = wave_sum(d);
+                                if (lane == 0) {
+                                    const float eps = 1e-8f;
+                                    const float c = d / (fmaxf(sqrtf(nf), eps) * fmaxf(sqrtf(nk), eps));
+                                    arow[t] = (c + 1.0f) * 0.49f;
+                                }
+                            }
+                        }
+                    }
+                    break;
+                }
+                case STAIR_TILE_ROWDOT_SIGMOID: {
+                    if (KIND == 3) break;
+                    const v4f w0 = *reinterpret_cast<const v4f *>(p.vw + 4 * lane), w1 = *reinterpret_cast<const v4f *>(p.vw + 256 + 4 * lane);
+                    const float vb0 = p.vb[0];
+                    for (int R = wave; R < T; R += 8) {
+                        const float off = vb0 + pk_ex[R];
+                        const v4f f0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                        float d = 0.f;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) d += f0[i] * w0[i] + f1[i] * w1[i];
+                        d = wave_sum(d);
+                        if (lane == 0) TM_PK_OUT(R)[TM_PK_T(R)] = sigmoid_acc(d + off);
+                    }
+                    break;
+                }
+                case STAIR_TILE_LAYERNORM: {
+                    if (KIND == 3) break;
+                    const v4f g0 = *reinterpret_cast<const v4f *>(p.gamma + 4 * lane), g1 = *reinterpret_cast<const v4f *>(p.gamma + 256 + 4 * lane);
+                    const v4f b0 = *reinterpret_cast<const v4f *>(p.beta + 4 * lane), b1 = *reinterpret_cast<const v4f *>(p.beta + 256 + 4 * lane);
+                    for (int R = wave; R < T; R += 8) {
+                        v4f f0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                        float sum = 0.f;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) sum += f0[i] + f1[i];
+                        const float mean = wave_sum(sum) / (float)TM_H;
+                        float sq = 0.f;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) { const float a = f0[i] - mean, b = f1[i] - mean; sq += a * a + b * b; }
+                        const float rstd = rsqrtf(wave_sum(sq) / (float)TM_H + p.ln_eps);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) { f0[i] = (f0[i] - mean) * rstd * g0[i] + b0[i]; f1[i] = (f1[i] - mean) * rstd * g1[i] + b1[i]; }
+                        float *dst = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
+                        *reinterpret_cast<v4f *>(dst + 4 * lane) = f0;
+                        *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = f1;
+                    }
+                    break;
+                }
+                default: break;
+            }
+#undef TM_PK_OUT
+#undef TM_PK_T
+        } else
         if (KIND == 2) {
             // tail ROWSCALE_ADJ: the staged rows are G = dZ W, the gradient of the SCALED input r_t feat_t of the dense layer:
             // d feat_t += r_t G_t (one dword per lane, 256 contiguous bytes per wave-instruction), d r_t += G_t . feat_t
@@ -881,6 +1180,10 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
     }
 }
 
+#undef TM_ROWBASE
+#undef TM_PK_S
+#undef TM_PK_FIRST
+#undef TM_PK_LIVE
 #undef TM_TID
 #undef TM_LANE
 
@@ -944,6 +1247,17 @@ static bool g_tile_timing = false;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_tile_events;
 
 static int g_tile_on = 1;           // stair_set_tile_mlp
+static int g_tile_pack = 1;         // stair_set_tile_pack
+static std::atomic<int64_t> g_tile_work_items{0};     // stair_tile_work_items
+thread_local int tl_tile_pack_force = -1;
+// does a map-level launch on this thread pack short clips?  A plan's backward pass forces what its forward pass ran with
+// (TilePackForce); else the context's override (stair_ctx_set_tile_pack), else the process-wide switch.
+int tile_pack_setting() {
+    if (tl_tile_pack_force >= 0) return tl_tile_pack_force != 0;
+    if (tl_policy && tl_policy->tile_pack >= 0) return tl_policy->tile_pack != 0;
+    return g_tile_pack != 0;
+}
+static int tile_pack_factor(int T, bool on) { return on && T >= 1 && T <= TM_ROWS / 2 ? TM_ROWS / T : 1; }
 bool tile_mlp_usable(int H, int T) {
     const bool on = policy_or(STAIR_OPT_TILE_MLP, g_tile_on) != 0;
     return on && H == TM_H && T >= 1 && T <= TM_ROWS && matmul_mode() == STAIR_MATMUL_BF16X3;
@@ -1022,6 +1336,9 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         int v = 256;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         cus[dev] = v;
@@ -1041,6 +1358,9 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
         for (int l = 0; l < a.n_layers && l < 3; ++l) chain = chain || a.act[l] == 3;
         return chain ? 3 : 0;
     };
+    // short clips share a tile (the packed kernel forms): P = 64 / T instances per tile whenever T <= 32, decided here for the
+    // whole call -- the caller's buckets count INSTANCES either way
+    const bool pack_on = tile_pack_setting() != 0;
     for (int kind = 0; kind < 4; ++kind) {
         const int vec = kind == 1;
         TmParams pp;
@@ -1068,23 +1388,30 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
             }
         }
         std::stable_sort(order, order + m, [&](int x, int y) { return rounds(x) > rounds(y); });    // long tiles first
+        bool packed = false;
         for (int j = 0; j < m; ++j) {
             const stair_tile_mlp_args &a = args[order[j]];
-            pp.a[j] = tm_arg(a, kind);
-            pp.first[j + 1] = pp.first[j] + a.cnt;
+            const int P = kind == 1 ? 1 : tile_pack_factor(a.T, pack_on);
+            packed = packed || P > 1;
+            pp.a[j] = tm_arg(a, kind, P);
+            pp.first[j + 1] = pp.first[j] + (a.cnt + P - 1) / P;          // work items are TILES
             const int64_t M = a.vec_pack ? a.vec_cnt : (int64_t)a.cnt * a.T;
             const int kl = rounds(order[j]);
             STAIR_ACCT_MFMA("tile_mlp", (M * TM_H * 2 + (int64_t)kl * TM_H * TM_H) * 4, 2 * M * TM_H * TM_H * kl);
         }
         for (int j = m; j < TM_MAXB; ++j) { pp.a[j] = pp.a[0]; pp.first[j + 1] = pp.first[m]; }
         pp.nb = m;
+        g_tile_work_items.fetch_add(pp.first[m], std::memory_order_relaxed);
         const int grid = std::min(pp.first[m], cus[dev]);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (g_tile_timing) {
             STAIR_HIP(hipEventCreate(&e0)); STAIR_HIP(hipEventCreate(&e1));
             STAIR_HIP(hipEventRecord(e0, s));
         }
-        if (vec) hipLaunchKernelGGL((tile_mlp_kernel<false, 1>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        if (packed && kind == 0) hipLaunchKernelGGL((tile_mlp_kernel<true, 0, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        else if (packed && kind == 2) hipLaunchKernelGGL((tile_mlp_kernel<true, 2, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        else if (packed && kind == 3) hipLaunchKernelGGL((tile_mlp_kernel<true, 3, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        else if (vec) hipLaunchKernelGGL((tile_mlp_kernel<false, 1>), dim3(grid), dim3(512), TM_LDS, s, pp);
         else if (kind == 2) hipLaunchKernelGGL((tile_mlp_kernel<true, 2>), dim3(grid), dim3(512), TM_LDS, s, pp);
         else if (kind == 3) hipLaunchKernelGGL((tile_mlp_kernel<true, 3>), dim3(grid), dim3(512), TM_LDS, s, pp);
         else hipLaunchKernelGGL((tile_mlp_kernel<true, 0>), dim3(grid), dim3(512), TM_LDS, s, pp);
@@ -1102,6 +1429,16 @@ int launch_tile_mlp(const stair_tile_mlp_args &a, hipStream_t s) { return launch
 }  // namespace stair
 
 extern "C" int stair_set_tile_mlp(int32_t on) { stair::g_tile_on = on; return 0; }
+
+extern "C" int stair_set_tile_pack(int32_t on) { stair::g_tile_pack = on < 0 ? 1 : (on != 0); return 0; }
+
+extern "C" int32_t stair_tile_pack_factor(int32_t T) { return stair::tile_pack_factor(T, stair::g_tile_pack != 0); }
+
+extern "C" int stair_tile_work_items(int64_t *items, int32_t reset) {
+    const int64_t v = reset ? stair::g_tile_work_items.exchange(0) : stair::g_tile_work_items.load();
+    if (items) *items = v;
+    return 0;
+}
 
 extern "C" int stair_tile_mlp_fwd(const stair_tile_mlp_args *args, stair_stream stream) {
     if (!args) {

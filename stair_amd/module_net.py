@@ -362,8 +362,12 @@ class VideoNMN(nn.Module):
 
     def set_option(self, name, value):
         """Per-context override of a process-wide library setting (stair_ctx_set_option): 'matmul_mode' ('f32' / 'bf16x3' / 'bf16'),
-        'tile_mlp', 'tile_queue', 'vec_group' (0 / 1), 'tn_slab_min_rows'; None restores the process default.  In force for this
+        'tile_mlp', 'tile_queue', 'vec_group' (0 / 1), 'tn_slab_min_rows', and 'tile_pack' (0 / 1: clips of at most 32 frames share
+        a 64-row tile; stair_ctx_set_tile_pack); None restores the process default.  In force for this
         model's forward and backward passes only: other models of the process keep their own settings."""
+        if name == 'tile_pack':
+            check(lib.stair_ctx_set_tile_pack(self._ctx, -1 if value is None else int(value)))
+            return
         if name == 'matmul_mode' and isinstance(value, str):
             value = self.MATMUL_MODES[value]
         check(lib.stair_ctx_set_option(self._ctx, self.OPTIONS[name], -1 if value is None else int(value)))
