@@ -319,7 +319,16 @@ int stair_lstm_bidir_bwd(const stair_lstm_bwd_args *args, stair_stream stream);
  * index array and len / extra / pair_first / pair_cnt / STAIR_TILE_STORE_FIRST stays per instance.  Results are those of the
  * unpacked launch bit for bit, except dgamma / dbeta of a ln_bwd chain (float sums over a TILE's rows before they reach the
  * fixed-point accumulators: reproducible from run to run, but grouped differently).  Only save_bits / act_bits / in_bits change
- * meaning: they are indexed by TILE (see below), so a chain must run with the packing of the forward launch that wrote its bits. */
+ * meaning: they are indexed by TILE (see below), so a chain must run with the packing of the forward launch that wrote its bits.
+ * Segmented tiles (stair_set_tile_split, on by default): a map-level launch takes 64 < T <= 141 and runs every instance as
+ * S = ceil(T / 64) segments, segment g = frames 64 g .. min(64 g + 64, T) - 1, a bucket of cnt instances being cnt S tiles (a SUM_ROWS
+ * bucket: cnt work items, one workgroup adding an instance's segments in frame order -- a fixed-order sum without atomics).  The
+ * arguments do not change and a row's result depends on no other row: every output is what the same rows give as instances of
+ * their own, bit for bit (dgamma / dbeta of a ln_bwd chain: tile-wise float sums, as above).  save_bits / act_bits / in_bits are
+ * indexed by tile = instance * S + segment and hold cnt * S * H words.  With len, a segment behind its clip's end (64 g >= len[i])
+ * is not computed: zeros are written wherever a live segment writes (save, save_in, the bits, rs_out, the STORE / LAYERNORM rows,
+ * the COSINE / ROWDOT_SIGMOID values, the rows of a chain tail marked STAIR_TILE_STORE_FIRST); a chain tail that adds, adds nothing.
+ * With the switch off a launch of T > 64 is refused, as it always was. */
 enum stair_tile_tail { STAIR_TILE_NONE = 0, STAIR_TILE_STORE = 1, STAIR_TILE_SUM_ROWS = 2, STAIR_TILE_COSINE = 3,
                        STAIR_TILE_ROWDOT_SIGMOID = 4, STAIR_TILE_LAYERNORM = 5, STAIR_TILE_ACCUMULATE = 6,
                        STAIR_TILE_STORE_ROWS = 7, STAIR_TILE_ROWSCALE_ADJ = 8 };
@@ -449,6 +458,15 @@ int stair_set_tile_pack(int32_t on);
 int stair_ctx_set_tile_pack(stair_ctx *ctx, int32_t value);
 int stair_ctx_get_tile_pack(const stair_ctx *ctx, int32_t *value);
 int32_t stair_tile_pack_factor(int32_t T);
+/* Long clips as 64-row segments: process-wide, on = 1 (default) admits 64 < T <= 141 to the fused tile operators, on = 0 keeps them
+ * to T <= 64 (plans of longer clips then run the launch-per-layer sequences), on < 0 restores the default.  A context may override
+ * it (0 / 1; -1 inherits), a switch of its own like stair_ctx_set_tile_pack; a plan's backward pass runs with the setting of its
+ * last forward pass.  stair_tile_segments: host only, the S of a map-level launch of T frames under the process-wide setting
+ * (ceil(T / 64) for T > 64 while on, else 1).  stair_tile_work_items counts a segmented bucket as cnt * S tiles. */
+int stair_set_tile_split(int32_t on);
+int stair_ctx_set_tile_split(stair_ctx *ctx, int32_t value);
+int stair_ctx_get_tile_split(const stair_ctx *ctx, int32_t *value);
+int32_t stair_tile_segments(int32_t T);
 int stair_tile_work_items(int64_t *items, int32_t reset);
 /* W [N, K] fp32 row-major -> planes: [N/32][K/16][hi, lo][64 lanes][8 bf16] (2 * N * K * 2 bytes, 16-byte aligned);
  * N % 32 == 0, K % 16 == 0.  transpose != 0: W is stored [K, N] and the planes are those of W^T (backward chains). */

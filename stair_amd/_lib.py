@@ -146,6 +146,10 @@ SIGNATURES = [
     ('stair_ctx_set_tile_pack', C.c_int, [C.c_void_p, C.c_int32]),
     ('stair_ctx_get_tile_pack', C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     ('stair_tile_pack_factor', C.c_int32, [C.c_int32]),
+    ('stair_set_tile_split', C.c_int, [C.c_int32]),
+    ('stair_ctx_set_tile_split', C.c_int, [C.c_void_p, C.c_int32]),
+    ('stair_ctx_get_tile_split', C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    ('stair_tile_segments', C.c_int32, [C.c_int32]),
     ('stair_tile_work_items', C.c_int, [C.POINTER(C.c_int64), C.c_int32]),
     ('stair_tile_mlp_fwd', C.c_int, [C.POINTER(TileMlpArgs), C.c_void_p]),
     ('stair_pack_wfrag', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

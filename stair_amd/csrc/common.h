@@ -95,6 +95,7 @@ extern bool g_acct_on;
 struct Policy {
     int v[STAIR_OPT_COUNT];
     int tile_pack = -1;              // stair_ctx_set_tile_pack (a switch of its own: the option ids of stair_option are closed)
+    int tile_split = -1;             // stair_ctx_set_tile_split (likewise)
     Policy() { for (int &x : v) x = -1; }
 };       // -1: inherit the process default
 extern thread_local const Policy *tl_policy;
@@ -173,6 +174,15 @@ struct TilePackForce {
     int prev;
     explicit TilePackForce(int v) : prev(tl_tile_pack_force) { tl_tile_pack_force = v; }
     ~TilePackForce() { tl_tile_pack_force = prev; }
+};
+// clips of more than 64 frames as 64-row segments (csrc/tile_mlp.hip): the bits are indexed by (instance, segment), so the same rule
+constexpr int kTileSplitMaxFrames = 141;       // the library's frame limit (stair_plan_build)
+int tile_split_setting();
+extern thread_local int tl_tile_split_force;
+struct TileSplitForce {
+    int prev;
+    explicit TileSplitForce(int v) : prev(tl_tile_split_force) { tl_tile_split_force = v; }
+    ~TileSplitForce() { tl_tile_split_force = prev; }
 };
 // csrc/vec_group.hip: the row-wise Linear layers of a program level as one launch
 using VgProblem = stair_vec_problem;

@@ -517,8 +517,9 @@ struct stair_plan {
     std::vector<int32_t> roots;
     std::vector<int32_t> idx;       // host image of the device index buffer
     int64_t off_seqv = 0, off_seqt = 0, off_roots = 0, off_lenv = 0;
-    bool ragged = false;            // clips of different frame counts in this batch (padded to T; per-instance lengths in col[6])
+    bool ragged = false;            // clips of different frame counts in this batch (padded to T; per-instance lengths in col[6] of every T-mixing and every tile operator's bucket)
     bool bits_written = false;      // the last forward run of this (training) plan went through the fused tile operators: Bucket::bit* are valid
+    int tile_split = 1;             // ... and whether clips of more than 64 frames ran as segments (tile_split_setting() of that run)
     int tile_pack = 0;              // ... and whether its map-level tiles were packed (tile_pack_setting() of that run): the relu' bits are
                                     // indexed by TILE, so the backward chains of the plan run with the same packing, whatever the switches say by then
     std::vector<int32_t> vlen;      // frames per clip [n_vid]
@@ -995,7 +996,7 @@ int interpret_programs(stair_plan *pl, const int32_t *prog_off, const int32_t *t
                         if (variant < 0) return bad("FilterFrame keyword must be a [H] vector or relations/actions (modules.py:384-388)");
                         nd.kind = STAIR_VAL_MAP; nd.slot = pl->n_map++;
                         Bucket &b = B.bucket(nd.level, tok, variant, 0);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(variant == 0 ? c1.slot : 0); b.col[2].push_back(nd.slot);
+                        b.col[0].push_back(c0.slot); b.col[1].push_back(variant == 0 ? c1.slot : 0); b.col[2].push_back(nd.slot); b.col[6].push_back(Lq);      // (the clip's frames: segments of a long clip behind its end are not computed)
                         b.cnt++;
                         break;
                     }
@@ -1003,7 +1004,7 @@ int interpret_programs(stair_plan *pl, const int32_t *prog_off, const int32_t *t
                         if (c0.kind != STAIR_VAL_MAP) return bad("HasItem(feat [T,H])");
                         nd.kind = STAIR_VAL_FRAME; nd.slot = pl->n_att++;
                         Bucket &b = B.bucket(nd.level, tok, 0, 0);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(nd.slot);
+                        b.col[0].push_back(c0.slot); b.col[1].push_back(nd.slot); b.col[6].push_back(Lq);
                         b.cnt++;
                         break;
                     }
@@ -1014,7 +1015,7 @@ int interpret_programs(stair_plan *pl, const int32_t *prog_off, const int32_t *t
                         nd.kind = STAIR_VAL_ATT; nd.slot = pl->n_att; nd.aux = K;
                         pl->n_att += K;
                         Bucket &b = B.bucket(nd.level, tok, 0, 0);
-                        b.col[0].push_back(c0.slot);
+                        b.col[0].push_back(c0.slot); b.col[6].push_back(Lq);
                         b.col[4].push_back(b.nrows);      // first pair of this instance
                         b.col[5].push_back(K);            // number of pairs
                         for (int k = 0; k < K; ++k) {
@@ -1284,7 +1285,9 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
     pl->o_sup = pl->take("sup", (int64_t)std::max(pl->maxSupRows, 1) * T, 64);
     pl->o_extra = pl->take("extra", std::max(pl->maxI, 1), 64);
     pl->o_logits = pl->take("logits", (int64_t)n * A, 64);
-    pl->o_wfrag = (H == 512 && T <= 64) ? pl->take("wfrag", (int64_t)WV_END * H * H, 64) : 0;     // bf16 hi/lo fragment-order planes of the fused tile operators' weights
+    // (clips of 65 .. 141 frames run on the tile operators as 64-row segments while stair_set_tile_split is on -- decided per pass by
+    // tile_mlp_usable, so the planes and the bit regions below are laid out for either setting)
+    pl->o_wfrag = (H == 512 && T <= kTileSplitMaxFrames) ? pl->take("wfrag", (int64_t)WV_END * H * H, 64) : 0;     // bf16 hi/lo fragment-order planes of the fused tile operators' weights
     pl->o_status = pl->take("status", 128, 64);  // word 0: sticky "a cooperative hand-off timed out" flag of this plan's passes; words 16, 17
                                                  // and 18, 19: the self-resetting work queues of the fused forward / backward tile launches
     for (int bi = 0; bi < nb; ++bi) {
@@ -1382,7 +1385,7 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
             if (pl->o_wfrag > 0 && b.cnt > 0) {          // the level's backward chains share a launch: no scratch in common
                 if (b.op == STAIR_OP_FILTER) b.gRow = pl->take("gRow", (int64_t)b.cnt * H, 64);
                 if (b.op == STAIR_OP_FILTERFRAME && b.variant != 0) b.dzC = pl->take("dzC", (int64_t)b.cnt * T * H, 64);
-                const int64_t words = (int64_t)b.cnt * 512 * 2;          // 64-bit words, counted in floats
+                const int64_t words = (int64_t)b.cnt * ((T + 63) / 64) * 512 * 2;    // 64-bit words, counted in floats, per TILE: (instance, 64-row segment)
                 switch (b.op) {
                     case STAIR_OP_FILTER: b.bitA = pl->take(".bitA", words, 64, bi); b.bitB = pl->take(".bitB", words, 64, bi); break;
                     case STAIR_OP_FILTERFRAME:
@@ -1947,6 +1950,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
     const bool fused = pl->o_wfrag > 0 && tile_mlp_usable(H, T);
     pl->bits_written = fused && pl->train;
     pl->tile_pack = tile_pack_setting();
+    pl->tile_split = tile_split_setting();
     auto WF = [&](int slot) { return static_cast<const void *>(ws + pl->o_wfrag + (int64_t)slot * H * H); };
     const WeightIndex &WIX = weight_index();
     if (fused) {
@@ -2015,9 +2019,11 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
         a.tail = STAIR_TILE_STORE_ROWS; a.out = vec; a.out_gstride = H; a.out_row_idx = io;
         return a;
     };
-    auto tile_args = [&](const int32_t *x_idx, int cnt_) {
+    // len_: the clips' frames (ragged plans); given to every operator of a long clip, whose segments behind a clip's end run no k loop
+    auto tile_args = [&](const int32_t *x_idx, int cnt_, const int32_t *len_) {
         stair_tile_mlp_args a = {};
         a.X = map; a.x_gstride = TH; a.x_idx = x_idx; a.cnt = cnt_; a.T = T; a.H = H; a.ln_eps = 1e-5f;
+        a.len = T > 64 ? len_ : nullptr;
         return a;
     };
     // drop_pos: the layer's activation is followed by nn.Dropout, position `drop_pos` of the bucket (the `pos` of drop() below)
@@ -2156,7 +2162,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
                 const int v = b.variant;
                 if (fused) {            // both layers and the sum over frames on the tile
                     if (phase == 1) {
-                        stair_tile_mlp_args a = tile_args(I0, c);
+                        stair_tile_mlp_args a = tile_args(I0, c, LEN);
                         tile_layer(a, WF_F0 + v, W.f0[v], 1, tmpA, b.bitA, 0);
                         tile_layer(a, WF_F3 + v, W.f3[v], 1, tmpB, b.bitB, 1);
                         a.tail = STAIR_TILE_SUM_ROWS; a.out = cat; a.out_gstride = H; a.len = LEN;
@@ -2183,7 +2189,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
                 if (fused) {            // three layers with the sigmoid attention in between
                     if (phase != 1) break;
                     if (v == 0) RUN(launch_vecdot(vec, I1, W.ffatt.w + H, extra, c, H, s));
-                    stair_tile_mlp_args a = tile_args(I0, c);
+                    stair_tile_mlp_args a = tile_args(I0, c, LEN);
                     tile_layer(a, WF_FF0 + v, W.ff0[v], 1, tmpA, b.bitA, 0);
                     tile_layer(a, WF_FF3 + v, W.ff3[v], 1, tmpB, b.bitB, 1);
                     tile_layer(a, WF_FFD, W.ffdense, 1, nullptr, b.bitC, 2);
@@ -2211,7 +2217,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
                 if (fused) {
                     if (phase == 2) RUN(drop(att, T, I1, c, T, 1));        // (the D behind HasItem's sigmoid: after the level's tile launch)
                     if (phase != 1) break;
-                    stair_tile_mlp_args a = tile_args(I0, c);
+                    stair_tile_mlp_args a = tile_args(I0, c, LEN);
                     tile_layer(a, WF_HI0, W.hi0, 1, tmpA, b.bitA, 0);
                     a.tail = STAIR_TILE_ROWDOT_SIGMOID; a.vw = W.hi3.w; a.vb = W.hi3.b; a.out = att; a.out_gstride = T; a.out_idx = I1;
                     tile_queue.push_back(a);
@@ -2229,7 +2235,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
                         vg1.push_back(vg_fwd(b.nrows, vec, I2, H, nullptr, nullptr, 0, VG_IN_A, W.lk.w, H, W.lk.b, H, 0, kbuf, nullptr, H));
                         vg1.back().wplanes = WF(WV_LK);
                     } else RUN(dense(s, vec, H, H, I2, W.lk, H, kbuf, H, H, nullptr, b.nrows, 1, H, H, 0));
-                    stair_tile_mlp_args a = tile_args(I0, c);
+                    stair_tile_mlp_args a = tile_args(I0, c, LEN);
                     tile_layer(a, WF_LV0, W.lv0, 1, tmpA, b.bitA, 0);
                     tile_layer(a, WF_LV3, W.lv3, 0, tmpB);
                     a.tail = STAIR_TILE_COSINE; a.kb = kbuf; a.pair_first = I4; a.pair_cnt = I5; a.att_idx = I3; a.att = att;
@@ -2247,7 +2253,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
                 break;
             case STAIR_OP_SUPERLATIVE:  // modules.py:220-248 (shares Localize's weights, module_net.py:31-32)
                 if (fused && phase == 1) {
-                    stair_tile_mlp_args a = tile_args(I0, c);
+                    stair_tile_mlp_args a = tile_args(I0, c, LEN);
                     tile_layer(a, WF_LV0, W.lv0, 1, tmpA, b.bitA, 0);
                     tile_layer(a, WF_LV3, W.lv3, 0, nullptr);
                     a.tail = STAIR_TILE_STORE; a.out = tmpB; a.out_gstride = TH;
@@ -2275,7 +2281,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
                                            mode ? W.relate[mode - 1] : nullptr, s, LEN));
                 if (fused) {            // r_t feat_t -> Lin . ReLU -> LayerNorm on the tile
                     if (phase != 1) break;
-                    stair_tile_mlp_args a = tile_args(I0, c);
+                    stair_tile_mlp_args a = tile_args(I0, c, LEN);
                     tile_layer(a, WF_TD, W.tdense, 1, tmpA, -1, 0);
                     a.row_scale = att; a.rs_idx = I3;
                     a.tail = STAIR_TILE_LAYERNORM; a.gamma = W.ln_w; a.beta = W.ln_b; a.out = map; a.out_gstride = TH; a.out_idx = I4;
@@ -2529,6 +2535,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     STAIR_CHECK(ctx && pl && video && question && workspace && (answers || d_logits_in), "null argument");
     PolicyScope policy_scope(&ctx->policy);
     TilePackForce tile_pack_scope(pl->tile_pack);          // the packing of the forward pass that wrote the saves and bits
+    TileSplitForce tile_split_scope(pl->tile_split);       // ... and its segment setting
     STAIR_CHECK(pl->train, "plan was not built with STAIR_PLAN_TRAIN");
     // slab products queued by a pass that failed half-way must not be added into THIS pass's buffers: the queue starts empty and
     // is emptied again however this function returns
@@ -2836,7 +2843,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                         break;
                     }
                     stair_tile_mlp_args a = {};
-                    a.cnt = c; a.T = T; a.H = H;
+                    a.cnt = c; a.T = T; a.H = H; a.len = T > 64 ? LEN : nullptr;      // (segments behind a clip's end run no k loop)
                     a.X = g_map; a.x_gstride = TH; a.x_idx = I2;
                     if (use_bits && b.bitC >= 0) a.in_bits = BITS(b.bitC); else { a.in_mask = map; a.in_mask_gstride = TH; a.in_mask_idx = I2; }
                     a.in_scale = inv_keep; a.save_in = gC;
@@ -2877,7 +2884,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                 RUN(launch_sum_all(gRs2, W.hi3.db, c * T, s));
                 if (fused) {
                     stair_tile_mlp_args a = {};
-                    a.cnt = c; a.T = T; a.H = H;
+                    a.cnt = c; a.T = T; a.H = H; a.len = T > 64 ? LEN : nullptr;
                     a.X = gA; a.x_gstride = TH; a.in_scale = inv_keep; a.save_in = gA;
                     if (use_bits && b.bitA >= 0) a.in_bits = BITS(b.bitA); else { a.in_mask = svA; a.in_mask_gstride = TH; }
                     a.n_layers = 1; a.W[0] = WFT(WF_HI0); a.act[0] = 0;
@@ -2925,7 +2932,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                     // d(output tile) -> LayerNorm adjoint * relu' = dZ (kept in the weight's region) -> dZ W -> += r_t . into the
                     // input's gradient tile, d r_t = (dZ W)_t . feat_t: one chain per tile, all Temporal buckets of the level in one launch
                     stair_tile_mlp_args a = {};
-                    a.cnt = c; a.T = T; a.H = H; a.ln_eps = 1e-5f;
+                    a.cnt = c; a.T = T; a.H = H; a.ln_eps = 1e-5f; a.len = T > 64 ? LEN : nullptr;
                     a.X = g_map; a.x_gstride = TH; a.x_idx = I4;
                     a.ln_bwd = 1; a.in_mask = svA; a.in_mask_gstride = TH; a.in_scale = inv_keep; a.save_in = gA;
                     a.gamma = W.ln_w; a.dgamma = W.dln_w; a.dbeta = W.dln_b;
@@ -3243,6 +3250,16 @@ extern "C" int stair_ctx_set_option(stair_ctx *ctx, int32_t option, int32_t valu
 extern "C" int stair_ctx_set_tile_pack(stair_ctx *ctx, int32_t value) {
     STAIR_CHECK(ctx, "null context");
     ctx->policy.tile_pack = value < 0 ? -1 : (value != 0);
+    return 0;
+}
+extern "C" int stair_ctx_set_tile_split(stair_ctx *ctx, int32_t value) {
+    STAIR_CHECK(ctx, "null context");
+    ctx->policy.tile_split = value < 0 ? -1 : (value != 0);
+    return 0;
+}
+extern "C" int stair_ctx_get_tile_split(const stair_ctx *ctx, int32_t *value) {
+    STAIR_CHECK(ctx && value, "null argument");
+    *value = ctx->policy.tile_split;
     return 0;
 }
 extern "C" int stair_ctx_get_tile_pack(const stair_ctx *ctx, int32_t *value) {

@@ -1,6 +1,7 @@
 // Fused per-clip tile operators: one workgroup carries one [T, H] tile (T <= 64 frames of one module instance, H = 512)
 // through up to three Linear layers and the module's tile-local tail WITHOUT the intermediates leaving the CU.
 // Clips of T <= 32 frames share a tile, 64 / T instances each (the PACK kernel forms; stair_set_tile_pack).
+// Clips of 64 < T <= 141 frames run as ceil(T / 64) tiles of 64 rows each (the SPLIT kernel forms; stair_set_tile_split).
 //
 // Replaces, per module of /root/reference/video_nmn/modules.py, the launch sequences GEMM -> HBM -> GEMM -> HBM -> row kernel:
 //   Localize   (:199-217)  Lin . ReLU . Lin on the tile, then (cos(f_t, k_j) + 1) * 0.49 against the K keyword rows
@@ -74,7 +75,8 @@ struct TmArg {
     const float *kb; const int32_t *pair_first, *pair_cnt, *att_idx; float *att;
     const int32_t *len;
     int32_t cnt, T, H;
-    int32_t pack;                // instances per tile (packed launches; 1 otherwise) -- sits in what was padding
+    int32_t pack;                // instances per tile (packed launches; 1 otherwise) -- sits in what was padding.  SPLIT launches: the
+                                 // segments per instance, ceil(T / 64)
     const float *act_mask[3]; float act_scale;
     const float *in_mask; int64_t in_mask_gstride; const int32_t *in_mask_idx; float in_scale; int32_t x_broadcast;
     float *save_in;
@@ -184,9 +186,24 @@ __device__ __forceinline__ int tm_fresh_v(int v) {
 // (lane R = row R) into small LDS tables (pk_*); a row's entry is wave-uniform (row = wave + 8 j), so it is read back into SGPRs.
 // Rows of instances >= cnt and rows >= P T do not exist: their entries point at row 0 of the tile (read, zeroed, never written).
 // The relu' bit masks stay indexed by TILE number: a packed chain reads what the packed forward launch of the same bucket wrote.
-template <bool NT, int KIND, bool PACK = false>
+//
+// SPLIT (forms 0, 2, 3): an instance of T > 64 frames runs as S = ceil(T / 64) SEGMENTS, segment g = frames 64 g .. min(64 g + 64, T) - 1,
+// and a bucket has cnt S tiles (tile = instance * S + segment; TmArg::pack carries S).  Every row of a tile belongs to ONE instance, so
+// nothing of the packed forms' tables is needed: the instance's lookups (x_idx, out_idx, extra, pair_*, len) are shared by its
+// segments, every [cnt, T, H] buffer and every per-frame array is entered 64 g rows / frames further on, and the MFMA loop does
+// not know.  The relu' bit masks stay indexed by TILE number, now (instance, segment).  The one tail that crosses segments is
+// Filter's sum over frames: a SUM_ROWS bucket's work item is the INSTANCE, whose segments this workgroup walks in order with the
+// running sum in a register -- a fixed-order sum, nothing crosses workgroups.
+// A segment behind its clip's end (ragged plans: 64 g >= len) is skipped here: it loads nothing and runs NO k loop.  Everything
+// a live segment writes is still written, as ZEROS, by tile_split_pad_kernel, which the launcher runs ahead of this kernel: the saved activations and dZ rows (the weight-gradient products read all cnt T rows of them),
+// the relu' bits, rs_out, and the rows / values of the STORE, LAYERNORM, COSINE and ROWDOT_SIGMOID tails; a chain tail that would
+// ADD adds nothing, one that stores first (STAIR_TILE_STORE_FIRST) stores zeros.  These are frames behind the clip's end: no
+// operator mixes them into a live frame and a plan zeroes them in its node outputs at the end of the pass anyway.
+template <bool NT, int KIND, bool PACK = false, bool SPLIT = false>
 __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
     static_assert(!PACK || KIND != 1, "vector-level tiles hold 64 instances already");
+    static_assert(!SPLIT || (KIND != 1 && !PACK), "segments are a map-level form of their own");
+    static_assert((kTileSplitMaxFrames + TM_ROWS - 1) / TM_ROWS <= 3, "the segment quotient below is written for S <= 3");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float *F = reinterpret_cast<float *>(lds);
     // per-row tables of a packed tile.  pk_tf: bits 0..5 the frame to READ for the input row (0 where the row is zeroed), 16..21 the
@@ -211,19 +228,26 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #define TM_TID() (64 * wave + TM_LANE())
     const int total = pp.first[pp.nb];
     __shared__ int next_work;
+    // SPLIT, SUM_ROWS buckets: the next segment of the instance in hand (0: take a new work item), the extra trips through the
+    // loop that walking cost, and the running sum of column tid
+    int walk_next = 0, walked = 0, walk_w = 0;
+    float walk_sum = 0.f;
     // Work items = tiles of all buckets of the launch, handed out through one atomic counter: a workgroup that finishes a
     // one-layer tile takes the next item while another is still in a three-layer one, and the last partial round of one
     // bucket is filled with the next bucket's tiles (the buckets are listed by decreasing layer count).
     for (int it = 0;; ++it) {
         int w;
         TM_SYNC();                          // the previous tile's tail has finished reading the staging (and next_work)
+        if (SPLIT && walk_next > 0) {
+            w = walk_w; ++walked;           // the instance in hand, its next segment
+        } else
         if (pp.counter) {
             if (TM_TID() == 0) next_work = (int)atomicAdd(pp.counter, 1u);
             TM_SYNC();
             w = __builtin_amdgcn_readfirstlane(next_work);       // uniform BY CONSTRUCTION: says so, so that everything derived from it
                                                                  // (argument block, tile pointers) lives in SGPRs, not in 64-bit VGPR pairs
         } else {
-            w = blockIdx.x + it * gridDim.x;
+            w = blockIdx.x + (SPLIT ? it - walked : it) * gridDim.x;
         }
         // UNSIGNED: whatever the head word held (a ticket >= 2^31 read as a negative int passed the signed test and indexed the
         // bucket table and the tile pointers out of bounds), a workgroup only ever touches tiles 0 .. total - 1
@@ -232,7 +256,23 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #pragma unroll
         for (int j = 1; j < TM_MAXB; ++j) bsel += (j < pp.nb && w >= pp.first[j]) ? 1 : 0;
         const TmArg &p = pp.a[bsel];
-        const int inst = w - pp.first[bsel];
+        // SPLIT: `inst` is the TILE number (what the relu' bits are indexed by), `ii` the instance whose lookups the tile shares,
+        // sfr0 its first frame; T (below) the rows of the segment that exist
+        const int nsg = SPLIT ? p.pack : 1;
+        const bool walk = SPLIT && KIND == 0 && p.tail == STAIR_TILE_SUM_ROWS;
+        const int item = w - pp.first[bsel];
+        // (S <= 3: the quotient by shift / multiply-high on the scalar unit, not the vector unit's division sequence)
+        const int ii = SPLIT ? (walk || nsg == 1 ? item : (nsg == 2 ? item >> 1 : (int)(__umulhi((unsigned)item, 0xAAAAAAABu) >> 1))) : item;
+        const int sgn = SPLIT ? (walk ? walk_next : item - ii * nsg) : 0;
+        const int sfr0 = SPLIT ? TM_ROWS * sgn : 0;
+        const int inst = SPLIT ? ii * nsg + sgn : item;
+        if (SPLIT) walk_w = w;
+        // SPLIT: the clip's frames in this segment, and whether it has none (a segment behind the clip's end)
+        const int seg_rows = SPLIT ? min(TM_ROWS, p.T - sfr0) : 0;
+        const int seg_len = SPLIT ? (p.len ? max(0, min(seg_rows, __builtin_amdgcn_readfirstlane(p.len[ii]) - sfr0)) : seg_rows) : 0;
+        const bool seg_empty = SPLIT && seg_len == 0;
+        // (nothing more in THIS kernel: a branch that wrote the zeros here cost the chain form 60 spilled registers)
+        if (SPLIT && seg_empty) continue;
         // the lane id, re-derived per tile from an opaque copy: the dozens of lane-dependent LDS / row offsets below are then computed
         // where they are used instead of being hoisted out of this (persistent) loop and kept alive -- or spilled -- across it
         const int lane = tm_fresh_v(TM_LANE());
@@ -251,10 +291,10 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
         // packed tiles: `inst` is the TILE number, pkI0 its first instance, pkN the instances it holds; T = the rows that exist
         const int pkI0 = PACK ? inst * p.pack : 0;
         const int pkN = PACK ? min(p.pack, p.cnt - pkI0) : 1;
-        const int T = PACK ? pkN * p.T : (vpack ? min(TM_ROWS, p.vec_cnt - TM_ROWS * inst) : p.T);
+        const int T = PACK ? pkN * p.T : (vpack ? min(TM_ROWS, p.vec_cnt - TM_ROWS * inst) : (SPLIT ? min(TM_ROWS, p.T - sfr0) : p.T));
         const int Ts = vpack ? TM_ROWS : p.T;            // rows between two tiles in the [cnt, T, H] save / mask buffers
         // first row of the tile in the [cnt, T, H] buffers
-#define TM_ROWBASE (PACK ? (int64_t)pkI0 * p.T : (int64_t)inst * Ts)
+#define TM_ROWBASE (PACK ? (int64_t)pkI0 * p.T : (SPLIT ? (int64_t)ii * p.T + sfr0 : (int64_t)inst * Ts))
         const int nseg = vpack == 0 ? 1 : (vpack == 1 ? 2 : 3);
         const bool xbc = KIND == 3 && p.x_broadcast;
         if (PACK) {
@@ -293,13 +333,15 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             TM_SYNC();
         }
         // ---- the input tile: fp32 rows -> (row scale) -> bf16 hi / lo image ------------------------------------------
-        const float *x = PACK ? nullptr : tm_fresh(p.X + (int64_t)(p.x_idx ? __builtin_amdgcn_readfirstlane(p.x_idx[inst]) : inst) * p.x_gstride);
-        const float *rsrow = PACK ? nullptr : (KIND == 0 && p.row_scale ? p.row_scale + (int64_t)(p.rs_idx ? __builtin_amdgcn_readfirstlane(p.rs_idx[inst]) : inst) * T : nullptr);
+        // (SPLIT: the bases enter the instance's rows / per-frame values at the segment's first frame; a broadcast input is one row)
+        const float *x = PACK ? nullptr : tm_fresh(p.X + (int64_t)(p.x_idx ? __builtin_amdgcn_readfirstlane(p.x_idx[ii]) : ii) * p.x_gstride + (SPLIT && !xbc ? (int64_t)sfr0 * TM_H : 0));
+        const float *rsrow = PACK ? nullptr : (KIND == 0 && p.row_scale ? p.row_scale + (int64_t)(p.rs_idx ? __builtin_amdgcn_readfirstlane(p.rs_idx[ii]) : ii) * (SPLIT ? p.T : T) + sfr0 : nullptr);
         const bool has_rs = PACK ? (KIND == 0 && p.row_scale != nullptr) : rsrow != nullptr;
         // (a NULL must stay a visible NULL: through tm_fresh the forward kernel kept the whole mask path, and its registers)
         const float *imask = PACK ? ((KIND == 2 || KIND == 3) && p.in_mask ? p.in_mask : nullptr)
-                                  : ((KIND == 2 || KIND == 3) && p.in_mask ? tm_fresh(p.in_mask + (int64_t)(p.in_mask_idx ? __builtin_amdgcn_readfirstlane(p.in_mask_idx[inst]) : inst) * p.in_mask_gstride) : nullptr);
-        const int Lrows = PACK ? T : (xbc ? (p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T) : T);     // a broadcast row fills the clip's own frames only
+                                  : ((KIND == 2 || KIND == 3) && p.in_mask ? tm_fresh(p.in_mask + (int64_t)(p.in_mask_idx ? __builtin_amdgcn_readfirstlane(p.in_mask_idx[ii]) : ii) * p.in_mask_gstride + (SPLIT ? (int64_t)sfr0 * TM_H : 0)) : nullptr);
+        const int Lrows = PACK ? T : (SPLIT ? (xbc ? seg_len : T)
+                                            : (xbc ? (p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T) : T));     // a broadcast row fills the clip's own frames only
         // vector-level modules: row t of the tile is H-wide block `seg` of the concatenation built from the two operand rows
         // of instance 64 inst + t (never materialised for the GEMM; cat_save keeps it for the weight gradient)
         auto build_vec_image = [&](const int seg) {
@@ -595,7 +637,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                             if (act == 1) z[i] = fmaxf(z[i], 0.0f);
                         }
                         if (KIND == 0 && dsite) {       // nn.Dropout behind this activation: the bits stair_dropout_fwd draws for the [cnt, T, H] rows
-                            const unsigned long long e0 = ((PACK ? (unsigned long long)pkI0 : (unsigned long long)inst) * p.T + t) * p.H + (64 * wave + 32 * nt + 8 * q + 4 * h_e);
+                            const unsigned long long e0 = ((PACK ? (unsigned long long)pkI0 : (unsigned long long)ii) * p.T + sfr0 + t) * p.H + (64 * wave + 32 * nt + 8 * q + 4 * h_e);
                             const unsigned long long bits4 = drop_hash4(pp.drop_seed, dsite - 1u, e0 >> 2);      // e0 % 4 == 0 (H % 4 == 0)
 #pragma unroll
                             for (int i = 0; i < 4; ++i) z[i] = drop_keep(bits4, i, pp.drop_thresh) ? z[i] * pp.drop_inv_keep : 0.0f;
@@ -632,7 +674,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 float rd_b = 0.f;
                 if (rowdot) {
                     w0 = *reinterpret_cast<const v4f *>(p.vw + 8 * lane_e); w1 = *reinterpret_cast<const v4f *>(p.vw + 8 * lane_e + 4);
-                    rd_b = PACK ? p.vb[0] : p.vb[0] + (p.extra ? p.extra[inst] : 0.f);       // (packed: extra is the ROW's instance's)
+                    rd_b = PACK ? p.vb[0] : p.vb[0] + (p.extra ? p.extra[ii] : 0.f);       // (packed: extra is the ROW's instance's)
                 }
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
@@ -674,7 +716,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) d += a[i] * w0[i] + b[i] * w1[i];
                                 const float at = sigmoid_acc(wave_sum(d) + (PACK ? rd_b + pk_ex[t] : rd_b));
-                                if (p.rs_out && lane_e == 0) p.rs_out[(PACK ? (int64_t)pkI0 * p.T : (int64_t)inst * T) + t] = at;
+                                if (p.rs_out && lane_e == 0) p.rs_out[(PACK ? (int64_t)pkI0 * p.T : (SPLIT ? (int64_t)ii * p.T + sfr0 : (int64_t)inst * T)) + t] = at;
                                 a *= at; b *= at;
                             }
                         }
@@ -718,9 +760,10 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             p.save_bits[p.n_layers - 1][(int64_t)inst * TM_H + 64 * wave + lane] = obits;
         }
         // backward chains (forms 2 and 3): bit STAIR_TILE_STORE_FIRST of an out_idx entry marks a target nothing has written yet
-        const int oraw = PACK ? 0 : (p.out_idx ? __builtin_amdgcn_readfirstlane(p.out_idx[inst]) : (int)inst);
+        const int oraw = PACK ? 0 : (p.out_idx ? __builtin_amdgcn_readfirstlane(p.out_idx[ii]) : (int)ii);
         const bool ofirst = KIND >= 2 && (oraw & STAIR_TILE_STORE_FIRST) != 0;
         const int64_t oslot = KIND >= 2 ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
+        const int64_t orow0 = SPLIT ? (int64_t)sfr0 * TM_H : 0;       // the segment's first row in the instance's [T, H] target
         if (PACK) {
             // ---- the tails of a packed tile: the same arithmetic per row, every row at its own instance's targets ----------------
             // (a copy of the unpacked tails below with per-row addresses, so that the unpacked instantiations compile as they did:
@@ -955,11 +998,11 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
         if (KIND == 2) {
             // tail ROWSCALE_ADJ: the staged rows are G = dZ W, the gradient of the SCALED input r_t feat_t of the dense layer:
             // d feat_t += r_t G_t (one dword per lane, 256 contiguous bytes per wave-instruction), d r_t += G_t . feat_t
-            const float *feat = tm_fresh(p.adj_feat + (int64_t)(p.adj_feat_idx ? __builtin_amdgcn_readfirstlane(p.adj_feat_idx[inst]) : inst) * p.adj_feat_gstride);
-            const int64_t rslot = p.adj_rs_idx ? __builtin_amdgcn_readfirstlane(p.adj_rs_idx[inst]) : inst;
-            const float *rs = p.adj_rs + rslot * T;
-            float *drs = p.adj_drs + rslot * T;
-            float *dst = tm_fresh(p.out + oslot * p.out_gstride);
+            const float *feat = tm_fresh(p.adj_feat + (int64_t)(p.adj_feat_idx ? __builtin_amdgcn_readfirstlane(p.adj_feat_idx[ii]) : ii) * p.adj_feat_gstride + (SPLIT ? (int64_t)sfr0 * TM_H : 0));
+            const int64_t rslot = p.adj_rs_idx ? __builtin_amdgcn_readfirstlane(p.adj_rs_idx[ii]) : ii;
+            const float *rs = p.adj_rs + rslot * (SPLIT ? p.T : T) + sfr0;
+            float *drs = p.adj_drs + rslot * (SPLIT ? p.T : T) + sfr0;
+            float *dst = tm_fresh(p.out + oslot * p.out_gstride + (SPLIT ? (int64_t)sfr0 * TM_H : 0));
             __builtin_amdgcn_sched_barrier(0);      // the loads stay below the epilogue (hoisted, they cost registers there)
             v4f f0[8], f1[8];
             float rr[8];
@@ -1028,7 +1071,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                                                              : (KIND != 3 && p.tail == STAIR_TILE_ACCUMULATE ? STAIR_TILE_NONE : p.tail)) {
             case STAIR_TILE_STORE:
                 for (int t = wave; t < T; t += 8) {
-                    float *dst = p.out + oslot * p.out_gstride + (int64_t)t * TM_H;
+                    float *dst = p.out + oslot * p.out_gstride + orow0 + (int64_t)t * TM_H;
                     tm_st<NT>(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane));
                     tm_st<NT>(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane));
                 }
@@ -1049,7 +1092,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     // the first contribution of the pass to a tile that was not cleared (stair_plan_backward marks it): what the
                     // read - add - write below leaves in a zeroed tile, without the 128 KB read (a branch of its own, like that one)
                     for (int t = wave; t < T; t += 8) {
-                        float *dst = p.out + oslot * p.out_gstride + (int64_t)t * TM_H;
+                        float *dst = p.out + oslot * p.out_gstride + orow0 + (int64_t)t * TM_H;
                         *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane);
                         *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
                     }
@@ -1060,7 +1103,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     // gives every same-level reader of a slot a target of its own): whole rows read, added and written back, every
                     // load of the tile's rows in flight at once -- float atomics retire 256 B per ~50 ns and CU (1.3 TB/s chip-wide,
                     // MI355X_MICROARCH.md "Global float atomics"): 25 us per tile, as long as two layers of the chain
-                    float *dst = tm_fresh(p.out + oslot * p.out_gstride);
+                    float *dst = tm_fresh(p.out + oslot * p.out_gstride + orow0);
                     __builtin_amdgcn_sched_barrier(0);          // the loads stay below the epilogue (hoisted, they cost registers there)
                     v4f o0[8], o1[8];
 #pragma unroll
@@ -1080,28 +1123,32 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     break;
                 }
                 for (int t = wave; t < T; t += 8) {
-                    float *dst = p.out + oslot * p.out_gstride + (int64_t)t * TM_H;
+                    float *dst = p.out + oslot * p.out_gstride + orow0 + (int64_t)t * TM_H;
 #pragma unroll
                     for (int c = 0; c < TM_H / 64; ++c) unsafeAtomicAdd(dst + 64 * c + lane, F[t * TM_FLD + 64 * c + lane]);
                 }
                 break;
             case STAIR_TILE_SUM_ROWS: {               // Filter: sum over the clip's own frames (modules.py:374,376)
                 if (KIND == 3) break;
-                const int L = p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T;
+                const int L = SPLIT ? seg_len : (p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T);
                 const int col = tm_fresh_v(TM_TID());       // (not hoisted out of the tile loop: three values kept that way went to scratch)
-                float s = 0.f;
+                float s = SPLIT && sgn > 0 ? walk_sum : 0.f;    // (SPLIT: the instance's frames in order, segment after segment)
                 for (int t = 0; t < L; ++t) s += F[t * TM_FLD + col];
+                // (the walk ends with the clip's last live segment: the ones behind it are skipped above)
+                const int nlive = SPLIT ? (p.len ? max(1, (min(__builtin_amdgcn_readfirstlane(p.len[ii]), p.T) + TM_ROWS - 1) / TM_ROWS) : nsg) : 1;
+                if (SPLIT && sgn + 1 < nlive) { walk_sum = s; walk_next = sgn + 1; break; }
+                if (SPLIT) walk_next = 0;
                 p.out[oslot * p.out_gstride + col] = s;
                 break;
             }
             case STAIR_TILE_COSINE: {                 // Localize: (cos(f_t, k_j) + 1) * 0.49, nn.CosineSimilarity eps 1e-8
                 if (KIND == 3) break;
-                const int first = __builtin_amdgcn_readfirstlane(p.pair_first[inst]), cn = __builtin_amdgcn_readfirstlane(p.pair_cnt[inst]);
+                const int first = __builtin_amdgcn_readfirstlane(p.pair_first[ii]), cn = __builtin_amdgcn_readfirstlane(p.pair_cnt[ii]);
                 // pair-major: a keyword row (and its norm, and its attention slot) is fetched once, not once per frame
                 for (int j = 0; j < cn; ++j) {
                     const float *k = p.kb + (int64_t)(first + j) * TM_H;
                     const v4f k0 = *reinterpret_cast<const v4f *>(k + 4 * lane), k1 = *reinterpret_cast<const v4f *>(k + 256 + 4 * lane);
-                    float *arow = p.att + (int64_t)p.att_idx[first + j] * T;
+                    float *arow = p.att + (int64_t)p.att_idx[first + j] * (SPLIT ? p.T : T) + sfr0;
                     float nk = 0.f;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) nk += k0[i] * k0[i] + k1[i] * k1[i];
@@ -1124,14 +1171,14 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             case STAIR_TILE_ROWDOT_SIGMOID: {         // HasItem: sigmoid(w . row + b) (modules.py:131-137)
                 if (KIND == 3) break;
                 const v4f w0 = *reinterpret_cast<const v4f *>(p.vw + 4 * lane), w1 = *reinterpret_cast<const v4f *>(p.vw + 256 + 4 * lane);
-                const float off = p.vb[0] + (p.extra ? p.extra[inst] : 0.f);
+                const float off = p.vb[0] + (p.extra ? p.extra[ii] : 0.f);
                 for (int t = wave; t < T; t += 8) {
                     const v4f f0 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
                     float d = 0.f;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) d += f0[i] * w0[i] + f1[i] * w1[i];
                     d = wave_sum(d);
-                    if (lane == 0) p.out[oslot * p.out_gstride + t] = sigmoid_acc(d + off);
+                    if (lane == 0) p.out[oslot * p.out_gstride + sfr0 + t] = sigmoid_acc(d + off);
                 }
                 break;
             }
@@ -1151,7 +1198,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     const float rstd = rsqrtf(wave_sum(sq) / (float)TM_H + p.ln_eps);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { f0[i] = (f0[i] - mean) * rstd * g0[i] + b0[i]; f1[i] = (f1[i] - mean) * rstd * g1[i] + b1[i]; }
-                    float *dst = p.out + oslot * p.out_gstride + (int64_t)t * TM_H;
+                    float *dst = p.out + oslot * p.out_gstride + orow0 + (int64_t)t * TM_H;
                     *reinterpret_cast<v4f *>(dst + 4 * lane) = f0;
                     *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = f1;
                 }
@@ -1180,6 +1227,61 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
     }
 }
 
+// SPLIT launches of ragged plans: the segments behind a clip's end (64 g >= len), which tile_mlp_kernel skips.  A workgroup per
+// tile (counted in TILES, cnt S per bucket, whatever the buckets' work items are); a live tile's workgroup leaves at once.  Zeros wherever the
+// tile's live form writes: the save / save_in rows and relu' bits, rs_out, the rows or values of the storing tails.  A chain tail
+// that adds has nothing to add; Filter's sum (SUM_ROWS) belongs to the live segments -- a clip of no frames at all gets its zero here.
+template <int KIND>
+__global__ __launch_bounds__(512) void tile_split_pad_kernel(TmParams pp) {
+    int tile = blockIdx.x, b = 0;
+    while (b + 1 < pp.nb && tile >= pp.a[b].cnt * pp.a[b].pack) { tile -= pp.a[b].cnt * pp.a[b].pack; ++b; }
+    const TmArg &p = pp.a[b];
+    if (tile >= p.cnt * p.pack || !p.len) return;
+    const int ii = tile / p.pack, sgn = tile - ii * p.pack, sfr0 = TM_ROWS * sgn;
+    const int len = p.len[ii];
+    if (sfr0 < len) return;                             // a live segment: tile_mlp_kernel's
+    const int rows = min(TM_ROWS, p.T - sfr0);          // the segment's rows that exist
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t row0 = (int64_t)ii * p.T + sfr0;      // its first row in the [cnt, T, H] buffers
+    const v4f z4 = {0.f, 0.f, 0.f, 0.f};
+    auto zero_rows = [&](float *base) {
+        for (int t = wave; t < rows; t += 8) {
+            *reinterpret_cast<v4f *>(base + (int64_t)t * TM_H + 4 * lane) = z4;
+            *reinterpret_cast<v4f *>(base + (int64_t)t * TM_H + 256 + 4 * lane) = z4;
+        }
+    };
+    if (KIND >= 2 && p.save_in) zero_rows(p.save_in + row0 * TM_H);
+    for (int l = 0; l < p.n_layers; ++l) {
+        if (p.save[l]) zero_rows(p.save[l] + row0 * TM_H);
+        if (KIND == 0 && p.save_bits[l]) p.save_bits[l][(int64_t)tile * TM_H + tid] = 0ull;
+    }
+    const int oraw = p.out_idx ? p.out_idx[ii] : ii;
+    const int64_t oslot = KIND >= 2 ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
+    if (KIND >= 2) {
+        const bool stores = (KIND == 2 || p.tail == STAIR_TILE_ACCUMULATE) ? (oraw & STAIR_TILE_STORE_FIRST) != 0 : p.tail == STAIR_TILE_STORE;
+        if (stores) zero_rows(p.out + oslot * p.out_gstride + (int64_t)sfr0 * TM_H);
+        return;
+    }
+    if (p.mid_rowdot && p.rs_out && tid < rows) p.rs_out[row0 + tid] = 0.f;
+    switch (p.tail) {
+        case STAIR_TILE_STORE: case STAIR_TILE_LAYERNORM:
+            zero_rows(p.out + oslot * p.out_gstride + (int64_t)sfr0 * TM_H);
+            break;
+        case STAIR_TILE_ROWDOT_SIGMOID:
+            if (tid < rows) p.out[oslot * p.out_gstride + sfr0 + tid] = 0.f;
+            break;
+        case STAIR_TILE_COSINE: {
+            const int first = p.pair_first[ii], cn = p.pair_cnt[ii];
+            for (int j = 0; j < cn; ++j)
+                if (tid < rows) p.att[(int64_t)p.att_idx[first + j] * p.T + sfr0 + tid] = 0.f;
+            break;
+        }
+        case STAIR_TILE_SUM_ROWS:
+            if (sgn == 0) p.out[oslot * p.out_gstride + tid] = 0.f;     // (segment 0 is empty: the clip has no frame)
+            break;
+        default: break;
+    }
+}
 #undef TM_ROWBASE
 #undef TM_PK_S
 #undef TM_PK_FIRST
@@ -1258,9 +1360,19 @@ int tile_pack_setting() {
     return g_tile_pack != 0;
 }
 static int tile_pack_factor(int T, bool on) { return on && T >= 1 && T <= TM_ROWS / 2 ? TM_ROWS / T : 1; }
+// long clips as 64-row segments (the SPLIT kernel forms): the same three levels as the packing switch -- a plan's backward pass
+// forces what its forward pass ran with (TileSplitForce), else the context's override (stair_ctx_set_tile_split), else the process
+static int g_tile_split = 1;        // stair_set_tile_split
+thread_local int tl_tile_split_force = -1;
+int tile_split_setting() {
+    if (tl_tile_split_force >= 0) return tl_tile_split_force != 0;
+    if (tl_policy && tl_policy->tile_split >= 0) return tl_policy->tile_split != 0;
+    return g_tile_split != 0;
+}
+static int tile_segments(int T, bool on) { return on && T > TM_ROWS ? (T + TM_ROWS - 1) / TM_ROWS : 1; }
 bool tile_mlp_usable(int H, int T) {
     const bool on = policy_or(STAIR_OPT_TILE_MLP, g_tile_on) != 0;
-    return on && H == TM_H && T >= 1 && T <= TM_ROWS && matmul_mode() == STAIR_MATMUL_BF16X3;
+    return on && H == TM_H && T >= 1 && T <= (tile_split_setting() ? kTileSplitMaxFrames : TM_ROWS) && matmul_mode() == STAIR_MATMUL_BF16X3;
 }
 
 static int tile_mlp_check(const stair_tile_mlp_args &a) {
@@ -1274,7 +1386,8 @@ static int tile_mlp_check(const stair_tile_mlp_args &a) {
         STAIR_CHECK(a.tail == STAIR_TILE_STORE_ROWS || a.tail == STAIR_TILE_NONE, "vector-level tiles end in STORE_ROWS");
         for (int l = 0; l < a.n_layers; ++l) STAIR_CHECK(a.act[l] != 3, "no backward chains on vector-level tiles");
     } else {
-        STAIR_CHECK(a.T >= 1 && a.T <= TM_ROWS, "a tile holds 1..64 frames");
+        STAIR_CHECK(a.T >= 1 && (a.T <= TM_ROWS || tile_split_setting()), "a tile holds 1..64 frames");
+        STAIR_CHECK(a.T <= kTileSplitMaxFrames, "the tile operators take clips of at most 141 frames (64-row segments)");
         STAIR_CHECK(a.X && a.cnt >= 0, "null input");
         STAIR_CHECK(a.tail != STAIR_TILE_STORE_ROWS, "STORE_ROWS is the vector-level tail");
     }
@@ -1339,6 +1452,9 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
+        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 3, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         int v = 256;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         cus[dev] = v;
@@ -1388,27 +1504,48 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
             }
         }
         std::stable_sort(order, order + m, [&](int x, int y) { return rounds(x) > rounds(y); });    // long tiles first
-        bool packed = false;
+        bool packed = false, split = false;
+        // clips of more than 64 frames (admitted by tile_mlp_check only while the segment switch is on) run as segments: the SPLIT
+        // form for the whole launch -- a bucket of T <= 64 in it is one segment per instance
+        for (int j = 0; j < m; ++j) split = split || (kind != 1 && args[order[j]].T > TM_ROWS);
+        int64_t tiles = 0;
         for (int j = 0; j < m; ++j) {
             const stair_tile_mlp_args &a = args[order[j]];
-            const int P = kind == 1 ? 1 : tile_pack_factor(a.T, pack_on);
+            const int P = kind == 1 || split ? 1 : tile_pack_factor(a.T, pack_on);
+            const int S = split ? tile_segments(a.T, true) : 1;
             packed = packed || P > 1;
-            pp.a[j] = tm_arg(a, kind, P);
-            pp.first[j + 1] = pp.first[j] + (a.cnt + P - 1) / P;          // work items are TILES
+            pp.a[j] = tm_arg(a, kind, split ? S : P);
+            // work items are TILES; a SUM_ROWS bucket of a split launch hands out INSTANCES (one workgroup walks the segments)
+            const bool walk = split && kind == 0 && a.tail == STAIR_TILE_SUM_ROWS;
+            pp.first[j + 1] = pp.first[j] + (split ? (walk ? a.cnt : a.cnt * S) : (a.cnt + P - 1) / P);
+            tiles += split ? (int64_t)a.cnt * S : (a.cnt + P - 1) / P;
             const int64_t M = a.vec_pack ? a.vec_cnt : (int64_t)a.cnt * a.T;
             const int kl = rounds(order[j]);
             STAIR_ACCT_MFMA("tile_mlp", (M * TM_H * 2 + (int64_t)kl * TM_H * TM_H) * 4, 2 * M * TM_H * TM_H * kl);
         }
         for (int j = m; j < TM_MAXB; ++j) { pp.a[j] = pp.a[0]; pp.first[j + 1] = pp.first[m]; }
         pp.nb = m;
-        g_tile_work_items.fetch_add(pp.first[m], std::memory_order_relaxed);
+        g_tile_work_items.fetch_add(tiles, std::memory_order_relaxed);
         const int grid = std::min(pp.first[m], cus[dev]);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (g_tile_timing) {
             STAIR_HIP(hipEventCreate(&e0)); STAIR_HIP(hipEventCreate(&e1));
             STAIR_HIP(hipEventRecord(e0, s));
         }
-        if (packed && kind == 0) hipLaunchKernelGGL((tile_mlp_kernel<true, 0, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        if (split) {            // ragged plans: zeros for the segments behind a clip's end, which the tile kernel skips
+            bool any_len = false;
+            for (int j = 0; j < m; ++j) any_len = any_len || args[order[j]].len != nullptr;
+            if (any_len) {
+                if (kind == 0) hipLaunchKernelGGL((tile_split_pad_kernel<0>), dim3((unsigned)tiles), dim3(512), 0, s, pp);
+                else if (kind == 2) hipLaunchKernelGGL((tile_split_pad_kernel<2>), dim3((unsigned)tiles), dim3(512), 0, s, pp);
+                else hipLaunchKernelGGL((tile_split_pad_kernel<3>), dim3((unsigned)tiles), dim3(512), 0, s, pp);
+                STAIR_LAUNCH_CHECK();
+            }
+        }
+        if (split && kind == 0) hipLaunchKernelGGL((tile_mlp_kernel<true, 0, false, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        else if (split && kind == 2) hipLaunchKernelGGL((tile_mlp_kernel<true, 2, false, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        else if (split && kind == 3) hipLaunchKernelGGL((tile_mlp_kernel<true, 3, false, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        else if (packed && kind == 0) hipLaunchKernelGGL((tile_mlp_kernel<true, 0, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
         else if (packed && kind == 2) hipLaunchKernelGGL((tile_mlp_kernel<true, 2, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
         else if (packed && kind == 3) hipLaunchKernelGGL((tile_mlp_kernel<true, 3, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
         else if (vec) hipLaunchKernelGGL((tile_mlp_kernel<false, 1>), dim3(grid), dim3(512), TM_LDS, s, pp);
@@ -1433,6 +1570,10 @@ extern "C" int stair_set_tile_mlp(int32_t on) { stair::g_tile_on = on; return 0;
 extern "C" int stair_set_tile_pack(int32_t on) { stair::g_tile_pack = on < 0 ? 1 : (on != 0); return 0; }
 
 extern "C" int32_t stair_tile_pack_factor(int32_t T) { return stair::tile_pack_factor(T, stair::g_tile_pack != 0); }
+
+extern "C" int stair_set_tile_split(int32_t on) { stair::g_tile_split = on < 0 ? 1 : (on != 0); return 0; }
+
+extern "C" int32_t stair_tile_segments(int32_t T) { return stair::tile_segments(T, stair::g_tile_split != 0); }
 
 extern "C" int stair_tile_work_items(int64_t *items, int32_t reset) {
     const int64_t v = reset ? stair::g_tile_work_items.exchange(0) : stair::g_tile_work_items.load();

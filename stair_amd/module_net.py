@@ -363,10 +363,14 @@ class VideoNMN(nn.Module):
     def set_option(self, name, value):
         """Per-context override of a process-wide library setting (stair_ctx_set_option): 'matmul_mode' ('f32' / 'bf16x3' / 'bf16'),
         'tile_mlp', 'tile_queue', 'vec_group' (0 / 1), 'tn_slab_min_rows', and 'tile_pack' (0 / 1: clips of at most 32 frames share
-        a 64-row tile; stair_ctx_set_tile_pack); None restores the process default.  In force for this
+        a 64-row tile; stair_ctx_set_tile_pack) and 'tile_split' (0 / 1: clips of more than 64 frames run on the tile operators as
+        64-row segments; stair_ctx_set_tile_split); None restores the process default.  In force for this
         model's forward and backward passes only: other models of the process keep their own settings."""
         if name == 'tile_pack':
             check(lib.stair_ctx_set_tile_pack(self._ctx, -1 if value is None else int(value)))
+            return
+        if name == 'tile_split':
+            check(lib.stair_ctx_set_tile_split(self._ctx, -1 if value is None else int(value)))
             return
         if name == 'matmul_mode' and isinstance(value, str):
             value = self.MATMUL_MODES[value]
