@@ -92,10 +92,11 @@ extern bool g_acct_on;
 // stair_set_tile_queue, stair_set_tn_slab_min_rows) and the environment give the DEFAULTS; a context may override each of them, and
 // its values are in force on the calling thread for the duration of stair_plan_run / stair_plan_backward on that context (PolicyScope):
 // two contexts of one process -- two GPUs driven from two threads, or two configurations on one GPU -- do not see each other's settings.
+enum { TILE_PACK = 0, TILE_SPLIT = 1 };      // the tile operators' two on/off switches (TileSwitch below)
+struct TileSwitches { int v[2] = {-1, -1}; };
 struct Policy {
     int v[STAIR_OPT_COUNT];
-    int tile_pack = -1;              // stair_ctx_set_tile_pack (a switch of its own: the option ids of stair_option are closed)
-    int tile_split = -1;             // stair_ctx_set_tile_split (likewise)
+    TileSwitches tile;               // stair_ctx_set_tile_pack / _split (switches of their own: the option ids of stair_option are closed)
     Policy() { for (int &x : v) x = -1; }
 };       // -1: inherit the process default
 extern thread_local const Policy *tl_policy;
@@ -166,24 +167,30 @@ int launch_gemm_tn_batch(const stair_gemm_tn_args *a, int n, hipStream_t s);
 int launch_tile_mlp(const stair_tile_mlp_args &a, hipStream_t s);          // csrc/tile_mlp.hip
 int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *counter, hipStream_t s);   // <= 8 buckets, one launch
 bool tile_mlp_usable(int H, int T);
-// short clips packed into one tile (csrc/tile_mlp.hip): the setting in force on this thread, and a scope that pins it -- a plan's
-// backward chains read the relu' bits by TILE number, so they run with the packing of the forward pass that wrote them
-int tile_pack_setting();
-extern thread_local int tl_tile_pack_force;
-struct TilePackForce {
-    int prev;
-    explicit TilePackForce(int v) : prev(tl_tile_pack_force) { tl_tile_pack_force = v; }
-    ~TilePackForce() { tl_tile_pack_force = prev; }
+// The tile operators' switches (csrc/tile_mlp.hip): g_tile_pack -- clips of at most 32 frames share a 64-row tile -- and g_tile_split
+// -- clips of more than 64 frames run as 64-row segments.  Each is one on/off setting on three levels: what a TileSwitchForce pins on
+// this thread, else the context's override (Policy::tile), else the process default.  A plan's backward chains read the relu' bits
+// by TILE number, so its backward pass pins both to what the forward pass that wrote them ran with.
+extern thread_local TileSwitches tl_tile_force;
+struct TileSwitch {
+    int id;                      // TILE_PACK / TILE_SPLIT: its slot in a TileSwitches
+    int process = 1;             // the process default (stair_set_tile_pack / _split; < 0 restores it: on)
+    void set_process(int on) { process = on < 0 ? 1 : (on != 0); }
+    bool on() const {            // the setting in force on this thread
+        if (tl_tile_force.v[id] >= 0) return tl_tile_force.v[id] != 0;
+        if (tl_policy && tl_policy->tile.v[id] >= 0) return tl_policy->tile.v[id] != 0;
+        return process != 0;
+    }
 };
-// clips of more than 64 frames as 64-row segments (csrc/tile_mlp.hip): the bits are indexed by (instance, segment), so the same rule
+extern TileSwitch g_tile_pack, g_tile_split;
+inline TileSwitches tile_switches_now() { return {{g_tile_pack.on(), g_tile_split.on()}}; }
+struct TileSwitchForce {
+    TileSwitches prev;
+    explicit TileSwitchForce(const TileSwitches &v) : prev(tl_tile_force) { tl_tile_force = v; }
+    ~TileSwitchForce() { tl_tile_force = prev; }
+};
 constexpr int kTileSplitMaxFrames = 141;       // the library's frame limit (stair_plan_build)
-int tile_split_setting();
-extern thread_local int tl_tile_split_force;
-struct TileSplitForce {
-    int prev;
-    explicit TileSplitForce(int v) : prev(tl_tile_split_force) { tl_tile_split_force = v; }
-    ~TileSplitForce() { tl_tile_split_force = prev; }
-};
+int64_t tile_max_tiles(int cnt, int T);        // the tiles of a map-level bucket under the largest layout a pass may choose (relu' bit regions)
 // csrc/vec_group.hip: the row-wise Linear layers of a program level as one launch
 using VgProblem = stair_vec_problem;
 constexpr int VG_FWD = STAIR_VEC_FWD, VG_ADJ = STAIR_VEC_ADJ;

@@ -506,6 +506,15 @@ void pinned_park(PinnedBuf b, hipEvent_t ev) {
 }
 }  // namespace
 
+// Which clips' lengths (ragged plans; NULL: every clip has T frames) a tile bucket carries.  The kernels read len for T <= 64 too
+// (the broadcast rows, the packed tables), so the two rules are not interchangeable:
+//   LEN_ALWAYS         whatever T is: Filter's sum over frames and the two-layer backward chains (mlp_tail_fused, whose input may
+//                      be Filter's broadcast row) stop at the clip's end
+//   LEN_OF_LONG_CLIPS  only when T > 64, where the segments behind a clip's end run no k loop; up to 64 frames the operator
+//                      computes the padding frames as it always did
+enum TileLen { LEN_ALWAYS, LEN_OF_LONG_CLIPS };
+static const int32_t *tile_len(TileLen rule, int T, const int32_t *len) { return rule == LEN_ALWAYS || T > 64 ? len : nullptr; }
+
 struct stair_plan {
     stair_config cfg;
     PinnedBuf pin;                  // page-locked copy of idx, made at the first upload
@@ -519,9 +528,8 @@ struct stair_plan {
     int64_t off_seqv = 0, off_seqt = 0, off_roots = 0, off_lenv = 0;
     bool ragged = false;            // clips of different frame counts in this batch (padded to T; per-instance lengths in col[6] of every T-mixing and every tile operator's bucket)
     bool bits_written = false;      // the last forward run of this (training) plan went through the fused tile operators: Bucket::bit* are valid
-    int tile_split = 1;             // ... and whether clips of more than 64 frames ran as segments (tile_split_setting() of that run)
-    int tile_pack = 0;              // ... and whether its map-level tiles were packed (tile_pack_setting() of that run): the relu' bits are
-                                    // indexed by TILE, so the backward chains of the plan run with the same packing, whatever the switches say by then
+    TileSwitches tile_sw{{0, 1}};   // ... and whether its map-level tiles were packed / its long clips ran as segments (tile_switches_now() of that run):
+                                    // the relu' bits are indexed by TILE, so the backward chains of the plan run with the same, whatever the switches say by then
     std::vector<int32_t> vlen;      // frames per clip [n_vid]
     std::vector<int32_t> pad_map, pad_att;      // ragged plans: (map tile | att row, frames) of every node output of a short clip
     int64_t off_pad_map = 0, off_pad_att = 0;
@@ -1385,7 +1393,7 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
             if (pl->o_wfrag > 0 && b.cnt > 0) {          // the level's backward chains share a launch: no scratch in common
                 if (b.op == STAIR_OP_FILTER) b.gRow = pl->take("gRow", (int64_t)b.cnt * H, 64);
                 if (b.op == STAIR_OP_FILTERFRAME && b.variant != 0) b.dzC = pl->take("dzC", (int64_t)b.cnt * T * H, 64);
-                const int64_t words = (int64_t)b.cnt * ((T + 63) / 64) * 512 * 2;    // 64-bit words, counted in floats, per TILE: (instance, 64-row segment)
+                const int64_t words = tile_max_tiles(b.cnt, T) * 512 * 2;    // 64-bit words, counted in floats, per TILE: (instance, 64-row segment)
                 switch (b.op) {
                     case STAIR_OP_FILTER: b.bitA = pl->take(".bitA", words, 64, bi); b.bitB = pl->take(".bitB", words, 64, bi); break;
                     case STAIR_OP_FILTERFRAME:
@@ -1949,8 +1957,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
     // epilogues)
     const bool fused = pl->o_wfrag > 0 && tile_mlp_usable(H, T);
     pl->bits_written = fused && pl->train;
-    pl->tile_pack = tile_pack_setting();
-    pl->tile_split = tile_split_setting();
+    pl->tile_sw = tile_switches_now();
     auto WF = [&](int slot) { return static_cast<const void *>(ws + pl->o_wfrag + (int64_t)slot * H * H); };
     const WeightIndex &WIX = weight_index();
     if (fused) {
@@ -2019,11 +2026,11 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
         a.tail = STAIR_TILE_STORE_ROWS; a.out = vec; a.out_gstride = H; a.out_row_idx = io;
         return a;
     };
-    // len_: the clips' frames (ragged plans); given to every operator of a long clip, whose segments behind a clip's end run no k loop
-    auto tile_args = [&](const int32_t *x_idx, int cnt_, const int32_t *len_) {
+    // len_: the clips' frames (ragged plans), passed by the bucket's TileLen rule
+    auto tile_args = [&](const int32_t *x_idx, int cnt_, const int32_t *len_, TileLen rule = LEN_OF_LONG_CLIPS) {
         stair_tile_mlp_args a = {};
         a.X = map; a.x_gstride = TH; a.x_idx = x_idx; a.cnt = cnt_; a.T = T; a.H = H; a.ln_eps = 1e-5f;
-        a.len = T > 64 ? len_ : nullptr;
+        a.len = tile_len(rule, T, len_);
         return a;
     };
     // drop_pos: the layer's activation is followed by nn.Dropout, position `drop_pos` of the bucket (the `pos` of drop() below)
@@ -2162,10 +2169,10 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
                 const int v = b.variant;
                 if (fused) {            // both layers and the sum over frames on the tile
                     if (phase == 1) {
-                        stair_tile_mlp_args a = tile_args(I0, c, LEN);
+                        stair_tile_mlp_args a = tile_args(I0, c, LEN, LEN_ALWAYS);         // (the sum stops at the clip's end)
                         tile_layer(a, WF_F0 + v, W.f0[v], 1, tmpA, b.bitA, 0);
                         tile_layer(a, WF_F3 + v, W.f3[v], 1, tmpB, b.bitB, 1);
-                        a.tail = STAIR_TILE_SUM_ROWS; a.out = cat; a.out_gstride = H; a.len = LEN;
+                        a.tail = STAIR_TILE_SUM_ROWS; a.out = cat; a.out_gstride = H;
                         tile_queue.push_back(a);
                         if (grouped) {
                             vg2.push_back(vg_fwd(c, cat, nullptr, H, nullptr, nullptr, 0, VG_IN_A, W.fdense.w, H, W.fdense.b, H, 1, vec, I1, H));
@@ -2534,8 +2541,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                          float *d_video, float *d_question, int32_t flags, stair_stream stream) {
     STAIR_CHECK(ctx && pl && video && question && workspace && (answers || d_logits_in), "null argument");
     PolicyScope policy_scope(&ctx->policy);
-    TilePackForce tile_pack_scope(pl->tile_pack);          // the packing of the forward pass that wrote the saves and bits
-    TileSplitForce tile_split_scope(pl->tile_split);       // ... and its segment setting
+    TileSwitchForce tile_scope(pl->tile_sw);               // the packing and segments of the forward pass that wrote the saves and bits
     STAIR_CHECK(pl->train, "plan was not built with STAIR_PLAN_TRAIN");
     // slab products queued by a pass that failed half-way must not be added into THIS pass's buffers: the queue starts empty and
     // is emptied again however this function returns
@@ -2706,7 +2712,16 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     // (acc_exclusive = 1)
     // relu' masks as bits (written by the fused forward launches of THIS plan's last run; without them the fp32 activations)
     const bool use_bits = pl->bits_written;
-    auto BITS = [&](int64_t off) { return reinterpret_cast<const unsigned long long *>(ws + off); };
+    auto BITS = [&](int64_t off) { return use_bits && off >= 0 ? reinterpret_cast<const unsigned long long *>(ws + off) : nullptr; };
+    // relu'(saved activation) on a chain's way in / behind its layer l: the bits at `bits` if this run wrote them, else the floats
+    auto chain_in_mask = [&](stair_tile_mlp_args &a, int64_t bits, const float *mask, const int32_t *mask_idx = nullptr) {
+        if ((a.in_bits = BITS(bits))) return;
+        a.in_mask = mask; a.in_mask_gstride = TH; a.in_mask_idx = mask_idx;
+    };
+    auto chain_act3 = [&](stair_tile_mlp_args &a, int l, const void *w, float *save, int64_t bits, const float *mask) {
+        a.W[l] = w; a.act[l] = 3; a.save[l] = save;
+        if (!(a.act_bits[l] = BITS(bits))) a.act_mask[l] = mask;
+    };
     auto bwd_bucket = [&](const Bucket &b, const int phase) -> int {
         if (b.cnt == 0) return 0;
         const int c = b.cnt;
@@ -2720,25 +2735,28 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         const float *svRs = ws + b.svRs, *svSup = ws + b.svSup;
         // dZ of the bucket's first / second tile layer: its block of the weight's region (the product with X is deferred), else scratch
         float *gA = b.dzA >= 0 ? ws + b.dzA : scrA, *gB = b.dzB >= 0 ? ws + b.dzB : scrB;
+        // a backward chain of this bucket starts here: every one adds its dX into the input's gradient tile (ACCUMULATE into g_map at
+        // G0c, exclusively), scales by inv_keep wherever it multiplies by a relu' mask, and picks its TileLen rule
+        auto chain_args = [&](TileLen rule) {
+            stair_tile_mlp_args a = {};
+            a.cnt = c; a.T = T; a.H = H; a.len = tile_len(rule, T, LEN);
+            a.in_scale = a.act_scale = inv_keep;
+            a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0c; a.acc_exclusive = 1;
+            return a;
+        };
         // tail shared by Filter / FilterFrame / Localize / Superlative: gB = d(second linear output)
         // the same on the tile: the chain's two dX products, the ReLU mask between them and the accumulation into the input's
         // gradient tile in ONE launch; the two weight-gradient products (reductions over all instances) stay TN GEMMs.
         // in_bcast: Filter -- the incoming gradient is ONE row per instance (the sum over frames), broadcast and masked on load.
         auto mlp_tail_fused = [&](const Lin &l3, const Lin &l0, int slot3, int slot0, bool relu_second, const float *bcast_row) -> int {
             (void)l3; (void)l0;             // their weight-gradient products run per weight, after all buckets
-            stair_tile_mlp_args a = {};
-            a.cnt = c; a.T = T; a.H = H; a.len = LEN;
+            stair_tile_mlp_args a = chain_args(LEN_ALWAYS);
             if (bcast_row) { a.X = bcast_row; a.x_gstride = H; a.x_broadcast = 1; }
             else { a.X = gB; a.x_gstride = TH; }
-            if (bcast_row || relu_second) {
-                if (use_bits && b.bitB >= 0) a.in_bits = BITS(b.bitB); else { a.in_mask = svB; a.in_mask_gstride = TH; }
-                a.in_scale = inv_keep; a.save_in = gB;
-            }
+            if (bcast_row || relu_second) { chain_in_mask(a, b.bitB, svB); a.save_in = gB; }
             a.n_layers = 2;
-            a.W[0] = WFT(slot3); a.act[0] = 3; a.act_scale = inv_keep; a.save[0] = gA;
-            if (use_bits && b.bitA >= 0) a.act_bits[0] = BITS(b.bitA); else a.act_mask[0] = svA;
-            a.W[1] = WFT(slot0); a.act[1] = 0;
-            a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0c; a.acc_exclusive = 1;
+            chain_act3(a, 0, WFT(slot3), gA, b.bitA, svA);
+            a.W[1] = WFT(slot0);
             chain_queue.push_back(a);
             return 0;
         };
@@ -2842,18 +2860,13 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                         RUN(dense_bwd(B, gC, c, T, H, H, svB, H, TH, nullptr, W.ffdense, nullptr, H, TH, nullptr, 0));
                         break;
                     }
-                    stair_tile_mlp_args a = {};
-                    a.cnt = c; a.T = T; a.H = H; a.len = T > 64 ? LEN : nullptr;      // (segments behind a clip's end run no k loop)
+                    stair_tile_mlp_args a = chain_args(LEN_OF_LONG_CLIPS);
                     a.X = g_map; a.x_gstride = TH; a.x_idx = I2;
-                    if (use_bits && b.bitC >= 0) a.in_bits = BITS(b.bitC); else { a.in_mask = map; a.in_mask_gstride = TH; a.in_mask_idx = I2; }
-                    a.in_scale = inv_keep; a.save_in = gC;
-                    a.n_layers = 3; a.act_scale = inv_keep;
-                    a.W[0] = WFT(WF_FFD); a.act[0] = 3; a.save[0] = gB;
-                    a.W[1] = WFT(WF_FF3 + v); a.act[1] = 3; a.save[1] = gA;
-                    if (use_bits && b.bitB >= 0) a.act_bits[0] = BITS(b.bitB); else a.act_mask[0] = svB;
-                    if (use_bits && b.bitA >= 0) a.act_bits[1] = BITS(b.bitA); else a.act_mask[1] = svA;
-                    a.W[2] = WFT(WF_FF0 + v); a.act[2] = 0;
-                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0c; a.acc_exclusive = 1;
+                    chain_in_mask(a, b.bitC, map, I2); a.save_in = gC;
+                    a.n_layers = 3;
+                    chain_act3(a, 0, WFT(WF_FFD), gB, b.bitB, svB);
+                    chain_act3(a, 1, WFT(WF_FF3 + v), gA, b.bitA, svA);
+                    a.W[2] = WFT(WF_FF0 + v);
                     chain_queue.push_back(a);
                     break;
                 }
@@ -2883,12 +2896,10 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                 RUN(launch_weighted_colsum(svA, H, nullptr, gRs2, W.hi3.dw, c * T, H, s));
                 RUN(launch_sum_all(gRs2, W.hi3.db, c * T, s));
                 if (fused) {
-                    stair_tile_mlp_args a = {};
-                    a.cnt = c; a.T = T; a.H = H; a.len = T > 64 ? LEN : nullptr;
-                    a.X = gA; a.x_gstride = TH; a.in_scale = inv_keep; a.save_in = gA;
-                    if (use_bits && b.bitA >= 0) a.in_bits = BITS(b.bitA); else { a.in_mask = svA; a.in_mask_gstride = TH; }
-                    a.n_layers = 1; a.W[0] = WFT(WF_HI0); a.act[0] = 0;
-                    a.tail = STAIR_TILE_ACCUMULATE; a.out = g_map; a.out_gstride = TH; a.out_idx = G0c; a.acc_exclusive = 1;
+                    stair_tile_mlp_args a = chain_args(LEN_OF_LONG_CLIPS);
+                    a.X = gA; a.x_gstride = TH; a.save_in = gA;
+                    chain_in_mask(a, b.bitA, svA);
+                    a.n_layers = 1; a.W[0] = WFT(WF_HI0);
                     chain_queue.push_back(a);
                     break;
                 }
@@ -2931,13 +2942,13 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
                     }
                     // d(output tile) -> LayerNorm adjoint * relu' = dZ (kept in the weight's region) -> dZ W -> += r_t . into the
                     // input's gradient tile, d r_t = (dZ W)_t . feat_t: one chain per tile, all Temporal buckets of the level in one launch
-                    stair_tile_mlp_args a = {};
-                    a.cnt = c; a.T = T; a.H = H; a.ln_eps = 1e-5f; a.len = T > 64 ? LEN : nullptr;
+                    stair_tile_mlp_args a = chain_args(LEN_OF_LONG_CLIPS);
+                    a.ln_eps = 1e-5f;
                     a.X = g_map; a.x_gstride = TH; a.x_idx = I4;
-                    a.ln_bwd = 1; a.in_mask = svA; a.in_mask_gstride = TH; a.in_scale = inv_keep; a.save_in = gA;
+                    a.ln_bwd = 1; a.in_mask = svA; a.in_mask_gstride = TH; a.save_in = gA;      // (the saved rows themselves, never bits)
                     a.gamma = W.ln_w; a.dgamma = W.dln_w; a.dbeta = W.dln_b;
-                    a.n_layers = 1; a.W[0] = WFT(WF_TD); a.act[0] = 0;
-                    a.tail = STAIR_TILE_ROWSCALE_ADJ; a.out = g_map; a.out_gstride = TH; a.out_idx = G0c; a.acc_exclusive = 1;
+                    a.n_layers = 1; a.W[0] = WFT(WF_TD);
+                    a.tail = STAIR_TILE_ROWSCALE_ADJ;       // ... and the row-scale adjoint on the way into the same gradient tile
                     a.adj_feat = map; a.adj_feat_gstride = TH; a.adj_feat_idx = I0;
                     a.adj_rs = att; a.adj_rs_idx = I3; a.adj_drs = g_att;
                     chain_queue.push_back(a);
@@ -3249,22 +3260,22 @@ extern "C" int stair_ctx_set_option(stair_ctx *ctx, int32_t option, int32_t valu
 }
 extern "C" int stair_ctx_set_tile_pack(stair_ctx *ctx, int32_t value) {
     STAIR_CHECK(ctx, "null context");
-    ctx->policy.tile_pack = value < 0 ? -1 : (value != 0);
+    ctx->policy.tile.v[TILE_PACK] = value < 0 ? -1 : (value != 0);
     return 0;
 }
 extern "C" int stair_ctx_set_tile_split(stair_ctx *ctx, int32_t value) {
     STAIR_CHECK(ctx, "null context");
-    ctx->policy.tile_split = value < 0 ? -1 : (value != 0);
+    ctx->policy.tile.v[TILE_SPLIT] = value < 0 ? -1 : (value != 0);
     return 0;
 }
 extern "C" int stair_ctx_get_tile_split(const stair_ctx *ctx, int32_t *value) {
     STAIR_CHECK(ctx && value, "null argument");
-    *value = ctx->policy.tile_split;
+    *value = ctx->policy.tile.v[TILE_SPLIT];
     return 0;
 }
 extern "C" int stair_ctx_get_tile_pack(const stair_ctx *ctx, int32_t *value) {
     STAIR_CHECK(ctx && value, "null argument");
-    *value = ctx->policy.tile_pack;
+    *value = ctx->policy.tile.v[TILE_PACK];
     return 0;
 }
 extern "C" int stair_ctx_get_option(const stair_ctx *ctx, int32_t option, int32_t *value) {

@@ -95,9 +95,16 @@ struct TmArg {
         };
     };
 };
-static TmArg tm_arg(const stair_tile_mlp_args &a, int kind, int pack) {
+// A bucket's geometry under the form its launch runs (tile_geom below): what the launcher, the pad kernel's grid, the work-item
+// counter, stair_tile_pack_factor / stair_tile_segments and the plan's bit regions (tile_max_tiles) all read.
+struct TileGeom {
+    int P, S;                    // instances per tile (packed launches), segments per instance (split launches); 1 otherwise
+    bool walk;                   // the bucket hands out INSTANCES: the SUM_ROWS walk of a split launch (one workgroup, all segments)
+    int items; int64_t tiles;    // work items of the bucket, and its tiles (they differ only under walk)
+};
+static TmArg tm_arg(const stair_tile_mlp_args &a, int kind, const TileGeom &g) {
     TmArg t = {};
-    t.pack = pack;
+    t.pack = g.S > 1 ? g.S : g.P;        // (a launch packs or splits, never both: at most one of them is above 1)
     t.X = a.X; t.x_gstride = a.x_gstride; t.x_idx = a.x_idx; t.row_scale = a.row_scale; t.rs_idx = a.rs_idx;
     for (int l = 0; l < 3; ++l) { t.W[l] = a.W[l]; t.bias[l] = a.bias[l]; t.act[l] = a.act[l]; t.save[l] = a.save[l]; t.act_mask[l] = a.act_mask[l]; }
     t.n_layers = a.n_layers; t.mid_rowdot = a.mid_rowdot; t.vw = a.vw; t.vb = a.vb; t.extra = a.extra; t.rs_out = a.rs_out;
@@ -1349,31 +1356,52 @@ static bool g_tile_timing = false;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_tile_events;
 
 static int g_tile_on = 1;           // stair_set_tile_mlp
-static int g_tile_pack = 1;         // stair_set_tile_pack
 static std::atomic<int64_t> g_tile_work_items{0};     // stair_tile_work_items
-thread_local int tl_tile_pack_force = -1;
-// does a map-level launch on this thread pack short clips?  A plan's backward pass forces what its forward pass ran with
-// (TilePackForce); else the context's override (stair_ctx_set_tile_pack), else the process-wide switch.
-int tile_pack_setting() {
-    if (tl_tile_pack_force >= 0) return tl_tile_pack_force != 0;
-    if (tl_policy && tl_policy->tile_pack >= 0) return tl_policy->tile_pack != 0;
-    return g_tile_pack != 0;
-}
-static int tile_pack_factor(int T, bool on) { return on && T >= 1 && T <= TM_ROWS / 2 ? TM_ROWS / T : 1; }
-// long clips as 64-row segments (the SPLIT kernel forms): the same three levels as the packing switch -- a plan's backward pass
-// forces what its forward pass ran with (TileSplitForce), else the context's override (stair_ctx_set_tile_split), else the process
-static int g_tile_split = 1;        // stair_set_tile_split
-thread_local int tl_tile_split_force = -1;
-int tile_split_setting() {
-    if (tl_tile_split_force >= 0) return tl_tile_split_force != 0;
-    if (tl_policy && tl_policy->tile_split >= 0) return tl_policy->tile_split != 0;
-    return g_tile_split != 0;
-}
-static int tile_segments(int T, bool on) { return on && T > TM_ROWS ? (T + TM_ROWS - 1) / TM_ROWS : 1; }
+// the two switches of the map-level forms (common.h TileSwitch): short clips share a tile, long clips run as 64-row segments
+TileSwitch g_tile_pack{TILE_PACK}, g_tile_split{TILE_SPLIT};
+thread_local TileSwitches tl_tile_force;
 bool tile_mlp_usable(int H, int T) {
     const bool on = policy_or(STAIR_OPT_TILE_MLP, g_tile_on) != 0;
-    return on && H == TM_H && T >= 1 && T <= (tile_split_setting() ? kTileSplitMaxFrames : TM_ROWS) && matmul_mode() == STAIR_MATMUL_BF16X3;
+    return on && H == TM_H && T >= 1 && T <= (g_tile_split.on() ? kTileSplitMaxFrames : TM_ROWS) && matmul_mode() == STAIR_MATMUL_BF16X3;
 }
+
+// Which kernel form a bucket runs (the KIND of tile_mlp_kernel): 3 a map-level backward chain, 1 vector-level tiles, 2 Temporal's
+// backward chain, 0 a map-level forward operator.  in_mask and save_in are chain options except under ln_bwd, whose own they are.
+// An argument set that names a chain option AND vec_pack / ln_bwd is a chain here, and tile_mlp_check refuses it as one.
+static int tile_kind(const stair_tile_mlp_args &a) {
+    bool chain = a.tail == STAIR_TILE_ACCUMULATE || a.in_bits || a.x_broadcast || (!a.ln_bwd && (a.in_mask || a.save_in));
+    for (int l = 0; l < a.n_layers && l < 3; ++l) chain = chain || a.act[l] == 3;
+    return chain ? 3 : a.vec_pack ? 1 : a.ln_bwd ? 2 : 0;
+}
+
+// split: the launch runs the SPLIT form (one of its buckets has T > 64); a bucket of T <= 64 in it is one segment per instance.
+// Else short clips share a tile while pack_on: P = 64 / T instances whenever T <= 32.  The caller's cnt counts INSTANCES either way.
+static TileGeom tile_geom(int kind, const stair_tile_mlp_args &a, bool pack_on, bool split) {
+    TileGeom g;
+    g.S = split && a.T > TM_ROWS ? (a.T + TM_ROWS - 1) / TM_ROWS : 1;
+    g.P = !split && kind != 1 && pack_on && a.T >= 1 && a.T <= TM_ROWS / 2 ? TM_ROWS / a.T : 1;
+    g.tiles = split ? (int64_t)a.cnt * g.S : (a.cnt + g.P - 1) / g.P;
+    g.walk = split && kind == 0 && a.tail == STAIR_TILE_SUM_ROWS;
+    g.items = g.walk ? a.cnt : (int)g.tiles;
+    return g;
+}
+static stair_tile_mlp_args tile_frames(int cnt, int T) { stair_tile_mlp_args a = {}; a.cnt = cnt; a.T = T; return a; }
+// the most tiles a pass may run a map-level bucket as: nothing packed, segments whenever the clips are long
+int64_t tile_max_tiles(int cnt, int T) { return tile_geom(0, tile_frames(cnt, T), false, T > TM_ROWS).tiles; }
+
+// the kernel of every form, [plain / packed / split][KIND], and the pad kernel that goes ahead of a split form's ragged launches
+// (a table of its own, behind the other: the code object lists its kernels in the order they are first named).  The tile's own
+// traffic carries the non-temporal hint (NT) in every form but the vector-level one: with the first version of the kernel plain
+// accesses were faster (saves 273 -> 290 us per 1024 tiles); now that a layer is bound by the weight stream from L2, keeping the
+// streamed tiles from displacing the weight planes pays: 17.02 -> 16.89 ms per 2048-question step (three A/B pairs on one box),
+// neutral at 128 questions and in inference.
+enum { TF_PLAIN = 0, TF_PACKED = 1, TF_SPLIT = 2 };
+using TileKernel = void (*)(TmParams);
+static const TileKernel kTileKernels[3][4] = {
+    {tile_mlp_kernel<true, 0>, tile_mlp_kernel<false, 1>, tile_mlp_kernel<true, 2>, tile_mlp_kernel<true, 3>},
+    {tile_mlp_kernel<true, 0, true>, nullptr, tile_mlp_kernel<true, 2, true>, tile_mlp_kernel<true, 3, true>},
+    {tile_mlp_kernel<true, 0, false, true>, nullptr, tile_mlp_kernel<true, 2, false, true>, tile_mlp_kernel<true, 3, false, true>}};
+static const TileKernel kTileSplitPads[4] = {tile_split_pad_kernel<0>, nullptr, tile_split_pad_kernel<2>, tile_split_pad_kernel<3>};
 
 static int tile_mlp_check(const stair_tile_mlp_args &a) {
     STAIR_CHECK(a.H == TM_H, "the fused tile operators are built for hidden_size 512");
@@ -1386,7 +1414,7 @@ static int tile_mlp_check(const stair_tile_mlp_args &a) {
         STAIR_CHECK(a.tail == STAIR_TILE_STORE_ROWS || a.tail == STAIR_TILE_NONE, "vector-level tiles end in STORE_ROWS");
         for (int l = 0; l < a.n_layers; ++l) STAIR_CHECK(a.act[l] != 3, "no backward chains on vector-level tiles");
     } else {
-        STAIR_CHECK(a.T >= 1 && (a.T <= TM_ROWS || tile_split_setting()), "a tile holds 1..64 frames");
+        STAIR_CHECK(a.T >= 1 && (a.T <= TM_ROWS || g_tile_split.on()), "a tile holds 1..64 frames");
         STAIR_CHECK(a.T <= kTileSplitMaxFrames, "the tile operators take clips of at most 141 frames (64-row segments)");
         STAIR_CHECK(a.X && a.cnt >= 0, "null input");
         STAIR_CHECK(a.tail != STAIR_TILE_STORE_ROWS, "STORE_ROWS is the vector-level tail");
@@ -1403,16 +1431,12 @@ static int tile_mlp_check(const stair_tile_mlp_args &a) {
         STAIR_CHECK(a.W[l] && (reinterpret_cast<uintptr_t>(a.W[l]) & 15) == 0, "weight planes (stair_pack_wfrag) missing or unaligned");
     for (int l = 0; l < a.n_layers; ++l) STAIR_CHECK(a.act[l] != 3 || a.act_mask[l] || a.act_bits[l], "act 3 multiplies by relu'(act_mask[l]) (or its bits, act_bits[l])");
     STAIR_CHECK(!(a.in_mask && a.in_bits), "in_mask or in_bits, not both");
-    {   // the backward chains are a kernel of their own: chain options do not mix with the forward operators' options
-        bool chain = a.tail == STAIR_TILE_ACCUMULATE || (!a.ln_bwd && a.in_mask) || a.in_bits || a.x_broadcast || (!a.ln_bwd && a.save_in);
-        for (int l = 0; l < a.n_layers; ++l) chain = chain || a.act[l] == 3;
-        if (chain) {
-            STAIR_CHECK(!a.vec_pack && !a.ln_bwd, "chain options (act 3, in_mask, in_bits, x_broadcast, save_in, ACCUMULATE) are map-level");
-            STAIR_CHECK(a.tail == STAIR_TILE_ACCUMULATE || a.tail == STAIR_TILE_STORE || a.tail == STAIR_TILE_NONE, "a backward chain ends in ACCUMULATE, STORE or NONE");
-            STAIR_CHECK(!a.row_scale && !a.mid_rowdot && !a.save_bits[0] && !a.save_bits[1] && !a.save_bits[2], "a backward chain takes no row_scale / mid_rowdot / save_bits");
-        } else {
-            STAIR_CHECK(!a.act_bits[0] && !a.act_bits[1] && !a.act_bits[2], "act_bits belong to act 3");
-        }
+    if (tile_kind(a) == 3) {    // the backward chains are a kernel of their own: chain options do not mix with the forward operators' options
+        STAIR_CHECK(!a.vec_pack && !a.ln_bwd, "chain options (act 3, in_mask, in_bits, x_broadcast, save_in, ACCUMULATE) are map-level");
+        STAIR_CHECK(a.tail == STAIR_TILE_ACCUMULATE || a.tail == STAIR_TILE_STORE || a.tail == STAIR_TILE_NONE, "a backward chain ends in ACCUMULATE, STORE or NONE");
+        STAIR_CHECK(!a.row_scale && !a.mid_rowdot && !a.save_bits[0] && !a.save_bits[1] && !a.save_bits[2], "a backward chain takes no row_scale / mid_rowdot / save_bits");
+    } else {
+        STAIR_CHECK(!a.act_bits[0] && !a.act_bits[1] && !a.act_bits[2], "act_bits belong to act 3");
     }
     STAIR_CHECK(!((a.vec_pack || a.ln_bwd) && (a.in_bits || a.save_bits[0] || a.save_bits[1] || a.save_bits[2] || a.act_bits[0] || a.act_bits[1] || a.act_bits[2])),
                 "bit masks are a map-level option");
@@ -1445,46 +1469,27 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     static int cus[64] = {};
     if (!attr_set[dev]) {
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
-        STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_mlp_kernel<true, 3, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
+        for (const auto &forms : kTileKernels)
+            for (TileKernel k : forms)
+                if (k) STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         int v = 256;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         cus[dev] = v;
         attr_set[dev] = true;
     }
-    // non-temporal hints on the tile's own traffic (inputs, masks, saves) of every form but the vector-level one: with the first
-    // version of the kernel plain accesses were faster (saves 273 -> 290 us per 1024 tiles); now that a layer is bound by the weight
-    // stream from L2, keeping the streamed tiles from displacing the weight planes pays: 17.02 -> 16.89 ms per 2048-question step
-    // (three A/B pairs on one box), neutral at 128 questions and in inference.
     auto rounds = [&](int x) { return args[x].n_layers + (args[x].vec_pack ? (args[x].vec_pack == 1 ? 1 : 2) : 0); };   // k loops per tile
-    // map-level tiles, vector-level tiles and Temporal's backward chains are three kernels (what one form needs in registers the
-    // others do not pay for): one launch per form a level has; stream-ordered, so they share the (self-resetting) queue words
-    auto kind_of = [](const stair_tile_mlp_args &a) {
-        if (a.vec_pack) return 1;
-        if (a.ln_bwd) return 2;
-        bool chain = a.tail == STAIR_TILE_ACCUMULATE || a.in_mask || a.in_bits || a.x_broadcast || a.save_in;
-        for (int l = 0; l < a.n_layers && l < 3; ++l) chain = chain || a.act[l] == 3;
-        return chain ? 3 : 0;
-    };
-    // short clips share a tile (the packed kernel forms): P = 64 / T instances per tile whenever T <= 32, decided here for the
-    // whole call -- the caller's buckets count INSTANCES either way
-    const bool pack_on = tile_pack_setting() != 0;
+    // decided here for the whole call
+    const bool pack_on = g_tile_pack.on();
+    // map-level tiles, vector-level tiles, Temporal's backward chains and the map-level chains are four kernels (what one form needs
+    // in registers the others do not pay for): one launch per form a level has; stream-ordered, so they share the (self-resetting)
+    // queue words
     for (int kind = 0; kind < 4; ++kind) {
-        const int vec = kind == 1;
         TmParams pp;
         pp.nb = 0; pp.counter = counter; pp.first[0] = 0; pp.fx_g = pp.fx_b = nullptr;
         pp.drop_thresh = 0; pp.drop_inv_keep = 1.0f; pp.drop_seed = 0;
         int order[TM_MAXB], m = 0;
         for (int i = 0; i < n; ++i)
-            if (args[i].cnt > 0 && kind_of(args[i]) == kind) order[m++] = i;
+            if (args[i].cnt > 0 && tile_kind(args[i]) == kind) order[m++] = i;
         if (m == 0) continue;
         if (kind == 2) {            // one accumulator pair per workgroup: the chains of a launch share their LayerNorm
             for (int j = 1; j < m; ++j)
@@ -1504,21 +1509,19 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
             }
         }
         std::stable_sort(order, order + m, [&](int x, int y) { return rounds(x) > rounds(y); });    // long tiles first
-        bool packed = false, split = false;
         // clips of more than 64 frames (admitted by tile_mlp_check only while the segment switch is on) run as segments: the SPLIT
-        // form for the whole launch -- a bucket of T <= 64 in it is one segment per instance
+        // form for the whole launch
+        bool packed = false, split = false, any_len = false;
         for (int j = 0; j < m; ++j) split = split || (kind != 1 && args[order[j]].T > TM_ROWS);
         int64_t tiles = 0;
         for (int j = 0; j < m; ++j) {
             const stair_tile_mlp_args &a = args[order[j]];
-            const int P = kind == 1 || split ? 1 : tile_pack_factor(a.T, pack_on);
-            const int S = split ? tile_segments(a.T, true) : 1;
-            packed = packed || P > 1;
-            pp.a[j] = tm_arg(a, kind, split ? S : P);
-            // work items are TILES; a SUM_ROWS bucket of a split launch hands out INSTANCES (one workgroup walks the segments)
-            const bool walk = split && kind == 0 && a.tail == STAIR_TILE_SUM_ROWS;
-            pp.first[j + 1] = pp.first[j] + (split ? (walk ? a.cnt : a.cnt * S) : (a.cnt + P - 1) / P);
-            tiles += split ? (int64_t)a.cnt * S : (a.cnt + P - 1) / P;
+            const TileGeom g = tile_geom(kind, a, pack_on, split);
+            packed = packed || g.P > 1;
+            any_len = any_len || a.len != nullptr;
+            pp.a[j] = tm_arg(a, kind, g);
+            pp.first[j + 1] = pp.first[j] + g.items;
+            tiles += g.tiles;
             const int64_t M = a.vec_pack ? a.vec_cnt : (int64_t)a.cnt * a.T;
             const int kl = rounds(order[j]);
             STAIR_ACCT_MFMA("tile_mlp", (M * TM_H * 2 + (int64_t)kl * TM_H * TM_H) * 4, 2 * M * TM_H * TM_H * kl);
@@ -1532,26 +1535,11 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
             STAIR_HIP(hipEventCreate(&e0)); STAIR_HIP(hipEventCreate(&e1));
             STAIR_HIP(hipEventRecord(e0, s));
         }
-        if (split) {            // ragged plans: zeros for the segments behind a clip's end, which the tile kernel skips
-            bool any_len = false;
-            for (int j = 0; j < m; ++j) any_len = any_len || args[order[j]].len != nullptr;
-            if (any_len) {
-                if (kind == 0) hipLaunchKernelGGL((tile_split_pad_kernel<0>), dim3((unsigned)tiles), dim3(512), 0, s, pp);
-                else if (kind == 2) hipLaunchKernelGGL((tile_split_pad_kernel<2>), dim3((unsigned)tiles), dim3(512), 0, s, pp);
-                else hipLaunchKernelGGL((tile_split_pad_kernel<3>), dim3((unsigned)tiles), dim3(512), 0, s, pp);
-                STAIR_LAUNCH_CHECK();
-            }
+        if (split && any_len) {     // ragged plans: zeros for the segments behind a clip's end, which the tile kernel skips
+            hipLaunchKernelGGL(kTileSplitPads[kind], dim3((unsigned)tiles), dim3(512), 0, s, pp);
+            STAIR_LAUNCH_CHECK();
         }
-        if (split && kind == 0) hipLaunchKernelGGL((tile_mlp_kernel<true, 0, false, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (split && kind == 2) hipLaunchKernelGGL((tile_mlp_kernel<true, 2, false, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (split && kind == 3) hipLaunchKernelGGL((tile_mlp_kernel<true, 3, false, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (packed && kind == 0) hipLaunchKernelGGL((tile_mlp_kernel<true, 0, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (packed && kind == 2) hipLaunchKernelGGL((tile_mlp_kernel<true, 2, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (packed && kind == 3) hipLaunchKernelGGL((tile_mlp_kernel<true, 3, true>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (vec) hipLaunchKernelGGL((tile_mlp_kernel<false, 1>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (kind == 2) hipLaunchKernelGGL((tile_mlp_kernel<true, 2>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else if (kind == 3) hipLaunchKernelGGL((tile_mlp_kernel<true, 3>), dim3(grid), dim3(512), TM_LDS, s, pp);
-        else hipLaunchKernelGGL((tile_mlp_kernel<true, 0>), dim3(grid), dim3(512), TM_LDS, s, pp);
+        hipLaunchKernelGGL(kTileKernels[split ? TF_SPLIT : packed ? TF_PACKED : TF_PLAIN][kind], dim3(grid), dim3(512), TM_LDS, s, pp);
         STAIR_LAUNCH_CHECK();
         if (g_tile_timing) {
             STAIR_HIP(hipEventRecord(e1, s));
@@ -1567,13 +1555,13 @@ int launch_tile_mlp(const stair_tile_mlp_args &a, hipStream_t s) { return launch
 
 extern "C" int stair_set_tile_mlp(int32_t on) { stair::g_tile_on = on; return 0; }
 
-extern "C" int stair_set_tile_pack(int32_t on) { stair::g_tile_pack = on < 0 ? 1 : (on != 0); return 0; }
+extern "C" int stair_set_tile_pack(int32_t on) { stair::g_tile_pack.set_process(on); return 0; }
 
-extern "C" int32_t stair_tile_pack_factor(int32_t T) { return stair::tile_pack_factor(T, stair::g_tile_pack != 0); }
+extern "C" int32_t stair_tile_pack_factor(int32_t T) { return stair::tile_geom(0, stair::tile_frames(0, T), stair::g_tile_pack.process != 0, false).P; }
 
-extern "C" int stair_set_tile_split(int32_t on) { stair::g_tile_split = on < 0 ? 1 : (on != 0); return 0; }
+extern "C" int stair_set_tile_split(int32_t on) { stair::g_tile_split.set_process(on); return 0; }
 
-extern "C" int32_t stair_tile_segments(int32_t T) { return stair::tile_segments(T, stair::g_tile_split != 0); }
+extern "C" int32_t stair_tile_segments(int32_t T) { return stair::tile_geom(0, stair::tile_frames(0, T), false, stair::g_tile_split.process != 0).S; }
 
 extern "C" int stair_tile_work_items(int64_t *items, int32_t reset) {
     const int64_t v = reset ? stair::g_tile_work_items.exchange(0) : stair::g_tile_work_items.load();

@@ -2,19 +2,16 @@
 of T <= 32 frames share a 64-row tile, P = 64 / T instances each.  Every case runs with packing on and off; the unpacked launch is
 the reference, bit for bit, and the packed one is also compared with fp64 at the tolerance tests/test_gpu_building_blocks.py (or,
 for the backward chains, tests/test_gpu_tile_fused.py) uses for the same operator.  `-m gpu`."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from stair_amd import spec, synth
-from stair_amd._lib import lib, check, TileMlpArgs
+from stair_amd._lib import lib
+from tile_helpers import (DEV, H, STORE_FIRST, _gen, _lin, d, i32, _perm, _close, _launch, _mlp_ref, _chain_ref, _fwd2, _tile_words,
+                          _work_items)
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-H = 512
-STORE_FIRST = 0x40000000
 # (T, cnt): one tile / a full and a partial tile / three tiles / T no multiple of 8, 60 used rows / 63 used rows / P = 2 / unpacked
 CASES = [(8, 1), (8, 9), (8, 17), (5, 13), (21, 4), (32, 3), (33, 3)]
 
@@ -23,33 +20,6 @@ CASES = [(8, 1), (8, 9), (8, 17), (5, 13), (21, 4), (32, 3), (33, 3)]
 def default_switch():
     yield
     lib.stair_set_tile_pack(-1)
-
-
-def _gen(T, cnt, salt):
-    return torch.Generator().manual_seed(1000 * salt + 37 * T + cnt)
-
-
-_W = {}
-
-
-def _lin(i):
-    """layer i of the tests' MLPs: (weight [512, 512], bias) on the CPU, made once"""
-    if i not in _W:
-        g = torch.Generator().manual_seed(77 + i)
-        _W[i] = (torch.randn(H, H, generator=g) / H ** 0.5, 0.1 * torch.randn(H, generator=g))
-    return _W[i]
-
-
-def d(t):
-    return t.to(DEV)
-
-
-def i32(a):
-    return torch.as_tensor(np.asarray(a), dtype=torch.int32).to(DEV)
-
-
-def _perm(n, k, g):
-    return torch.randperm(n, generator=g)[:k].to(torch.int32)
 
 
 def _both(run):
@@ -69,43 +39,6 @@ def _same(on, off, skip=()):
             assert torch.equal(on[k], off[k]), (k, float((on[k].double() - off[k].double()).abs().max()))
 
 
-def _close(got, ref, tol, what):
-    err = float((got.cpu().double() - ref.double()).abs().max())
-    bound = tol * max(1.0, float(ref.abs().max()))
-    assert err < bound, (what, err, bound)
-
-
-def _launch(cnt, T, layers, tail=0, **kw):
-    """stair_tile_mlp_fwd from named fields: layers = [(planes, bias or None, act)], everything else a tensor, a list of tensors
-    (per-layer arrays) or a number"""
-    from stair_amd import ops
-    a = TileMlpArgs()
-    for l, (planes, bias, act) in enumerate(layers):
-        a.W[l], a.bias[l], a.act[l] = planes.data_ptr(), (bias.data_ptr() if bias is not None else None), act
-    a.n_layers, a.tail, a.cnt, a.T, a.H = len(layers), tail, cnt, T, H
-    for k, v in kw.items():
-        if isinstance(v, (list, tuple)):
-            arr = getattr(a, k)
-            for l, x in enumerate(v):
-                if x is not None:
-                    arr[l] = x.data_ptr() if isinstance(x, torch.Tensor) else x
-        else:
-            setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-    check(lib.stair_tile_mlp_fwd(C.byref(a), ops._stream()))
-
-
-def _mlp_ref(x, n, last_relu=True):
-    """fp64: n layers Lin . ReLU of the tests' weights on x [..., 512]; returns every layer's activation"""
-    acts, h = [], x.double()
-    for i in range(n):
-        w, b = _lin(i)
-        h = h @ w.double().t() + b.double()
-        if i + 1 < n or last_relu:
-            h = torch.relu(h)
-        acts.append(h)
-    return acts
-
-
 def _expected_bits(act, T, cnt, P):
     """save_bits of activation rows act [cnt, T, 512] (> 0) as a launch with P instances per tile writes them, and the mask of the
     bits that belong to rows that exist: word (tile, 64 w + c), byte j, bit e <-> row w + 8 j of the tile, column 8 c + e"""
@@ -117,25 +50,7 @@ def _expected_bits(act, T, cnt, P):
         r0 = (i // P) * 64 + (i % P) * T
         rows[r0:r0 + T] = pos[i * T:(i + 1) * T]
         exists[r0:r0 + T] = True
-    def words(r):                                     # [tiles * 64, 512] bool -> [tiles, 512] int64
-        r = r.reshape(tiles, 8, 8, 64, 8).long()      # (tile, j, w, c, e): row = w + 8 j, column = 8 c + e
-        sh = (8 * torch.arange(8).reshape(1, 8, 1, 1, 1) + torch.arange(8).reshape(1, 1, 1, 1, 8))
-        return (r << sh).sum(dim=(1, 4)).reshape(tiles, H)          # (tile, w, c) -> 64 w + c; bit 63 wraps to the sign, as stored
-    return words(rows), words(exists.reshape(-1, 1).expand(-1, H))
-
-
-def _fwd2(T, cnt, g, drop=None):
-    """the forward launch the chain tests build on: 2 layers Lin . ReLU with saves and save_bits, no tail (packing as set)"""
-    from stair_amd import ops
-    x = torch.randn(cnt, T, H, generator=g)
-    planes = [ops.pack_wfrag(d(_lin(i)[0])) for i in range(2)]
-    sv = [torch.zeros(cnt, T, H, device=DEV) for _ in range(2)]
-    bits = [torch.zeros(cnt, H, dtype=torch.int64, device=DEV) for _ in range(2)]
-    kw = dict(X=d(x), x_gstride=T * H, save=sv, save_bits=bits)
-    if drop:
-        kw.update(drop_site=[1, 2], drop_p=drop[0], drop_seed=drop[1])
-    _launch(cnt, T, [(planes[0], d(_lin(0)[1]), 1), (planes[1], d(_lin(1)[1]), 1)], **kw)
-    return x, sv, bits
+    return _tile_words(rows.reshape(tiles, 64, H)), _tile_words(exists.reshape(tiles, 64, 1).expand(-1, -1, H))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -329,12 +244,6 @@ def test_dropout_drops_the_same_elements(T, cnt):
 # ---------------------------------------------------------------------------------------------
 # backward chains
 # ---------------------------------------------------------------------------------------------
-def _chain_ref(dy2, sv):
-    """fp64 of the chain dX = ((dY * relu'(h2)) W2 * relu'(h1)) W1 with the relu' masks of the forward launch's saves"""
-    m1, m2 = (sv[0].cpu() > 0).double(), (sv[1].cpu() > 0).double()
-    dz2 = dy2.double() * m2
-    dz1 = (dz2 @ _lin(1)[0].double()) * m1
-    return dz2, dz1, dz1 @ _lin(0)[0].double()
 
 
 @pytest.mark.parametrize('T,cnt', CASES)
@@ -528,12 +437,6 @@ def test_temporal_backward_chain(T, cnt, mode):
     _close(on['drs'].cpu() - drs0, R.grad, 3e-5, 'drs')
     _close(on['dgamma'], G.grad, 3e-5, 'dgamma')
     _close(on['dbeta'], Bt.grad, 3e-5, 'dbeta')
-
-
-def _work_items():
-    n = C.c_int64(0)
-    assert lib.stair_tile_work_items(C.byref(n), 1) == 0
-    return n.value
 
 
 @pytest.mark.parametrize('T,cnt,packed,unpacked', [(8, 17, 3, 17), (33, 3, 3, 3)])

@@ -5,19 +5,16 @@ an instance of its own (one launch per segment number over sliced views of the s
 with fp64 at the tolerance tests/test_gpu_building_blocks.py (forward operators) or tests/test_gpu_tile_fused.py (chains) uses for
 the same operator.  Filter's sum over frames is the one tail that crosses segments: fp64, and bit-identical from run to run.
 A segment behind its clip's end (ragged: 64 g >= len) is not computed and holds zeros wherever a live segment writes.  `-m gpu`."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from stair_amd import spec, synth
-from stair_amd._lib import lib, check, TileMlpArgs
+from stair_amd._lib import lib, check
+from tile_helpers import (DEV, H, STORE_FIRST, _gen, _lin, _planes, d, i32, _perm, _close, _launch, _fwd_layers, _mlp_ref, _chain_ref,
+                          _fwd2, _tile_words, _work_items)
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
-H = 512
-STORE_FIRST = 0x40000000
 # (T, cnt, lens): one live row in segment 1 / the same, several instances / a partial second segment / two full segments / three
 # segments / the largest admitted T / ragged: a one-row segment (65), an exactly empty one (64), an empty one behind a short clip (30, 1)
 CASES = [(65, 1, None), (65, 3, None), (100, 2, None), (128, 3, None), (129, 2, None), (141, 1, None), (100, 5, (100, 65, 64, 30, 1))]
@@ -33,43 +30,6 @@ def default_switches():
     lib.stair_set_tile_queue(-1)
 
 
-def _gen(T, cnt, salt):
-    return torch.Generator().manual_seed(1000 * salt + 37 * T + cnt)
-
-
-_W = {}
-
-
-def _lin(i):
-    """layer i of the tests' MLPs: (weight [512, 512], bias) on the CPU, made once"""
-    if i not in _W:
-        g = torch.Generator().manual_seed(77 + i)
-        _W[i] = (torch.randn(H, H, generator=g) / H ** 0.5, 0.1 * torch.randn(H, generator=g))
-    return _W[i]
-
-
-_P = {}
-
-
-def _planes(i, transpose=False):
-    from stair_amd import ops
-    if (i, transpose) not in _P:
-        _P[(i, transpose)] = ops.pack_wfrag(_lin(i)[0].to(DEV), transpose=transpose)
-    return _P[(i, transpose)]
-
-
-def d(t):
-    return t.to(DEV)
-
-
-def i32(a):
-    return torch.as_tensor(np.asarray(a), dtype=torch.int32).to(DEV)
-
-
-def _perm(n, k, g):
-    return torch.randperm(n, generator=g)[:k].to(torch.int32)
-
-
 def _segs(T):
     """(segment, first frame, rows) of a clip of T frames"""
     return [(s, 64 * s, min(64, T - 64 * s)) for s in range((T + 63) // 64)]
@@ -80,65 +40,18 @@ def _at(t, elems):
     return t.data_ptr() + elems * t.element_size()
 
 
-def _close(got, ref, tol, what):
-    err = float((got.cpu().double() - ref.double()).abs().max())
-    bound = tol * max(1.0, float(ref.abs().max()))
-    assert err < bound, (what, err, bound)
-
-
-def _launch(cnt, T, layers, tail=0, **kw):
-    """stair_tile_mlp_fwd from named fields: layers = [(planes, bias or None, act)], everything else a tensor, an address, a list
-    (per-layer arrays) or a number"""
-    from stair_amd import ops
-    a = TileMlpArgs()
-    for l, (planes, bias, act) in enumerate(layers):
-        a.W[l], a.bias[l], a.act[l] = planes.data_ptr(), (bias.data_ptr() if bias is not None else None), act
-    a.n_layers, a.tail, a.cnt, a.T, a.H = len(layers), tail, cnt, T, H
-    for k, v in kw.items():
-        if v is None:
-            continue
-        if isinstance(v, (list, tuple)):
-            arr = getattr(a, k)
-            for l, x in enumerate(v):
-                if x is not None:
-                    arr[l] = x.data_ptr() if isinstance(x, torch.Tensor) else x
-        else:
-            setattr(a, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
-    check(lib.stair_tile_mlp_fwd(C.byref(a), ops._stream()))
-
-
-def _fwd_layers(n, last_relu=True):
-    return [(_planes(i), d(_lin(i)[1]), 1 if (i + 1 < n or last_relu) else 0) for i in range(n)]
-
-
-def _mlp_ref(x, n, last_relu=True):
-    """fp64: n layers Lin . ReLU of the tests' weights on x [..., 512]; returns every layer's activation"""
-    acts, h = [], x.double()
-    for i in range(n):
-        w, b = _lin(i)
-        h = h @ w.double().t() + b.double()
-        if i + 1 < n or last_relu:
-            h = torch.relu(h)
-        acts.append(h)
-    return acts
-
-
 def _exists_words(rows):
     """the bits of a tile's words that belong to its first `rows` rows: word (64 w + c), byte j, bit e <-> row w + 8 j, column 8 c + e
     (as _expected_bits of tests/test_gpu_tile_pack.py, one instance per tile)"""
-    ex = (torch.arange(64) < rows).reshape(8, 8, 1, 1).expand(8, 8, 64, 8).long()         # (j, w, c, e)
-    sh = 8 * torch.arange(8).reshape(8, 1, 1, 1) + torch.arange(8).reshape(1, 1, 1, 8)
-    return (ex << sh).sum(dim=(0, 3)).reshape(H)
+    return _tile_words((torch.arange(64) < rows).reshape(1, 64, 1).expand(1, 64, H))[0]
 
 
 def _bits_of(act_seg):
     """save_bits words [cnt, 512] of activation rows act_seg [cnt, rows <= 64, 512], as the kernel lays them out"""
     cnt, rows, _ = act_seg.shape
-    pos = torch.zeros(cnt, 64, H, dtype=torch.long)
-    pos[:, :rows] = (act_seg.cpu() > 0).long()
-    r = pos.reshape(cnt, 8, 8, 64, 8)                                                    # (i, j, w, c, e)
-    sh = 8 * torch.arange(8).reshape(1, 8, 1, 1, 1) + torch.arange(8).reshape(1, 1, 1, 1, 8)
-    return (r << sh).sum(dim=(1, 4)).reshape(cnt, H)
+    pos = torch.zeros(cnt, 64, H, dtype=torch.bool)
+    pos[:, :rows] = act_seg.cpu() > 0
+    return _tile_words(pos)
 
 
 def _live(lens, i, f0):
@@ -445,12 +358,6 @@ def test_switch_off_refuses_more_than_64_frames_as_before():
     assert float(out.abs().max()) > 0
 
 
-def _work_items():
-    n = C.c_int64(0)
-    assert lib.stair_tile_work_items(C.byref(n), 1) == 0
-    return n.value
-
-
 @pytest.mark.parametrize('T,cnt,want', [(65, 3, 6), (129, 2, 6), (64, 3, 3)])
 def test_work_items_count_segments(T, cnt, want):
     x = torch.randn(cnt, T, H, device=DEV)
@@ -467,27 +374,11 @@ def test_work_items_count_segments(T, cnt, want):
 # ---------------------------------------------------------------------------------------------
 # backward chains
 # ---------------------------------------------------------------------------------------------
-def _fwd2(T, cnt, g, lens=None):
-    """the segmented forward launch the chain tests build on: 2 layers Lin . ReLU with saves and save_bits, no tail"""
-    S = len(_segs(T))
-    x = torch.randn(cnt, T, H, generator=g)
-    sv = [torch.zeros(cnt, T, H, device=DEV) for _ in range(2)]
-    bits = [torch.zeros(cnt * S, H, dtype=torch.int64, device=DEV) for _ in range(2)]
-    _launch(cnt, T, _fwd_layers(2), X=d(x), x_gstride=T * H, save=sv, save_bits=bits, len=i32(lens) if lens else None)
-    return x, sv, bits
 
 
 def _seg_bits(bits, cnt, T, s):
     """the words of segment s of every instance, [cnt, 512], as a launch of that segment alone indexes them"""
     return bits.reshape(cnt, len(_segs(T)), H)[:, s].contiguous()
-
-
-def _chain_ref(dy2, sv):
-    """fp64 of the chain dX = ((dY * relu'(h2)) W2 * relu'(h1)) W1 with the relu' masks of the forward launch's saves"""
-    m1, m2 = (sv[0].cpu() > 0).double(), (sv[1].cpu() > 0).double()
-    dz2 = dy2.double() * m2
-    dz1 = (dz2 @ _lin(1)[0].double()) * m1
-    return dz2, dz1, dz1 @ _lin(0)[0].double()
 
 
 def _chain_layers():
