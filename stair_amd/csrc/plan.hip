@@ -254,10 +254,6 @@ __global__ void zero_pad_frames_kernel(float *base, const int32_t *pairs, int T,
 }
 
 constexpr int OP_SPAN = 50;      // pseudo op: span mean (level 0)
-const int kArity[STAIR_OP_COUNT] = {2, 2, 3, 2, 2, 2, 2, 2, 2, 1, 2, 2, 3, 3, 2, 2, 2, 2};
-const char *kOpName[STAIR_OP_COUNT] = {"And", "AttnVideo", "Choose", "Compare", "Equals", "Exists", "ExistsFrame",
-                                       "Filter", "FilterFrame", "HasItem", "Localize", "Relate", "Superlative",
-                                       "Temporal", "ToAction", "Xor", "XorFrame", "Array2"};
 
 struct Node {
     int kind = -1, slot = -1, aux = -1, level = 0, rel = -1;
@@ -402,6 +398,108 @@ inline BucketLayers bucket_layers(const Bucket &b) {
     }
     return u;
 }
+
+// THE table of the modules, indexed by STAIR_OP_*: what a module takes and gives, where its bucket keeps them, which operands get a
+// gradient, whether it runs on the tile operator, what its bucket saves, and the form of the five vector-level modules.  The
+// builder (interpret_programs, build_grad_fanin, build_index_image, layout_workspace), stair_plan_saved_offset and the vector-level
+// cases of the two runners read these rows; the launch bodies of the tile operators and of the row-kernel modules stay code.
+enum : uint8_t { KS = 1 << STAIR_VAL_STR, KV = 1 << STAIR_VAL_VEC, KM = 1 << STAIR_VAL_MAP, KA = 1 << STAIR_VAL_ATT, KF = 1 << STAIR_VAL_FRAME,
+                 KP = 1 << STAIR_VAL_PAIR, KANY = 0xff };                        // operand kinds as a mask
+enum { OUT_AS_FIRST = -1 };      // the output has the kind of operand 0, which operand 1 must share (And / XorFrame)
+// gradient arenas (build_grad_fanin); FAN_SUB: that of the bucket's `sub` kind (And / XorFrame)
+enum { FAN_NONE = -1, FAN_VEC = 0, FAN_MAP = 1, FAN_ATT = 2, FAN_SUB = 3 };
+// The one concatenation of two operand rows a vector-level module feeds its first layer, under its three spellings: the pack
+// kernel's, the grouped launch's and the tile operator's.
+enum VecIn { IN_CAT2, IN_XOR, IN_EXISTS };       // cat[a, b], cat[|a - b|, a, b], cat[a, b, a * b]
+struct VecInForm { PackMode pack; int vg, vec_pack; };
+const VecInForm kVecIn[] = {{PACK_CAT2, VG_IN_CAT2, 1}, {PACK_XOR, VG_IN_XOR, 2}, {PACK_EXISTS, VG_IN_EXISTS, 3}};
+// The regions a bucket may own, in the order layout_workspace takes them: `per_row`: one piece per row of the secondary count
+// (Bucket::nrows) instead of per instance; a piece is (T if t) x (H if h) floats.
+struct SaveRegion { const char *name; int64_t Bucket::*off; bool per_row, t, h; };
+enum : uint16_t { SV_A = 1, SV_B = 2, SV_RS = 4, SV_EXTRA = 8, SV_K = 16, SV_SUP = 32, SV_CAT = 64, SV_HID = 128 };
+const SaveRegion kSaveRegions[] = {{".svA", &Bucket::svA, false, true, true},   {".svB", &Bucket::svB, false, true, true},
+                                   {".svRs", &Bucket::svRs, false, true, false}, {".svExtra", &Bucket::svExtra, false, false, false},
+                                   {".svK", &Bucket::svK, true, false, true},    {".svSup", &Bucket::svSup, true, true, false},
+                                   {".svCat", &Bucket::svCat, false, false, true}, {".svHid", &Bucket::svHid, false, false, true}};
+inline const SaveRegion *save_region(uint16_t bit) {
+    for (int r = 0; r < 8; ++r)
+        if (bit == 1u << r) return &kSaveRegions[r];
+    return nullptr;
+}
+
+struct ModuleRow {
+    const char *name = "";
+    int arity = 0;
+    struct { uint8_t kinds; int8_t col; } in[3] = {{0, -1}, {0, -1}, {0, -1}};      // per operand: the kinds it takes, its bucket column (-1: none)
+    const char *refuse = "";         // the text of an operand-kind refusal
+    const char *refuse_kw = "";      // ... and of a keyword / mode the module has no variant for
+    int8_t out_kind = 0, out_col = -1;      // STAIR_VAL_* of the output (hence its arena counter) and its bucket column
+    bool frames = false;             // col[6] carries the frames of the instance's clip
+    int8_t grad[3] = {FAN_NONE, FAN_NONE, FAN_NONE};      // per bucket COLUMN 0..2: the arena its gradient is scattered into
+    bool tile = false;               // runs on the tile operator ...
+    int8_t bit_layers = 0;           // ... whose first `bit_layers` layers write their relu' as bits in training
+    // regions the bucket owns (SV_*): an inference plan with tile operators, a training plan (whatever else a training bucket saves
+    // lies in its weights' regions: wg_sx -> svA of the two-layer tile MLPs, vd_x -> svCat / svHid); and what
+    // stair_plan_saved_offset reports as saved activation 0 / 1
+    uint16_t own_infer = 0, own_train = 0, saved[2] = {0, 0};
+    // vector-level modules (Linear . ReLU [. D . Linear . ReLU [. D]] over a concatenation; the layers are kWeightRows' VD_* rows):
+    int8_t vec_in = -1;              // VecIn
+    bool vec_swap = false;           // the concatenation takes (column 1, column 0)
+    int8_t vec_drops = 0;            // nn.Dropout positions: 1 = behind the hidden row (position 0), 2 = and behind the output (position 1),
+                                     // whose relu' mask then carries 1 / (1 - p) in the backward pass
+    constexpr ModuleRow() = default;
+    constexpr ModuleRow(const char *n, int ar, const char *why) : name(n), arity(ar), refuse(why) {}
+    constexpr ModuleRow op(int k, uint8_t kinds, int col = -1) const { ModuleRow r = *this; r.in[k].kinds = kinds; r.in[k].col = (int8_t)col; return r; }
+    constexpr ModuleRow out(int kind, int col) const { ModuleRow r = *this; r.out_kind = (int8_t)kind; r.out_col = (int8_t)col; return r; }
+    constexpr ModuleRow kw(const char *why) const { ModuleRow r = *this; r.refuse_kw = why; return r; }
+    constexpr ModuleRow clip_frames() const { ModuleRow r = *this; r.frames = true; return r; }
+    constexpr ModuleRow grads(int g0, int g1 = FAN_NONE, int g2 = FAN_NONE) const { ModuleRow r = *this; r.grad[0] = (int8_t)g0; r.grad[1] = (int8_t)g1; r.grad[2] = (int8_t)g2; return r; }
+    constexpr ModuleRow tiles(int bits) const { ModuleRow r = *this; r.tile = true; r.bit_layers = (int8_t)bits; return r; }
+    constexpr ModuleRow owns(int infer, int train) const { ModuleRow r = *this; r.own_infer = (uint16_t)infer; r.own_train = (uint16_t)train; return r; }
+    constexpr ModuleRow saves(int s0, int s1 = 0) const { ModuleRow r = *this; r.saved[0] = (uint16_t)s0; r.saved[1] = (uint16_t)s1; return r; }
+    constexpr ModuleRow vec(int in_, bool swap, int drops) const {
+        ModuleRow r = op(0, KV, 0).op(1, KV, 1).out(STAIR_VAL_VEC, 2).grads(FAN_VEC, FAN_VEC);
+        r.vec_in = (int8_t)in_; r.vec_swap = swap; r.vec_drops = (int8_t)drops;
+        return r;
+    }
+};
+using MR = ModuleRow;
+constexpr ModuleRow kModules[STAIR_OP_COUNT] = {
+    MR("And", 2, "needs two [H] vectors or two [T] frame attentions").op(0, KV | KF, 0).op(1, KV | KF, 1).out(OUT_AS_FIRST, 2).grads(FAN_SUB, FAN_SUB),
+    MR("AttnVideo", 2, "AttnVideo(feat [T,H], attn [T])").op(0, KM, 0).op(1, KF, 1).out(STAIR_VAL_MAP, 2).grads(FAN_MAP, FAN_ATT),
+    MR("Choose", 3, "Choose(kw1 [H], kw2 [H], query [H])").op(0, KV, 0).op(1, KV, 1).op(2, KV, 2).out(STAIR_VAL_VEC, 3).grads(FAN_VEC, FAN_VEC),
+    MR("Compare", 2, "needs two [H] vectors").vec(IN_CAT2, false, 0),                                  // modules.py:15-21
+    MR("Equals", 2, "needs two [H] vectors").vec(IN_CAT2, false, 0),                                   // modules.py:24-37
+    // modules.py:141-159: Exists(keyword, feat) -> cat[feat, keyword, feat * keyword]
+    MR("Exists", 2, "needs two [H] vectors").vec(IN_EXISTS, true, 2).owns(SV_HID, 0).saves(SV_HID),
+    MR("ExistsFrame", 2, "ExistsFrame(keyword [H], feat [T,H])").op(0, KV, 0).op(1, KM, 1).out(STAIR_VAL_FRAME, 2).grads(FAN_VEC, FAN_MAP),
+    // (Filter ignores a tensor keyword: no column for it)
+    MR("Filter", 2, "Filter(feat [T,H], keyword)").kw("Filter keyword must be a [H] vector or actions/objects/relations (modules.py:346-351)")
+        .op(0, KM, 0).op(1, KANY).out(STAIR_VAL_VEC, 1).clip_frames().grads(FAN_MAP).tiles(2).owns(SV_CAT, SV_B).saves(SV_A, SV_B),
+    // (column 1: the keyword row of variant 0, 0 for a keyword string; its gradient counts in variant 0 only)
+    MR("FilterFrame", 2, "FilterFrame(feat [T,H], keyword)").kw("FilterFrame keyword must be a [H] vector or relations/actions (modules.py:384-388)")
+        .op(0, KM, 0).op(1, KANY, 1).out(STAIR_VAL_MAP, 2).clip_frames().grads(FAN_MAP, FAN_VEC).tiles(3).owns(0, SV_B | SV_RS | SV_EXTRA).saves(SV_A, SV_B),
+    MR("HasItem", 1, "HasItem(feat [T,H])").op(0, KM, 0).out(STAIR_VAL_FRAME, 1).clip_frames().grads(FAN_MAP).tiles(1).owns(0, SV_A).saves(SV_A),
+    // Localize, Superlative: pair / action-row columns, built by hand in interpret_programs (and Superlative's action rows in build_grad_fanin)
+    MR("Localize", 2, "Localize(feat [T,H], keyword [H] or [2,H])").op(0, KM).op(1, KV | KP).grads(FAN_MAP, FAN_NONE, FAN_VEC).tiles(1)
+        .owns(0, SV_B | SV_K).saves(SV_A, SV_B),
+    MR("Relate", 2, "Relate(mode, attn [T])").op(0, KS).op(1, KF, 0).out(STAIR_VAL_FRAME, 1).clip_frames().grads(FAN_ATT),
+    MR("Superlative", 3, "Superlative(mode, actions [Ka,H], feat [T,H])").op(0, KS).op(1, KM | KP | KV).op(2, KM).grads(FAN_MAP).tiles(1)
+        .owns(SV_B, SV_B | SV_K | SV_SUP | SV_CAT).saves(SV_A, SV_B),
+    // Temporal: by hand too -- the only module with a second output (the related attention row) and an operand's width as a column
+    // (column 2, the rows per operand of column 1's gradient)
+    MR("Temporal", 3, "Temporal(mode, feat [T,H], attention [K,T])").kw("Temporal mode must be while/before/after/between (modules.py:263,279)")
+        .op(0, KS).op(1, KM).op(2, KA).grads(FAN_MAP, FAN_ATT).tiles(0).owns(0, SV_A).saves(SV_A),
+    MR("ToAction", 2, "needs two [H] vectors").vec(IN_CAT2, false, 1).owns(SV_HID, 0).saves(SV_HID),    // modules.py:102-120: cat[action, keyword]
+    MR("Xor", 2, "needs two [H] vectors").vec(IN_XOR, false, 0),                                         // modules.py:59-72: cat[|a-b|, a, b]
+    MR("XorFrame", 2, "needs two [H] vectors or two [T] frame attentions").op(0, KV | KF, 0).op(1, KV | KF, 1).out(OUT_AS_FIRST, 2).grads(FAN_SUB, FAN_SUB),
+    MR("Array2", 2, "Array2(a [H], b [H])").op(0, KV).op(1, KV),                                         // an alias of its operands: no bucket
+};
+static_assert(kModules[STAIR_OP_ARRAY2].arity == 2 && kModules[STAIR_OP_TEMPORAL].tile, "a row per STAIR_OP_*, in that order");
+inline bool is_tile_op(int op) { return op >= 0 && op < STAIR_OP_COUNT && kModules[op].tile; }
+// the bucket's backward pass is a chain on the tile operator (FilterFrame with a tensor keyword, variant 0, keeps the launch
+// sequence: its attention's adjoint runs between the layers)
+inline bool runs_chain(const Bucket &b) { return is_tile_op(b.op) && !(b.op == STAIR_OP_FILTERFRAME && b.variant == 0); }
 
 }  // namespace
 
@@ -617,7 +715,6 @@ int64_t ctx_weight_floats(const stair_ctx *ctx) {
 // launches again), and before the backward pass walks the level that PRODUCED the slot the staging slots are added to it in index
 // order by one small kernel (grad_fanin_kernel).  The columns below replace the operand columns wherever a gradient is scattered.
 struct GEdge { int32_t slot; int level; int bidx, col, pos; int width; };
-enum { FAN_VEC = 0, FAN_MAP = 1, FAN_ATT = 2 };
 
 // First-touch stores.  The backward pass walks the levels from the top down and a gradient target of the map arena (a slot or one of
 // its staging tiles) has at most one writer per level, so the first writer of target j of a slot (0: the slot, j >= 1: staging tile
@@ -631,12 +728,7 @@ void mark_store_first(stair_plan *pl, const std::vector<GEdge> &E) {
     std::vector<char> stored(n_targets, 0);
     pl->n_store_first = 0;
     for (Bucket &b : pl->buckets) { b.scol.clear(); b.soff = -1; }
-    auto chain_writer = [&](const GEdge &g) {
-        if (g.bidx < 0 || g.col != 0) return false;
-        const Bucket &b = pl->buckets[g.bidx];
-        return b.op == STAIR_OP_FILTER || (b.op == STAIR_OP_FILTERFRAME && b.variant != 0) || b.op == STAIR_OP_HASITEM ||
-               b.op == STAIR_OP_LOCALIZE || b.op == STAIR_OP_SUPERLATIVE || b.op == STAIR_OP_TEMPORAL;
-    };
+    auto chain_writer = [&](const GEdge &g) { return g.bidx >= 0 && g.col == 0 && runs_chain(pl->buckets[g.bidx]); };
     for (size_t i = 0; i < E.size();) {
         size_t e = i;
         while (e < E.size() && E[e].slot == E[i].slot) ++e;
@@ -677,34 +769,24 @@ int build_grad_fanin(stair_plan *pl, int T, std::vector<int32_t *> &vec_fix) {
             b.gcol[c] = b.col[c];
             for (int p = 0; p < (int)b.col[c].size(); ++p) dst.push_back({b.col[c][p], b.level, bi, c, p, w ? (*w)[p] : width});
         };
-        switch (b.op) {
-            case STAIR_OP_AND: case STAIR_OP_XORFRAME:
-                if (b.sub == STAIR_VAL_VEC) { all(ev, 0); all(ev, 1); } else { all(ea, 0); all(ea, 1); }
-                break;
-            case STAIR_OP_ATTNVIDEO: all(em, 0); all(ea, 1); break;
-            case STAIR_OP_CHOOSE: all(ev, 0); all(ev, 1); break;
-            case STAIR_OP_COMPARE: case STAIR_OP_EQUALS: case STAIR_OP_XOR: case STAIR_OP_TOACTION: case STAIR_OP_EXISTS:
-                all(ev, 0); all(ev, 1); break;
-            case STAIR_OP_EXISTSFRAME: all(ev, 0); all(em, 1); break;
-            case STAIR_OP_FILTER: all(em, 0); break;
-            case STAIR_OP_FILTERFRAME: all(em, 0); if (b.variant == 0) all(ev, 1); break;
-            case STAIR_OP_HASITEM: all(em, 0); break;
-            case STAIR_OP_LOCALIZE: all(em, 0); all(ev, 2); break;
-            case STAIR_OP_RELATE: all(ea, 0); break;
-            case STAIR_OP_TEMPORAL: all(em, 0); all(ea, 1, 1, &b.col[2]); break;
-            case STAIR_OP_SUPERLATIVE: {
-                all(em, 0);
-                // action rows (before they are resolved to global row ids): >= 0 a vec row, < 0 row a of map tile -(rid + 1) / T;
-                // a map tile is ONE operand of its instance (edge at its first row)
-                b.gcol[4] = b.col[4];
-                for (int p = 0; p < (int)b.col[4].size(); ++p) {
-                    const int rid = b.col[4][p];
-                    if (rid >= 0) ev.push_back({rid, b.level, bi, 4, p, 1});
-                    else if ((-rid - 1) % T == 0) em.push_back({(-rid - 1) / T, b.level, bi, 4, p, 1});
-                }
-                break;
+        if (b.op < 0 || b.op >= STAIR_OP_COUNT) continue;                  // (the span means: no gradient through the slots)
+        std::vector<GEdge> *arena[4] = {&ev, &em, &ea, b.sub == STAIR_VAL_VEC ? &ev : &ea};      // FAN_VEC, FAN_MAP, FAN_ATT, FAN_SUB
+        for (int c = 0; c < 3; ++c) {
+            const int fan = kModules[b.op].grad[c];
+            if (fan == FAN_NONE) continue;
+            if (b.op == STAIR_OP_FILTERFRAME && c == 1 && b.variant != 0) continue;      // (a keyword string: column 1 holds no slot)
+            if (b.op == STAIR_OP_TEMPORAL && c == 1) all(*arena[fan], c, 1, &b.col[2]);  // (an attention of col[2] rows)
+            else all(*arena[fan], c);
+        }
+        if (b.op == STAIR_OP_SUPERLATIVE) {
+            // action rows (before they are resolved to global row ids): >= 0 a vec row, < 0 row a of map tile -(rid + 1) / T;
+            // a map tile is ONE operand of its instance (edge at its first row)
+            b.gcol[4] = b.col[4];
+            for (int p = 0; p < (int)b.col[4].size(); ++p) {
+                const int rid = b.col[4][p];
+                if (rid >= 0) ev.push_back({rid, b.level, bi, 4, p, 1});
+                else if ((-rid - 1) % T == 0) em.push_back({(-rid - 1) / T, b.level, bi, 4, p, 1});
             }
-            default: break;
         }
     }
     pl->groots = pl->roots;
@@ -797,7 +879,7 @@ struct Builder {
 
 std::string where(int q, int i, int tok) {
     std::string s = "question " + std::to_string(q) + ", token " + std::to_string(i);
-    if (tok >= 0 && tok < STAIR_OP_COUNT) s += std::string(" (") + kOpName[tok] + ")";
+    if (tok >= 0 && tok < STAIR_OP_COUNT) s += std::string(" (") + kModules[tok].name + ")";
     return s;
 }
 
@@ -881,7 +963,8 @@ int interpret_programs(stair_plan *pl, const int32_t *prog_off, const int32_t *t
             const int tok = tokens[i];
             Node &nd = pl->nodes[i];
             if (tok >= 0 && tok < STAIR_OP_COUNT) {
-                const int ar = kArity[tok];
+                const ModuleRow &m = kModules[tok];
+                const int ar = m.arity;
                 STAIR_CHECK((int)stack.size() >= ar, "invalid program (stack underflow) at " + where(q, i, tok));
                 int ch[3] = {-1, -1, -1};
                 int lvl = 0;
@@ -940,85 +1023,14 @@ int interpret_programs(stair_plan *pl, const int32_t *prog_off, const int32_t *t
                         break;
                     default: break;
                 }
+                // the operand kinds the module takes, then the keyword / mode it has a variant for
+                const Node *cs[3] = {&c0, &c1, &c2};
+                for (int k = 0; k < ar; ++k)
+                    if (cs[k]->kind < 0 || !((m.in[k].kinds >> cs[k]->kind) & 1)) return bad(m.refuse);
+                if (m.out_kind == OUT_AS_FIRST && c0.kind != c1.kind) return bad(m.refuse);
+                if (variant < 0) return bad(m.refuse_kw);
                 switch (tok) {
-                    case STAIR_OP_AND:
-                    case STAIR_OP_XORFRAME: {
-                        if (!(c0.kind == c1.kind && (c0.kind == STAIR_VAL_VEC || c0.kind == STAIR_VAL_FRAME)))
-                            return bad("needs two [H] vectors or two [T] frame attentions");
-                        nd.kind = c0.kind;
-                        nd.slot = c0.kind == STAIR_VAL_VEC ? pl->n_vec++ : pl->n_att++;
-                        Bucket &b = B.bucket(nd.level, tok, 0, sub);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(c1.slot); b.col[2].push_back(nd.slot);
-                        b.cnt++;
-                        break;
-                    }
-                    case STAIR_OP_ATTNVIDEO: {
-                        if (c0.kind != STAIR_VAL_MAP || c1.kind != STAIR_VAL_FRAME) return bad("AttnVideo(feat [T,H], attn [T])");
-                        nd.kind = STAIR_VAL_MAP; nd.slot = pl->n_map++;
-                        Bucket &b = B.bucket(nd.level, tok, 0, 0);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(c1.slot); b.col[2].push_back(nd.slot);
-                        b.cnt++;
-                        break;
-                    }
-                    case STAIR_OP_CHOOSE: {
-                        if (c0.kind != STAIR_VAL_VEC || c1.kind != STAIR_VAL_VEC || c2.kind != STAIR_VAL_VEC)
-                            return bad("Choose(kw1 [H], kw2 [H], query [H])");
-                        nd.kind = STAIR_VAL_VEC; nd.slot = pl->n_vec++;
-                        Bucket &b = B.bucket(nd.level, tok, 0, 0);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(c1.slot); b.col[2].push_back(c2.slot);
-                        b.col[3].push_back(nd.slot);
-                        b.cnt++;
-                        break;
-                    }
-                    case STAIR_OP_COMPARE:
-                    case STAIR_OP_EQUALS:
-                    case STAIR_OP_XOR:
-                    case STAIR_OP_TOACTION:
-                    case STAIR_OP_EXISTS: {
-                        if (c0.kind != STAIR_VAL_VEC || c1.kind != STAIR_VAL_VEC) return bad("needs two [H] vectors");
-                        nd.kind = STAIR_VAL_VEC; nd.slot = pl->n_vec++;
-                        Bucket &b = B.bucket(nd.level, tok, 0, 0);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(c1.slot); b.col[2].push_back(nd.slot);
-                        b.cnt++;
-                        break;
-                    }
-                    case STAIR_OP_EXISTSFRAME: {
-                        if (c0.kind != STAIR_VAL_VEC || c1.kind != STAIR_VAL_MAP) return bad("ExistsFrame(keyword [H], feat [T,H])");
-                        nd.kind = STAIR_VAL_FRAME; nd.slot = pl->n_att++;
-                        Bucket &b = B.bucket(nd.level, tok, 0, 0);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(c1.slot); b.col[2].push_back(nd.slot);
-                        b.cnt++;
-                        break;
-                    }
-                    case STAIR_OP_FILTER: {
-                        if (c0.kind != STAIR_VAL_MAP) return bad("Filter(feat [T,H], keyword)");
-                        if (variant < 0) return bad("Filter keyword must be a [H] vector or actions/objects/relations (modules.py:346-351)");
-                        nd.kind = STAIR_VAL_VEC; nd.slot = pl->n_vec++;
-                        Bucket &b = B.bucket(nd.level, tok, variant, 0);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(nd.slot); b.col[6].push_back(Lq);
-                        b.cnt++;
-                        break;
-                    }
-                    case STAIR_OP_FILTERFRAME: {
-                        if (c0.kind != STAIR_VAL_MAP) return bad("FilterFrame(feat [T,H], keyword)");
-                        if (variant < 0) return bad("FilterFrame keyword must be a [H] vector or relations/actions (modules.py:384-388)");
-                        nd.kind = STAIR_VAL_MAP; nd.slot = pl->n_map++;
-                        Bucket &b = B.bucket(nd.level, tok, variant, 0);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(variant == 0 ? c1.slot : 0); b.col[2].push_back(nd.slot); b.col[6].push_back(Lq);      // (the clip's frames: segments of a long clip behind its end are not computed)
-                        b.cnt++;
-                        break;
-                    }
-                    case STAIR_OP_HASITEM: {
-                        if (c0.kind != STAIR_VAL_MAP) return bad("HasItem(feat [T,H])");
-                        nd.kind = STAIR_VAL_FRAME; nd.slot = pl->n_att++;
-                        Bucket &b = B.bucket(nd.level, tok, 0, 0);
-                        b.col[0].push_back(c0.slot); b.col[1].push_back(nd.slot); b.col[6].push_back(Lq);
-                        b.cnt++;
-                        break;
-                    }
                     case STAIR_OP_LOCALIZE: {
-                        if (c0.kind != STAIR_VAL_MAP || !(c1.kind == STAIR_VAL_VEC || c1.kind == STAIR_VAL_PAIR))
-                            return bad("Localize(feat [T,H], keyword [H] or [2,H])");
                         const int K = c1.kind == STAIR_VAL_PAIR ? 2 : 1;
                         nd.kind = STAIR_VAL_ATT; nd.slot = pl->n_att; nd.aux = K;
                         pl->n_att += K;
@@ -1035,18 +1047,7 @@ int interpret_programs(stair_plan *pl, const int32_t *prog_off, const int32_t *t
                         b.cnt++;
                         break;
                     }
-                    case STAIR_OP_RELATE: {
-                        if (c0.kind != STAIR_VAL_STR || c1.kind != STAIR_VAL_FRAME) return bad("Relate(mode, attn [T])");
-                        nd.kind = STAIR_VAL_FRAME; nd.slot = pl->n_att++;
-                        Bucket &b = B.bucket(nd.level, tok, variant, 0);
-                        b.col[0].push_back(c1.slot); b.col[1].push_back(nd.slot); b.col[6].push_back(Lq);
-                        b.cnt++;
-                        break;
-                    }
                     case STAIR_OP_SUPERLATIVE: {
-                        if (c0.kind != STAIR_VAL_STR || c2.kind != STAIR_VAL_MAP ||
-                            !(c1.kind == STAIR_VAL_MAP || c1.kind == STAIR_VAL_PAIR || c1.kind == STAIR_VAL_VEC))
-                            return bad("Superlative(mode, actions [Ka,H], feat [T,H])");
                         nd.kind = STAIR_VAL_VEC; nd.slot = pl->n_vec++;
                         Bucket &b = B.bucket(nd.level, tok, variant, 0);
                         b.col[0].push_back(c2.slot);          // feat map
@@ -1067,9 +1068,6 @@ int interpret_programs(stair_plan *pl, const int32_t *prog_off, const int32_t *t
                         break;
                     }
                     case STAIR_OP_TEMPORAL: {
-                        if (c0.kind != STAIR_VAL_STR || c1.kind != STAIR_VAL_MAP || c2.kind != STAIR_VAL_ATT)
-                            return bad("Temporal(mode, feat [T,H], attention [K,T])");
-                        if (variant < 0) return bad("Temporal mode must be while/before/after/between (modules.py:263,279)");
                         nd.kind = STAIR_VAL_MAP; nd.slot = pl->n_map++; nd.rel = pl->n_att++;
                         Bucket &b = B.bucket(nd.level, tok, variant, 0);
                         b.col[0].push_back(c1.slot); b.col[1].push_back(c2.slot); b.col[2].push_back(c2.aux);
@@ -1077,13 +1075,20 @@ int interpret_programs(stair_plan *pl, const int32_t *prog_off, const int32_t *t
                         b.cnt++;
                         break;
                     }
-                    case STAIR_OP_ARRAY2: {
-                        if (c0.kind != STAIR_VAL_VEC || c1.kind != STAIR_VAL_VEC) return bad("Array2(a [H], b [H])");
+                    case STAIR_OP_ARRAY2:
                         nd.kind = STAIR_VAL_PAIR; nd.slot = c0.slot; nd.aux = c1.slot;   // alias, no launch
                         break;
+                    default: {                      // the row says it all: operand slots and the output's slot into their columns
+                        nd.kind = m.out_kind == OUT_AS_FIRST ? c0.kind : m.out_kind;
+                        nd.slot = nd.kind == STAIR_VAL_VEC ? pl->n_vec++ : nd.kind == STAIR_VAL_MAP ? pl->n_map++ : pl->n_att++;
+                        Bucket &b = B.bucket(nd.level, tok, variant, sub);
+                        for (int k = 0; k < ar; ++k)
+                            if (m.in[k].col >= 0) b.col[m.in[k].col].push_back(cs[k]->kind == STAIR_VAL_STR ? 0 : cs[k]->slot);   // (a keyword string has no slot)
+                        b.col[m.out_col].push_back(nd.slot);
+                        if (m.frames) b.col[6].push_back(Lq);      // (the clip's frames: T-mixing operators, and segments of a long clip behind its end are not computed)
+                        b.cnt++;
+                        break;
                     }
-                    default:
-                        STAIR_FAIL("unknown module token at " + where(q, i, tok));
                 }
                 if (tok != STAIR_OP_ARRAY2) {         // ... and as which of its instances
                     nd.bop = tok; nd.bvariant = variant; nd.bsub = sub;
@@ -1146,13 +1151,7 @@ int build_index_image(stair_plan *pl, const int32_t *q_off) {
     pl->maxV = n;
     for (Bucket &b : pl->buckets) {
         pl->n_levels = std::max(pl->n_levels, b.level + 1);
-        switch (b.op) {
-            case STAIR_OP_FILTER: case STAIR_OP_FILTERFRAME: case STAIR_OP_HASITEM: case STAIR_OP_LOCALIZE:
-            case STAIR_OP_SUPERLATIVE: case STAIR_OP_TEMPORAL:
-                pl->maxI = std::max(pl->maxI, b.cnt);
-                break;
-            default: break;
-        }
+        if (is_tile_op(b.op)) pl->maxI = std::max(pl->maxI, b.cnt);
         pl->maxV = std::max(pl->maxV, b.cnt);
         if (b.op == STAIR_OP_LOCALIZE) pl->maxK = std::max(pl->maxK, b.nrows);
         if (b.op == STAIR_OP_SUPERLATIVE) {
@@ -1302,33 +1301,15 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
         Bucket &b = pl->buckets[bi];
         b.svA = pl->o_tmpA; b.svB = pl->o_tmpB; b.svK = pl->o_kbuf; b.svCat = pl->o_cat; b.svHid = pl->o_hid;
         b.svRs = pl->o_rs; b.svSup = pl->o_sup; b.svExtra = pl->o_extra;
-        if (!pl->train) {
-            // inference: the tile operators of one level run in ONE launch (fused path), so what a bucket's tile operator
-            // writes for its own later launches must not be shared with the level's other buckets
-            if (pl->o_wfrag > 0 && b.cnt > 0) {
-                if (b.op == STAIR_OP_FILTER) b.svCat = pl->take(".svCat", (int64_t)b.cnt * H, 64, bi);
-                if (b.op == STAIR_OP_SUPERLATIVE) b.svB = pl->take(".svB", (int64_t)b.cnt * T * H, 64, bi);
-                // the grouped vector-level launches: a two-layer module's hidden rows live from the level's first launch to its second
-                if (b.op == STAIR_OP_EXISTS || b.op == STAIR_OP_TOACTION) b.svHid = pl->take(".svHid", (int64_t)b.cnt * H, 64, bi);
-            }
-            continue;
-        }
-        const int64_t c = b.cnt;
-        switch (b.op) {
-            // (svA of Filter / FilterFrame / Localize / Superlative lives in the per-weight region wg_sx, assigned below)
-            case STAIR_OP_FILTER:            // (svCat, the pooled rows = the dense layer's input, lives in the per-weight region vd_x)
-                b.svB = pl->take(".svB", c * T * H, 64, bi); break;
-            case STAIR_OP_FILTERFRAME:
-                b.svB = pl->take(".svB", c * T * H, 64, bi); b.svRs = pl->take(".svRs", c * T, 64, bi); b.svExtra = pl->take(".svExtra", c, 64, bi); break;
-            case STAIR_OP_HASITEM:
-            case STAIR_OP_TEMPORAL:
-                b.svA = pl->take(".svA", c * T * H, 64, bi); break;
-            case STAIR_OP_LOCALIZE:
-                b.svB = pl->take(".svB", c * T * H, 64, bi); b.svK = pl->take(".svK", (int64_t)b.nrows * H, 64, bi); break;
-            case STAIR_OP_SUPERLATIVE:
-                b.svB = pl->take(".svB", c * T * H, 64, bi); b.svK = pl->take(".svK", (int64_t)b.nrows * H, 64, bi);
-                b.svSup = pl->take(".svSup", (int64_t)b.nrows * T, 64, bi); b.svCat = pl->take(".svCat", c * H, 64, bi); break;
-            default: break;                  // (the vector-level modules' packed inputs and hidden rows: per-weight regions vd_x)
+        // What the bucket owns instead (ModuleRow::own_*).  Inference: the tile operators of one level run in ONE launch (fused path), and
+        // so do the grouped vector-level problems (a two-layer module's hidden rows live from the level's first launch to its second), so
+        // what a bucket writes for its own later launches must not be shared with the level's other buckets.  Training: kept until
+        // stair_plan_backward has consumed it.
+        if (b.op < 0 || b.op >= STAIR_OP_COUNT || (!pl->train && !(pl->o_wfrag > 0 && b.cnt > 0))) continue;
+        const uint16_t own = pl->train ? kModules[b.op].own_train : kModules[b.op].own_infer;
+        for (int r = 0; r < 8; ++r) {
+            const SaveRegion &sr = kSaveRegions[r];
+            if (own >> r & 1) b.*sr.off = pl->take(sr.name, (int64_t)(sr.per_row ? b.nrows : b.cnt) * (sr.t ? T : 1) * (sr.h ? H : 1), 64, bi);
         }
     }
     if (pl->train) {
@@ -1391,16 +1372,14 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
             Bucket &b = pl->buckets[bi];
             const int w0 = layers[bi].w0, w3 = layers[bi].w3;
             if (pl->o_wfrag > 0 && b.cnt > 0) {          // the level's backward chains share a launch: no scratch in common
+                // (scratch of one module's chain: Filter's gradient rows of the sum over frames, the third dZ of FilterFrame's three layers)
                 if (b.op == STAIR_OP_FILTER) b.gRow = pl->take("gRow", (int64_t)b.cnt * H, 64);
-                if (b.op == STAIR_OP_FILTERFRAME && b.variant != 0) b.dzC = pl->take("dzC", (int64_t)b.cnt * T * H, 64);
+                if (b.op == STAIR_OP_FILTERFRAME && runs_chain(b)) b.dzC = pl->take("dzC", (int64_t)b.cnt * T * H, 64);
                 const int64_t words = tile_max_tiles(b.cnt, T) * 512 * 2;    // 64-bit words, counted in floats, per TILE: (instance, 64-row segment)
-                switch (b.op) {
-                    case STAIR_OP_FILTER: b.bitA = pl->take(".bitA", words, 64, bi); b.bitB = pl->take(".bitB", words, 64, bi); break;
-                    case STAIR_OP_FILTERFRAME:
-                        b.bitA = pl->take(".bitA", words, 64, bi); b.bitB = pl->take(".bitB", words, 64, bi); b.bitC = pl->take(".bitC", words, 64, bi); break;
-                    case STAIR_OP_HASITEM: case STAIR_OP_LOCALIZE: case STAIR_OP_SUPERLATIVE: b.bitA = pl->take(".bitA", words, 64, bi); break;
-                    default: break;
-                }
+                const int bit_layers = is_tile_op(b.op) ? kModules[b.op].bit_layers : 0;
+                if (bit_layers > 0) b.bitA = pl->take(".bitA", words, 64, bi);
+                if (bit_layers > 1) b.bitB = pl->take(".bitB", words, 64, bi);
+                if (bit_layers > 2) b.bitC = pl->take(".bitC", words, 64, bi);
             }
             if (w0 >= 0) { b.dzA = pl->wg_dz[w0] + at[w0] * T * H; at[w0] += b.cnt; }
             if (w3 >= 0) { b.dzB = pl->wg_dz[w3] + at[w3] * T * H; b.svA = piece(".svA", bi, pl->wg_sx[w3] + at[w3] * T * H, (int64_t)b.cnt * T * H); at[w3] += b.cnt; }
@@ -1617,19 +1596,8 @@ extern "C" int stair_plan_saved_offset(const stair_plan *pl, int32_t tok, int32_
     if (nd.inst < 0) return 0;
     for (const Bucket &b : pl->buckets) {
         if (b.level != nd.level || b.op != nd.bop || b.variant != nd.bvariant || b.sub != nd.bsub) continue;
-        switch (b.op) {
-            case STAIR_OP_FILTER: case STAIR_OP_FILTERFRAME: case STAIR_OP_LOCALIZE: case STAIR_OP_SUPERLATIVE:
-                if (which == 0) *off = b.svA + nd.inst * T * H;
-                else if (which == 1) *off = b.svB + nd.inst * T * H;
-                break;
-            case STAIR_OP_HASITEM: case STAIR_OP_TEMPORAL:
-                if (which == 0) *off = b.svA + nd.inst * T * H;
-                break;
-            case STAIR_OP_EXISTS: case STAIR_OP_TOACTION:
-                if (which == 0) *off = b.svHid + nd.inst * H;
-                break;
-            default: break;
-        }
+        if (const SaveRegion *sr = which == 0 || which == 1 ? save_region(kModules[b.op].saved[which]) : nullptr)
+            *off = b.*(sr->off) + nd.inst * (sr->t ? T : 1) * (sr->h ? H : 1);
         return 0;
     }
     return 0;
@@ -2062,9 +2030,7 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
         const int32_t *LEN = pl->ragged ? didx + b.off[6] : nullptr;       // frames of each instance's clip (T-mixing operators)
         float *tmpA = ws + b.svA, *tmpB = ws + b.svB, *kbuf = ws + b.svK, *cat = ws + b.svCat, *hid = ws + b.svHid;
         float *rsb = ws + b.svRs, *sup = ws + b.svSup, *extra = ws + b.svExtra;
-        const bool tile_op = b.op == STAIR_OP_FILTER || b.op == STAIR_OP_FILTERFRAME || b.op == STAIR_OP_HASITEM ||
-                             b.op == STAIR_OP_LOCALIZE || b.op == STAIR_OP_SUPERLATIVE || b.op == STAIR_OP_TEMPORAL;
-        if (phase == 2 && !(fused && tile_op)) return 0;              // everything else ran in phase 1
+        if (phase == 2 && !(fused && is_tile_op(b.op))) return 0;     // everything else ran in phase 1
         switch (b.op) {
             case OP_SPAN:
                 RUN(launch_span_mean(tok, H, I0, I1, vec, I2, c, H, s));
@@ -2081,87 +2047,45 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
             case STAIR_OP_CHOOSE:
                 RUN(launch_choose(vec, I0, I1, I2, I3, c, H, s));
                 break;
-            case STAIR_OP_COMPARE:      // modules.py:15-21
-            case STAIR_OP_EQUALS: {     // modules.py:24-37
-                if (grouped) {
-                    if (phase != 1) break;
-                    const Lin &l = b.op == STAIR_OP_COMPARE ? W.compare : W.equals;
-                    VgProblem q = vg_fwd(c, vec, I0, H, vec, I1, H, VG_IN_CAT2, l.w, 2 * H, l.b, H, 1, vec, I2, H);
-                    q.wplanes = WF(b.op == STAIR_OP_COMPARE ? WV_CMP : WV_EQ);
-                    if (pl->train) { q.in_save = cat; q.ld_save = 2 * H; }
-                    vg1.push_back(q);
-                    break;
-                }
-                if (fused_vec_for(b)) {
-                    if (phase == 1) tile_queue.push_back(vec_module(b, 1, I0, I1, I2, b.op == STAIR_OP_COMPARE ? WV_CMP : WV_EQ,
-                                                                    b.op == STAIR_OP_COMPARE ? W.compare : W.equals, 0, nullptr, cat, nullptr));
-                    break;
-                }
-                RUN(launch_pack(PACK_CAT2, vec, I0, vec, I1, cat, c, H, s));
-                RUN(dense(s, cat, 2 * H, 2 * H, nullptr, b.op == STAIR_OP_COMPARE ? W.compare : W.equals, 2 * H, vec, H, H,
-                          I2, c, 1, H, 2 * H, 1));
-                break;
-            }
-            case STAIR_OP_XOR:          // modules.py:59-72: cat[|a-b|, a, b]
-                if (grouped) {
-                    if (phase != 1) break;
-                    VgProblem q = vg_fwd(c, vec, I0, H, vec, I1, H, VG_IN_XOR, W.xorl.w, 3 * H, W.xorl.b, H, 1, vec, I2, H);
-                    q.wplanes = WF(WV_XOR);
-                    if (pl->train) { q.in_save = cat; q.ld_save = 3 * H; }
-                    vg1.push_back(q);
-                    break;
-                }
-                if (fused_vec_for(b)) {
-                    if (phase == 1) tile_queue.push_back(vec_module(b, 2, I0, I1, I2, WV_XOR, W.xorl, 0, nullptr, cat, nullptr));
-                    break;
-                }
-                RUN(launch_pack(PACK_XOR, vec, I0, vec, I1, cat, c, H, s));
-                RUN(dense(s, cat, 3 * H, 3 * H, nullptr, W.xorl, 3 * H, vec, H, H, I2, c, 1, H, 3 * H, 1));
-                break;
-            case STAIR_OP_TOACTION:     // modules.py:102-120: cat[action, keyword]
+            case STAIR_OP_COMPARE: case STAIR_OP_EQUALS: case STAIR_OP_XOR: case STAIR_OP_TOACTION: case STAIR_OP_EXISTS: {
+                // Linear . ReLU over the concatenation of the two operand rows, written to the node's row -- or to the hidden rows, which
+                // D . Linear . ReLU [. D] take to the node's row: the form from the module's row, the layers from its VD_* weight rows
+                const ModuleRow &m = kModules[b.op];
+                const VecInForm &in = kVecIn[m.vec_in];
+                const BucketLayers u = bucket_layers(b);
+                const WeightRow &r0 = *WIX.vd[u.v0], *r3 = u.v3 >= 0 ? WIX.vd[u.v3] : nullptr;
+                const Lin &l0 = r0.lin(W), *l3 = r3 ? &r3->lin(W) : nullptr;
+                const int K = r0.nseg * H;
+                const int32_t *Ia = m.vec_swap ? I1 : I0, *Ib = m.vec_swap ? I0 : I1;
+                float *y0 = l3 ? hid : vec;                     // the first layer's output
+                const int32_t *y0_idx = l3 ? nullptr : I2;
                 if (grouped) {              // first layer before the level's tile operators, second layer after them
                     if (phase != 1) break;
-                    VgProblem q = vg_fwd(c, vec, I0, H, vec, I1, H, VG_IN_CAT2, W.ta0.w, 2 * H, W.ta0.b, H, 1, hid, nullptr, H);
-                    q.wplanes = WF(WV_TA0);
-                    if (pl->train) { q.in_save = cat; q.ld_save = 2 * H; }
-                    vg_drop(q, 0);
+                    VgProblem q = vg_fwd(c, vec, Ia, H, vec, Ib, H, in.vg, l0.w, K, l0.b, H, 1, y0, y0_idx, H);
+                    q.wplanes = WF(r0.wv);
+                    if (pl->train) { q.in_save = cat; q.ld_save = K; }
+                    if (m.vec_drops > 0) vg_drop(q, 0);
                     vg1.push_back(q);
-                    vg2.push_back(vg_fwd(c, hid, nullptr, H, nullptr, nullptr, 0, VG_IN_A, W.ta3.w, H, W.ta3.b, H, 1, vec, I2, H));
-                    vg2.back().wplanes = WF(WV_TA3);
+                    if (l3) {
+                        vg2.push_back(vg_fwd(c, hid, nullptr, H, nullptr, nullptr, 0, VG_IN_A, l3->w, H, l3->b, H, 1, vec, I2, H));
+                        vg2.back().wplanes = WF(r3->wv);
+                        if (m.vec_drops > 1) vg_drop(vg2.back(), 1);
+                    }
                     break;
                 }
                 if (fused_vec_for(b)) {
-                    if (phase == 1) tile_queue.push_back(vec_module(b, 1, I0, I1, I2, WV_TA0, W.ta0, WV_TA3, &W.ta3, cat, hid));
+                    if (phase == 1) tile_queue.push_back(vec_module(b, in.vec_pack, Ia, Ib, I2, r0.wv, l0, r3 ? r3->wv : 0, l3, cat, l3 ? hid : nullptr));
                     break;
                 }
-                RUN(launch_pack(PACK_CAT2, vec, I0, vec, I1, cat, c, H, s));
-                RUN(dense(s, cat, 2 * H, 2 * H, nullptr, W.ta0, 2 * H, hid, H, H, nullptr, c, 1, H, 2 * H, 1));
-                RUN(drop(hid, H, nullptr, c, H, 0));
-                RUN(dense(s, hid, H, H, nullptr, W.ta3, H, vec, H, H, I2, c, 1, H, H, 1));
+                RUN(launch_pack(in.pack, vec, Ia, vec, Ib, cat, c, H, s));
+                RUN(dense(s, cat, K, K, nullptr, l0, K, y0, H, H, y0_idx, c, 1, H, K, 1));
+                if (l3) {
+                    if (m.vec_drops > 0) RUN(drop(hid, H, nullptr, c, H, 0));
+                    RUN(dense(s, hid, H, H, nullptr, *l3, H, vec, H, H, I2, c, 1, H, H, 1));
+                    if (m.vec_drops > 1) RUN(drop(vec, H, I2, c, H, 1));
+                }
                 break;
-            case STAIR_OP_EXISTS:       // modules.py:141-159: Exists(keyword, feat) -> cat[feat, keyword, feat*keyword]
-                if (grouped) {
-                    if (phase != 1) break;
-                    VgProblem q = vg_fwd(c, vec, I1, H, vec, I0, H, VG_IN_EXISTS, W.exists0.w, 3 * H, W.exists0.b, H, 1, hid, nullptr, H);
-                    q.wplanes = WF(WV_EX0);
-                    if (pl->train) { q.in_save = cat; q.ld_save = 3 * H; }
-                    vg_drop(q, 0);
-                    vg1.push_back(q);
-                    vg2.push_back(vg_fwd(c, hid, nullptr, H, nullptr, nullptr, 0, VG_IN_A, W.exists3.w, H, W.exists3.b, H, 1, vec, I2, H));
-                    vg2.back().wplanes = WF(WV_EX3);
-                    vg_drop(vg2.back(), 1);
-                    break;
-                }
-                if (fused_vec_for(b)) {
-                    if (phase == 1) tile_queue.push_back(vec_module(b, 3, I1, I0, I2, WV_EX0, W.exists0, WV_EX3, &W.exists3, cat, hid));
-                    break;
-                }
-                RUN(launch_pack(PACK_EXISTS, vec, I1, vec, I0, cat, c, H, s));
-                RUN(dense(s, cat, 3 * H, 3 * H, nullptr, W.exists0, 3 * H, hid, H, H, nullptr, c, 1, H, 3 * H, 1));
-                RUN(drop(hid, H, nullptr, c, H, 0));
-                RUN(dense(s, hid, H, H, nullptr, W.exists3, H, vec, H, H, I2, c, 1, H, H, 1));
-                RUN(drop(vec, H, I2, c, H, 1));
-                break;
+            }
             case STAIR_OP_EXISTSFRAME:  // modules.py:162-178
                 RUN(launch_cosine_attn(map, TH, I1, vec, I0, att, I2, c, T, H, s));
                 break;
@@ -2763,8 +2687,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         // Temporal's backward as a chain of its own kernel form (LayerNorm adjoint in, row-scale adjoint out); unfused plans keep the
         // four-launch sequence per bucket
         const bool temporal_chain = fused && b.op == STAIR_OP_TEMPORAL && b.dzA >= 0;
-        const bool chain_op = fused && (b.op == STAIR_OP_FILTER || (b.op == STAIR_OP_FILTERFRAME && b.variant != 0) || b.op == STAIR_OP_HASITEM ||
-                                        b.op == STAIR_OP_LOCALIZE || b.op == STAIR_OP_SUPERLATIVE || temporal_chain);
+        const bool chain_op = fused && runs_chain(b) && (b.op != STAIR_OP_TEMPORAL || temporal_chain);
         if (phase == 2 && !chain_op) return 0;
         auto mlp_tail = [&](const Lin &l3, const Lin &l0, bool relu_second) -> int {
             if (relu_second) RUN(launch_mask_relu(gB, gB, TH, nullptr, svB, TH, nullptr, c, (int)TH, s, inv_keep));
@@ -2790,45 +2713,36 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
             case STAIR_OP_CHOOSE:
                 RUN(launch_choose_bwd(vec, g_vec, I0, I1, I2, I3, c, H, s, G0, G1));
                 break;
-            case STAIR_OP_COMPARE:
-            case STAIR_OP_EQUALS:
-            case STAIR_OP_XOR: {
-                const bool isx = b.op == STAIR_OP_XOR;
-                const int K = isx ? 3 * H : 2 * H;
-                const Lin &l = isx ? W.xorl : (b.op == STAIR_OP_COMPARE ? W.compare : W.equals);
-                float *dz0 = ws + b.dzV0;                 // this bucket's rows of the weight's dZ region (its product runs once, at the end)
+            case STAIR_OP_COMPARE: case STAIR_OP_EQUALS: case STAIR_OP_XOR: case STAIR_OP_TOACTION: case STAIR_OP_EXISTS: {
+                const ModuleRow &m = kModules[b.op];
+                const VecInForm &in = kVecIn[m.vec_in];
+                const BucketLayers u = bucket_layers(b);
+                const WeightRow &r0 = *WIX.vd[u.v0];
+                const Lin &l0 = r0.lin(W), *l3 = u.v3 >= 0 ? &WIX.vd[u.v3]->lin(W) : nullptr;
+                const int K = r0.nseg * H;
+                const int32_t *Ia = m.vec_swap ? I1 : I0, *Ib = m.vec_swap ? I0 : I1, *Ga = m.vec_swap ? G1 : G0, *Gb = m.vec_swap ? G0 : G1;
+                // this bucket's rows of its weights' dZ regions (their products run once, at the end); dzo: of the layer that wrote the node's row
+                float *dz0 = ws + b.dzV0, *dzo = l3 ? ws + b.dzV3 : dz0;
+                const float out_scale = m.vec_drops > 1 ? inv_keep : 1.0f;       // (a Dropout behind the output's ReLU)
                 if (grouped) {          // dZ = g[out] * relu'(out) on load (kept), dZ W, the concatenation's adjoint: one work list entry
-                    if (phase == 1) bvg1.push_back(vg_adj(c, g_vec, I2, vec, VG_IN_MASK, 1.0f, dz0, l, isx ? 3 : 2, isx ? VG_IN_XOR : VG_IN_CAT2, I0, I1, G0, G1));
-                    break;
-                }
-                RUN(launch_mask_relu(dz0, g_vec, H, I2, vec, H, I2, c, H, s));
-                RUN(dense_bwd(B, dz0, c, 1, H, K, svCat, K, K, nullptr, l, gCat, K, K, nullptr, 0));
-                RUN(launch_pack_bwd(isx ? PACK_XOR : PACK_CAT2, vec, I0, vec, I1, gCat, g_vec, g_vec, c, H, s));
-                break;
-            }
-            case STAIR_OP_TOACTION:
-            case STAIR_OP_EXISTS: {
-                const bool ex = b.op == STAIR_OP_EXISTS;
-                const int K = ex ? 3 * H : 2 * H;
-                float *dz3 = ws + b.dzV3, *dz0 = ws + b.dzV0;
-                if (grouped) {
                     if (phase != 1) break;
+                    if (!l3) { bvg1.push_back(vg_adj(c, g_vec, I2, vec, VG_IN_MASK, 1.0f, dz0, l0, r0.nseg, in.vg, Ia, Ib, Ga, Gb)); break; }
                     // stage 1: dZ3 = g[out] * relu'(out) (kept), dZ0 = (dZ3 W3) * relu'(hidden) written to the first layer's dZ region
-                    VgProblem q = vg_fwd(c, g_vec, I2, H, vec, I2, H, VG_IN_MASK, B.wt + B.wt_off[(ex ? W.exists3 : W.ta3).id], H, nullptr, H, 2, dz0, nullptr, H);
-                    q.in_scale = ex ? inv_keep : 1.0f; q.in_save = dz3; q.ld_save = H; q.emask = svHid; q.ldm = H; q.escale = inv_keep;
-                    q.wplanes = vslot(ex ? W.exists3 : W.ta3);
+                    VgProblem q = vg_fwd(c, g_vec, I2, H, vec, I2, H, VG_IN_MASK, B.wt + B.wt_off[l3->id], H, nullptr, H, 2, dz0, nullptr, H);
+                    q.in_scale = out_scale; q.in_save = dzo; q.ld_save = H; q.emask = svHid; q.ldm = H; q.escale = inv_keep;
+                    q.wplanes = vslot(*l3);
                     bvg1.push_back(q);
-                    // stage 2: dZ0 W0 and the concatenation's adjoint (Exists packs [feat, keyword, feat * keyword] = rows I1, I0)
-                    bvg2.push_back(vg_adj(c, dz0, nullptr, nullptr, VG_IN_A, 1.0f, nullptr, ex ? W.exists0 : W.ta0, ex ? 3 : 2, ex ? VG_IN_EXISTS : VG_IN_CAT2,
-                                          ex ? I1 : I0, ex ? I0 : I1, ex ? G1 : G0, ex ? G0 : G1));
+                    // stage 2: dZ0 W0 and the concatenation's adjoint
+                    bvg2.push_back(vg_adj(c, dz0, nullptr, nullptr, VG_IN_A, 1.0f, nullptr, l0, r0.nseg, in.vg, Ia, Ib, Ga, Gb));
                     break;
                 }
-                RUN(launch_mask_relu(dz3, g_vec, H, I2, vec, H, I2, c, H, s, ex ? inv_keep : 1.0f));     // only Exists ends in ReLU . Dropout
-                RUN(dense_bwd(B, dz3, c, 1, H, H, svHid, H, H, nullptr, ex ? W.exists3 : W.ta3, gV1, H, H, nullptr, 0));
-                RUN(launch_mask_relu(dz0, gV1, H, nullptr, svHid, H, nullptr, c, H, s, inv_keep));
-                RUN(dense_bwd(B, dz0, c, 1, H, K, svCat, K, K, nullptr, ex ? W.exists0 : W.ta0, gCat, K, K, nullptr, 0));
-                if (ex) RUN(launch_pack_bwd(PACK_EXISTS, vec, I1, vec, I0, gCat, g_vec, g_vec, c, H, s));
-                else RUN(launch_pack_bwd(PACK_CAT2, vec, I0, vec, I1, gCat, g_vec, g_vec, c, H, s));
+                RUN(launch_mask_relu(dzo, g_vec, H, I2, vec, H, I2, c, H, s, out_scale));
+                if (l3) {
+                    RUN(dense_bwd(B, dzo, c, 1, H, H, svHid, H, H, nullptr, *l3, gV1, H, H, nullptr, 0));
+                    RUN(launch_mask_relu(dz0, gV1, H, nullptr, svHid, H, nullptr, c, H, s, inv_keep));
+                }
+                RUN(dense_bwd(B, dz0, c, 1, H, K, svCat, K, K, nullptr, l0, gCat, K, K, nullptr, 0));
+                RUN(launch_pack_bwd(in.pack, vec, Ia, vec, Ib, gCat, g_vec, g_vec, c, H, s));
                 break;
             }
             case STAIR_OP_EXISTSFRAME:

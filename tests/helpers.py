@@ -1,16 +1,68 @@
 """Shared helpers for the parity tests (oracle is test infrastructure; see oracle/nmn_oracle.py)."""
+import ctypes as C
 import json
 import os
 
 import numpy as np
 import torch
 
-from stair_amd import synth
+from stair_amd import spec, synth
 from oracle import nmn_oracle as O
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 PRETRAIN_MODULES = frozenset({'Exists', 'Xor', 'Equals', 'Filter', 'ToAction', 'FilterFrame', 'ExistsFrame',
                               'Superlative', 'Localize', 'Temporal', 'decoder'})
+
+
+def plan_ctx(config):
+    """a library context (stair_ctx_create) for `config`; the caller destroys it"""
+    from stair_amd._lib import lib, check, StairConfig
+    cfg = StairConfig(config['hidden_size'], config['video_size'], config['text_size'], config['answer_vocab_length'],
+                      config['max_video_length'], config['object_types'], 1 if config['have_pretrain_head'] else 0)
+    h = C.c_void_p()
+    check(lib.stair_ctx_create(C.byref(cfg), C.byref(h)))
+    return h
+
+
+def int32_ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def pack_programs(programs, spans, q_lens):
+    """The arrays stair_plan_build* takes for a batch: (prog_off, tokens, lo, hi, q_off).  programs: token-name lists;
+    spans[q][i] = (lo, hi) of span token i of program q; q_lens: words per question."""
+    enc = [np.asarray(spec.encode_program(p), dtype=np.int32) for p in programs]
+    n = len(programs)
+    prog_off = np.zeros(n + 1, np.int32); np.cumsum([len(e) for e in enc], out=prog_off[1:])
+    tokens = np.concatenate(enc)
+    lo = np.zeros(len(tokens), np.int32); hi = np.zeros(len(tokens), np.int32)
+    for q in range(n):
+        for i, c in enumerate(enc[q]):
+            if c == spec.TOK_SPAN:
+                lo[prog_off[q] + i], hi[prog_off[q] + i] = spans[q][i]
+    q_off = np.zeros(n + 1, np.int32); np.cumsum(q_lens, out=q_off[1:])
+    return prog_off, tokens, lo, hi, q_off
+
+
+def build_plan(config, programs, spans, q_lens, T, flags=0, video_of_question=None, n_videos=None, video_len=None):
+    """stair_plan_build (or _shared / _ragged, by the arguments given) of a batch in a fresh context: (ctx, plan, rc, prog_off).
+    rc != 0: no plan, the message is in stair_last_error; the caller destroys what it got."""
+    from stair_amd._lib import lib
+    h = plan_ctx(config)
+    prog_off, tokens, lo, hi, q_off = pack_programs(programs, spans, q_lens)
+    n = len(programs)
+    arrays = [int32_ptr(a) for a in (prog_off, tokens, lo, hi, q_off)]
+    plan = C.c_void_p()
+    if video_of_question is None:
+        rc = lib.stair_plan_build(h, n, *arrays, T, flags, C.byref(plan))
+    else:
+        voq = np.asarray(video_of_question, np.int32)
+        if video_len is None:
+            rc = lib.stair_plan_build_shared(h, n, *arrays, n_videos, int32_ptr(voq), T, flags, C.byref(plan))
+        else:
+            vl = np.asarray(video_len, np.int32)
+            rc = lib.stair_plan_build_ragged(h, n, *arrays, n_videos, int32_ptr(voq), int32_ptr(vl), T, flags, C.byref(plan))
+    return h, plan, rc, prog_off
 
 
 def load_golden(name):

@@ -13,7 +13,7 @@ import pytest
 from stair_amd import spec, synth
 from stair_amd import _lib
 from stair_amd._lib import lib, check, StairConfig, PlanInfo, StairError
-from helpers import GOLDEN
+from helpers import GOLDEN, plan_ctx as _ctx, pack_programs, build_plan as _build, int32_ptr as ip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -27,14 +27,6 @@ def test_header_symbols_are_exported_and_bound():
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.stair_abi_version() == 6
-
-
-def _ctx(config):
-    cfg = StairConfig(config['hidden_size'], config['video_size'], config['text_size'], config['answer_vocab_length'],
-                      config['max_video_length'], config['object_types'], 1 if config['have_pretrain_head'] else 0)
-    h = C.c_void_p()
-    check(lib.stair_ctx_create(C.byref(cfg), C.byref(h)))
-    return h
 
 
 CONFIGS = [
@@ -104,24 +96,6 @@ def test_videonmn_state_dict_layout(heads):
     assert np.array_equal(m.state_dict()['submodules.decoder.3.bias'].numpy(), w['submodules.decoder.3.bias'])
 
 
-def _build(config, programs, spans, q_lens, T, flags=0):
-    h = _ctx(config)
-    enc = [np.asarray(spec.encode_program(p), dtype=np.int32) for p in programs]
-    n = len(programs)
-    prog_off = np.zeros(n + 1, np.int32); np.cumsum([len(e) for e in enc], out=prog_off[1:])
-    tokens = np.concatenate(enc)
-    lo = np.zeros(len(tokens), np.int32); hi = np.zeros(len(tokens), np.int32)
-    for q in range(n):
-        for i, c in enumerate(enc[q]):
-            if c == spec.TOK_SPAN:
-                lo[prog_off[q] + i], hi[prog_off[q] + i] = spans[q][i]
-    q_off = np.zeros(n + 1, np.int32); np.cumsum(q_lens, out=q_off[1:])
-    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-    plan = C.c_void_p()
-    rc = lib.stair_plan_build(h, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), T, flags, C.byref(plan))
-    return h, plan, rc, prog_off
-
-
 def test_plan_levels_match_reference_stat_module_levels():
     progs = json.load(open(os.path.join(GOLDEN, 'programs.json')))
     progs.pop('_nary_mappings')
@@ -148,12 +122,36 @@ def test_plan_levels_match_reference_stat_module_levels():
         lib.stair_ctx_destroy(h)
 
 
+KIND = 'stair_plan_build: operand kind mismatch (%s) at question 0, token %d (%s)'
+
+
 @pytest.mark.parametrize('program,msg', [
     (['Filter', 'video'], 'stack underflow'),                              # invalid: missing operand
     (['video', 'video'], 'stack holds 2'),                                 # assert len(stack)==1, module_net.py:135
     (['Temporal', 'while', 'video', 'Localize', 'video', 'x'], 'root must produce'),   # root is a [T,H] map
     (['Filter', 'dish', 'objects'], 'kind mismatch'),                      # feat is not a map
     (['Exists', 'dish', 'Filter', 'video', 'max'], 'Filter keyword'),      # KeyError 'max' in the reference
+    # every operand-kind refusal of the builder, and the second refusals of Filter, FilterFrame and Temporal for a keyword or mode
+    # the module has no variant for: the whole message
+    (['And', 'dish', 'video'], KIND % ('needs two [H] vectors or two [T] frame attentions', 0, 'And')),
+    (['AttnVideo', 'dish', 'video'], KIND % ('AttnVideo(feat [T,H], attn [T])', 0, 'AttnVideo')),
+    (['Choose', 'video', 'a', 'b'], KIND % ('Choose(kw1 [H], kw2 [H], query [H])', 0, 'Choose')),
+    (['Compare', 'video', 'a'], KIND % ('needs two [H] vectors', 0, 'Compare')),
+    (['ExistsFrame', 'video', 'a'], KIND % ('ExistsFrame(keyword [H], feat [T,H])', 0, 'ExistsFrame')),
+    (['Filter', 'dish', 'objects'], KIND % ('Filter(feat [T,H], keyword)', 0, 'Filter')),
+    (['Exists', 'dish', 'Filter', 'video', 'max'],
+     KIND % ('Filter keyword must be a [H] vector or actions/objects/relations (modules.py:346-351)', 2, 'Filter')),
+    (['FilterFrame', 'dish', 'actions'], KIND % ('FilterFrame(feat [T,H], keyword)', 0, 'FilterFrame')),
+    (['FilterFrame', 'video', 'objects'],
+     KIND % ('FilterFrame keyword must be a [H] vector or relations/actions (modules.py:384-388)', 0, 'FilterFrame')),
+    (['HasItem', 'dish'], KIND % ('HasItem(feat [T,H])', 0, 'HasItem')),
+    (['Localize', 'dish', 'a'], KIND % ('Localize(feat [T,H], keyword [H] or [2,H])', 0, 'Localize')),
+    (['Relate', 'forward', 'video'], KIND % ('Relate(mode, attn [T])', 0, 'Relate')),
+    (['Superlative', 'max', 'video', 'dish'], KIND % ('Superlative(mode, actions [Ka,H], feat [T,H])', 0, 'Superlative')),
+    (['Temporal', 'while', 'dish', 'video'], KIND % ('Temporal(mode, feat [T,H], attention [K,T])', 0, 'Temporal')),
+    (['Temporal', 'max', 'video', 'Localize', 'video', 'x'],
+     KIND % ('Temporal mode must be while/before/after/between (modules.py:263,279)', 0, 'Temporal')),
+    (['Array2', 'video', 'a'], KIND % ('Array2(a [H], b [H])', 0, 'Array2')),
 ])
 def test_invalid_programs_are_rejected(program, msg):
     config = dict(spec.DEFAULT_CONFIG)
@@ -161,7 +159,8 @@ def test_invalid_programs_are_rejected(program, msg):
     h, plan, rc, _ = _build(config, [program], [spans], [8], 64)
     try:
         assert rc != 0
-        assert msg in lib.stair_last_error().decode(), lib.stair_last_error()
+        err = lib.stair_last_error().decode()
+        assert err == msg if msg.startswith('stair_plan_build:') else msg in err, err
     finally:
         lib.stair_ctx_destroy(h)
 
@@ -218,17 +217,9 @@ def test_workspace_regions_are_disjoint(train):
     names = sorted(synth.CORPUS)
     qs = [synth.make_question(config, 0, i, form=name, with_video=False) for i, name in enumerate(names)]
     h = _ctx(config)
-    enc = [np.asarray(spec.encode_program(q['nmn_program_list']), dtype=np.int32) for q in qs]
     n = len(qs)
-    prog_off = np.zeros(n + 1, np.int32); np.cumsum([len(e) for e in enc], out=prog_off[1:])
-    tokens = np.concatenate(enc)
-    lo = np.zeros(len(tokens), np.int32); hi = np.zeros(len(tokens), np.int32)
-    for q in range(n):
-        for i, c in enumerate(enc[q]):
-            if c == spec.TOK_SPAN:
-                lo[prog_off[q] + i], hi[prog_off[q] + i] = qs[q]['prog_str_to_question_tokens'][i]
-    q_off = np.zeros(n + 1, np.int32); np.cumsum([q['question'].shape[0] for q in qs], out=q_off[1:])
-    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    prog_off, tokens, lo, hi, q_off = pack_programs([q['nmn_program_list'] for q in qs], [q['prog_str_to_question_tokens'] for q in qs],
+                                                    [q['question'].shape[0] for q in qs])
     plan = C.c_void_p()
     check(lib.stair_plan_build(h, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), 64, 1 if train else 0, C.byref(plan)))
     cap = 8192
@@ -259,17 +250,8 @@ def test_external_projection_plan_leaves_the_projection_regions_out(train):
     qs = [synth.make_question(config, 0, i, form=name, with_video=False) for i, name in enumerate(sorted(synth.CORPUS))]
     programs = [q['nmn_program_list'] for q in qs]
     h = _ctx(config)
-    enc = [np.asarray(spec.encode_program(p), dtype=np.int32) for p in programs]
     n = len(qs)
-    prog_off = np.zeros(n + 1, np.int32); np.cumsum([len(e) for e in enc], out=prog_off[1:])
-    tokens = np.concatenate(enc)
-    lo = np.zeros(len(tokens), np.int32); hi = np.zeros(len(tokens), np.int32)
-    for q in range(n):
-        for i, c in enumerate(enc[q]):
-            if c == spec.TOK_SPAN:
-                lo[prog_off[q] + i], hi[prog_off[q] + i] = qs[q]['prog_str_to_question_tokens'][i]
-    q_off = np.zeros(n + 1, np.int32); np.cumsum([q['question'].shape[0] for q in qs], out=q_off[1:])
-    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    prog_off, tokens, lo, hi, q_off = pack_programs(programs, [q['prog_str_to_question_tokens'] for q in qs], [q['question'].shape[0] for q in qs])
     sizes = {}
     for ext in (0, 4):
         plan = C.c_void_p()
@@ -310,21 +292,15 @@ def test_common_subexpressions_are_aliased_not_recomputed():
     h = _ctx(config)
     forms = ['P1', 'P1', 'P3', 'P3', 'P0', 'P7']
     progs = [synth.CORPUS[f][0] for f in forms]
-    enc = [np.asarray(spec.encode_program(p), dtype=np.int32) for p in progs]
     n = len(progs)
-    prog_off = np.zeros(n + 1, np.int32); np.cumsum([len(e) for e in enc], out=prog_off[1:])
-    tokens = np.concatenate(enc)
     # every span token of a program gets the span (1 + its phrase id): equal phrases -> equal spans
-    lo = np.zeros(len(tokens), np.int32); hi = np.zeros(len(tokens), np.int32)
-    for q in range(n):
+    spans = []
+    for prog in progs:
         phrase = {}
-        for i, c in enumerate(enc[q]):
-            if c == spec.TOK_SPAN:
-                k = phrase.setdefault(progs[q][i], len(phrase))
-                lo[prog_off[q] + i], hi[prog_off[q] + i] = 1 + k, 2 + k
-    q_off = np.zeros(n + 1, np.int32); np.cumsum([9] * n, out=q_off[1:])
+        spans.append({i: (1 + phrase.setdefault(t, len(phrase)), 2 + phrase[t]) for i, t in enumerate(prog)
+                      if t not in spec.OP_CODE and t not in spec.KW_CODE})
+    prog_off, tokens, lo, hi, q_off = pack_programs(progs, spans, [9] * n)
     clip = np.asarray([0, 0, 1, 1, 2, 0], dtype=np.int32)       # questions 0, 1, 5 ask about clip 0; 2, 3 about clip 1
-    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
     info = {}
     slots = {}
     for flag in (0, 2):

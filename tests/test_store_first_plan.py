@@ -7,45 +7,15 @@ import numpy as np
 import pytest
 
 from stair_amd import spec, synth
-from stair_amd._lib import lib, check, StairConfig, PlanInfo
-
-
-def _ctx(config):
-    cfg = StairConfig(config['hidden_size'], config['video_size'], config['text_size'], config['answer_vocab_length'],
-                      config['max_video_length'], config['object_types'], 1 if config['have_pretrain_head'] else 0)
-    h = C.c_void_p()
-    check(lib.stair_ctx_create(C.byref(cfg), C.byref(h)))
-    return h
+from stair_amd._lib import lib, check, PlanInfo
+from helpers import build_plan
 
 
 def _counts(config, programs, spans, q_lens, T, video_of_question=None, n_videos=None, video_len=None, train=True):
     """(n_store_first, n_cleared, PlanInfo) of the plan of a batch."""
-    h = _ctx(config)
-    enc = [np.asarray(spec.encode_program(p), dtype=np.int32) for p in programs]
-    n = len(programs)
-    prog_off = np.zeros(n + 1, np.int32); np.cumsum([len(e) for e in enc], out=prog_off[1:])
-    tokens = np.concatenate(enc)
-    lo = np.zeros(len(tokens), np.int32); hi = np.zeros(len(tokens), np.int32)
-    for q in range(n):
-        for i, c in enumerate(enc[q]):
-            if c == spec.TOK_SPAN:
-                lo[prog_off[q] + i], hi[prog_off[q] + i] = spans[q][i]
-    q_off = np.zeros(n + 1, np.int32); np.cumsum(q_lens, out=q_off[1:])
-    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-    plan = C.c_void_p()
-    flags = 1 if train else 0
+    h, plan, rc, _ = build_plan(config, programs, spans, q_lens, T, 1 if train else 0, video_of_question, n_videos, video_len)
     try:
-        if video_of_question is None:
-            check(lib.stair_plan_build(h, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), T, flags, C.byref(plan)))
-        else:
-            voq = np.asarray(video_of_question, np.int32)
-            if video_len is None:
-                check(lib.stair_plan_build_shared(h, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), n_videos, ip(voq), T, flags,
-                                                  C.byref(plan)))
-            else:
-                vl = np.asarray(video_len, np.int32)
-                check(lib.stair_plan_build_ragged(h, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), n_videos, ip(voq), ip(vl), T,
-                                                  flags, C.byref(plan)))
+        assert rc == 0, lib.stair_last_error()
         info = PlanInfo()
         check(lib.stair_plan_get_info(plan, C.byref(info)))
         a, b = C.c_int32(-1), C.c_int32(-1)
