@@ -715,7 +715,13 @@ int stair_plan_run_flags(stair_ctx *ctx, stair_plan *plan, const float *video, c
  * through decoder, every program level in reverse, and both encoders (BPTT); parameter gradients are
  * accumulated into the buffers given to stair_ctx_set_grad.  loss_out [n] (device, may be NULL)
  * receives the unscaled per-question CE.  answers[i] < 0 leaves question i without a decoder loss (its CE is
- * reported as 0): the train_decoder_after_iters gate of train_module.py:376.  What torch autograd does for :408. */
+ * reported as 0): the train_decoder_after_iters gate of train_module.py:376.  What torch autograd does for :408.
+ * Value range: most weight gradients are summed in 64-bit fixed point (scale 2^44; STAIR_DETERMINISTIC, default on), whose usable
+ * range is +-2^18 = 262144 in gradient units.  Out-of-range values are never hidden: a gradient element that receives a NaN or
+ * +-inf contribution, or one of whose contributions (a workgroup's partial sum) or whose sum of the pass has magnitude >= 2^18, comes
+ * out NON-FINITE (NaN) -- never finite and wrong -- so stair_grad_norm's guard sees it; elements inside the range are bit for bit what
+ * they would be without the checks.  (A sum of in-range contributions is caught as long as the true sum stays inside +-(2^20 - 2^18):
+ * the 64-bit sum wraps at 2^20 gradient units.)  With STAIR_DETERMINISTIC=0 the sums are float atomics, with float's range. */
 int stair_plan_backward(stair_ctx *ctx, stair_plan *plan, const float *video, const float *question,
                         void *workspace, int64_t workspace_bytes, const int32_t *answers, float loss_scale,
                         float *loss_out, int32_t flags, stair_stream stream);

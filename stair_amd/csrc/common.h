@@ -64,19 +64,44 @@ static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * 
 // Inside stair_plan_backward every kernel that ADDS into a weight-gradient tensor from several workgroups (slab partials of the
 // TN products, the bias sums riding along, LayerNorm / Relate / Conv1d / 1-output-Linear gradients) adds into a 64-bit fixed-point
 // shadow of that tensor instead: integer addition is associative, so the sum does not depend on the order in which the atomics
-// land.  Scale 2^44: a contribution is kept to 5.7e-14 absolute (the sums of a step stay far below 2^19); the shadows are added to
+// land.  Scale 2^44: a contribution is kept to 5.7e-14 absolute, the usable range is +-kFxRange (below); the shadows are added to
 // the fp32 gradients by one launch at the end of the pass (csrc/plan.hip det_*).  det_shadow(g): the shadow of the gradient
 // element g points at, or NULL outside a backward pass / for a pointer that is not inside a bound gradient tensor / STAIR_DETERMINISTIC=0.
+//
+// Values outside the fixed-point range are never hidden.  A float sum carries NaN and inf to its result; the conversion to int64
+// does not (NaN converts to 0, inf and anything of magnitude >= 2^19 to an unrelated finite number), and the 64-bit sum wraps.  So:
+//   1. a gradient element that receives a NaN or +-inf contribution comes out non-finite;
+//   2. a gradient element one of whose contributions, or whose sum of the pass, has magnitude >= kFxRange (2^18 = 262144 in gradient
+//      units) comes out non-finite (NaN), never finite and wrong;
+//   3. everything inside the range is the same bits as without these checks.
+// Mechanism: a contribution that is not inside (-kFxRange, kFxRange) is not converted; the site stores NaN into the fp32 gradient
+// element itself (a plain store of one value: nothing else writes that element while the scope is open, and the flush ADDS to it,
+// so it stays NaN).  fx_flush_kernel (csrc/plan.hip) turns a shadow of magnitude >= 2^62 into NaN.  Partial sums wrap modulo 2^64
+// = 2^20 gradient units, so point 2 holds for a sum of in-range contributions as long as the true sum stays inside +-(2^20 - 2^18):
+// a sum beyond that can alias back into the range.  The Temporal chain's per-workgroup accumulators (csrc/tile_mlp.hip) are private
+// to one thread and check every partial sum, with kFxPoison as the sticky mark.
 long long *det_shadow(const float *gptr);
 bool det_enabled();                                      // STAIR_DETERMINISTIC (default 1)
 constexpr float kFxScale = 17592186044416.0f;            // 2^44
+constexpr float kFxRange = 262144.0f;                    // 2^18: usable range of a contribution and of a sum, in gradient units (2^62 / kFxScale)
+constexpr long long kFxLimit = 1ll << 62;                // kFxRange in fixed point
+constexpr long long kFxPoison = -kFxLimit - kFxLimit;    // (INT64_MIN) an accumulator that left the range (fx_acc)
+__device__ __forceinline__ bool fx_in_range(float v) { return fabsf(v) < kFxRange; }       // false for NaN and inf
+__device__ __forceinline__ float fx_nan() { return __int_as_float(0x7fc00000); }
 __device__ __forceinline__ void fx_add(long long *p, float v) {
     atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__float2ll_rn(v * kFxScale));
 }
 // add into the shadow when there is one, else the plain float atomic
 __device__ __forceinline__ void grad_add(float *g, long long *g64, int64_t off, float v) {
-    if (g64) fx_add(g64 + off, v);
-    else unsafeAtomicAdd(g + off, v);
+    if (g64) {
+        if (fx_in_range(v)) fx_add(g64 + off, v);
+        else g[off] = fx_nan();
+    } else unsafeAtomicAdd(g + off, v);
+}
+// a thread-private fixed-point accumulator: acc + v, or kFxPoison (for good) once a contribution or a partial sum is outside the range
+__device__ __forceinline__ long long fx_acc(long long acc, float v) {
+    const long long s = acc + __float2ll_rn(v * kFxScale);       // (two in-range terms cannot wrap)
+    return (acc == kFxPoison || !fx_in_range(v) || s >= kFxLimit || s <= -kFxLimit) ? kFxPoison : s;
 }
 
 // ---- algorithmic-byte accounting of the HBM-bound row kernels (measurement aid, off unless stair_acct_enable(1)) --------

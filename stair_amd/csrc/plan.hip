@@ -2311,7 +2311,11 @@ __global__ void fx_flush_kernel(FxFlushBatch b) {
     float *d = b.dst[t];
     long long *sh = b.src[t];
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < b.count[t]; i += gridDim.x * blockDim.x)
-        if (sh[i] != 0) { d[i] += (float)((double)sh[i] * (1.0 / 17592186044416.0)); sh[i] = 0; }     // (emptied: a second flush adds nothing twice)
+        if (sh[i] != 0) {       // a sum outside the fixed-point range (common.h kFxLimit) comes out as NaN, never as the wrapped number
+            const long long v = sh[i];
+            d[i] += (v >= kFxLimit || v <= -kFxLimit) ? fx_nan() : (float)((double)v * (1.0 / 17592186044416.0));
+            sh[i] = 0;          // (emptied: a second flush adds nothing twice)
+        }
 }
 
 // the shadows of every tensor touched since the last flush -> the fp32 gradients, on stream s

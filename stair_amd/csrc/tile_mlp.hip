@@ -472,8 +472,8 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 const int tid = TM_TID();
 #pragma unroll
                 for (int q = 0; q < 8; ++q) { g += F[(2 * q) * TM_H + tid]; b += F[(2 * q + 1) * TM_H + tid]; }
-                tb_acc[tid] += __float2ll_rn(g * kFxScale);
-                tb_acc[TM_H + tid] += __float2ll_rn(b * kFxScale);
+                tb_acc[tid] = fx_acc(tb_acc[tid], g);               // (kFxPoison once a term or a partial sum left the range)
+                tb_acc[TM_H + tid] = fx_acc(tb_acc[TM_H + tid], b);
             }
             TM_SYNC();
 #pragma unroll
@@ -1220,10 +1220,14 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
     // (thread 0's last head ticket has RETURNED before it signs off -- it branched on the value -- so no fence is needed between the two)
     const int tid = TM_TID();
     if (KIND == 2) {        // column tid of d gamma / d beta: written and read by this thread only, no barrier needed
+        // an accumulator that left the fixed-point range (common.h fx_acc) makes its column NaN: added to the fp32 element, to which
+        // the shadow's flush / the other workgroups' float atomics add as well
         const long long g = tb_acc[tid], b = tb_acc[TM_H + tid];
-        if (pp.fx_g) { if (g) atomicAdd(reinterpret_cast<unsigned long long *>(pp.fx_g + tid), (unsigned long long)g); }
+        if (g == kFxPoison) unsafeAtomicAdd(pp.a[0].dgamma + tid, fx_nan());
+        else if (pp.fx_g) { if (g) atomicAdd(reinterpret_cast<unsigned long long *>(pp.fx_g + tid), (unsigned long long)g); }
         else if (g) unsafeAtomicAdd(pp.a[0].dgamma + tid, __ll2float_rn(g) * (1.0f / kFxScale));
-        if (pp.fx_b) { if (b) atomicAdd(reinterpret_cast<unsigned long long *>(pp.fx_b + tid), (unsigned long long)b); }
+        if (b == kFxPoison) unsafeAtomicAdd(pp.a[0].dbeta + tid, fx_nan());
+        else if (pp.fx_b) { if (b) atomicAdd(reinterpret_cast<unsigned long long *>(pp.fx_b + tid), (unsigned long long)b); }
         else if (b) unsafeAtomicAdd(pp.a[0].dbeta + tid, __ll2float_rn(b) * (1.0f / kFxScale));
     }
     if (pp.counter && tid == 0) {
