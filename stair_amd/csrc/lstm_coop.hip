@@ -16,7 +16,11 @@
 //     write-through (sc1) store / flag / sc1 load protocol of cdna_hip_programming.md Guideline 16 (R1, table row 1 of
 //     MI355X_MICROARCH.md "Valid forms"): every storing wave drains vmcnt, the workgroup barrier, ONE lane stores the
 //     epoch flag; a consumer polls the four flags relaxed, then every load of the slab is an sc1 load.  Two sequence
-//     tiles (A, B) are interleaved so that the hand-off of one tile hides behind the MFMAs of the other.
+//     tiles (A, B) are interleaved so that the hand-off of one tile hides behind the MFMAs of the other;
+//   * training: the activated gates (written over the consumed xproj row) and c are read by BPTT only, and a store issued in
+//     the cell update is waited for by the poll and by the slab loads that follow it (one vmcnt queue for loads and stores).
+//     The gates wait in LDS, c in its registers, and are stored behind the wait for the fetched slab, where nothing of the
+//     hand-off is in flight; they drain under the next compute's MFMA chain (store_saves).
 // Every spin is bounded; on a timeout an error word is set, the launch still drains, and the wave that gave up writes NaN
 // from then on (hidden states forward, gate gradients backward), so the failure reaches the logits / the gradients instead of
 // passing as a plausible result.
@@ -43,6 +47,9 @@ constexpr int CP = 4;                   // workgroups per group (64 units each)
 constexpr int TILE_BYTES = 2 * 32 * CH * 2;      // one sequence tile of h: 2 planes x 32 sequences x 256 bf16 = 32 KB
 constexpr int FLAG_STRIDE = 16;         // uint32 words between flags (64 B: no two flags share a line)
 constexpr unsigned SPIN_LIMIT = 1u << 20;     // ~1 s of polling
+constexpr int SAVE_PLANE = 512 * 16;    // training forward: one parked 16-byte vector per lane; 4 planes (the gates) behind the tiles
+// dynamic LDS of the forward kernels: the h tiles, 64 bytes of arrival counters, in training the parked gates
+constexpr size_t rec_lds_bytes(bool train, int nt) { return (size_t)nt * TILE_BYTES + 64 + (train ? 4 * SAVE_PLANE : 0); }
 
 struct CoopParams {
     float *xproj;             // [rows, 8 Hh]: gate pre-activations from the input projection; training: overwritten with activated gates
@@ -69,8 +76,9 @@ __device__ __forceinline__ int lds_unit(int seq, int chunk) { return (seq * 32 +
 // follow that compute, so part of the latency stays exposed.
 template <bool TRAIN, int NT>
 __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const int b, char *hl) {
-    // hl: [NT tiles][2 planes][32 seq][256] bf16, swizzled
+    // hl: [NT tiles][2 planes][32 seq][256] bf16, swizzled; counters; TRAIN: [4][512 lanes] parked 16-byte vectors
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    char *const sv = TRAIN ? hl + NT * TILE_BYTES + 64 + tid * 16 : nullptr;     // lane-linear: 1 KB contiguous per wave access, read by its writer only
     const int r = lane & 31, hh = lane >> 5;
     // group placement: blocks with equal b % 8 share an XCD (speed only); the 4 workgroups of a group do
     const int q8 = b >> 3;
@@ -124,6 +132,9 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
         __syncthreads();
 
         v4u inflight[4];                                           // slab of the tile being fetched (16 B x 4 per thread)
+        // TRAIN: row and predicate of the compute just done, whose activated gates wait in LDS for store_saves
+        int64_t sv_row = 0;
+        bool sv_active = false;
         // Every wave checks the 4 flags of tile x for epoch ep itself (lanes 0..3), then issues the sc1 loads of its share of
         // the slab: no workgroup barrier between the poll and the loads (MI355X_MICROARCH.md "Valid forms": the wave that
         // polled loads after its poll has matched).
@@ -151,12 +162,29 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
             for (int i = 0; i < 4; ++i)
                 inflight[i] = __builtin_amdgcn_raw_buffer_load_b128(xh_rs, so + (tid + 512 * i) * 16, 0, 16);     // aux 16 = sc1
         };
-        auto fetch_land = [&](const int x) {
+        // TRAIN: the activated gates replace the row's xproj (consumed by the compute that produced them), c is saved.  Nobody
+        // reads them before BPTT, but vmcnt counts loads and stores in ONE queue: stores issued in the cell update stand in
+        // front of the poll (its first test waits for vmcnt(0)) and of the slab loads, so the wave would wait out their
+        // write acknowledgements on the hand-off chain, every compute.  They are issued where nothing of the hand-off is
+        // in flight any more -- behind fetch_land's wait for the slab, in front of its barrier -- and drain under the next
+        // compute's MFMA chain, before the drain that precedes the counter add.  Until then the gates wait in the lane's own
+        // LDS slots (held in registers across the poll and the fetch they spilled) and c in creg[x]; row and predicate are
+        // those of the compute that produced them, nothing is carried into another loop iteration.
+        auto store_saves = [&](const int x) {                      // x: the tile just computed; its c is still in creg[x]
+            if (!sv_active) return;
+            float *gs = p.xproj + sv_row * ldx + xcol;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                *(__attribute__((address_space(1))) v4f *)(gs + q * Hh) = *reinterpret_cast<const v4f *>(sv + q * SAVE_PLANE);
+            *(__attribute__((address_space(1))) v4f *)(p.cbuf + sv_row * 2 * Hh + dir * Hh + U0) = v4f{creg[x][0], creg[x][1], creg[x][2], creg[x][3]};
+        };
+        auto fetch_land = [&](const int x, const int x_done) {       // x_done: the tile whose compute this fetch follows
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int u = tid + 512 * i;                       // 16-byte unit: plane = u >> 10, seq = (u >> 5) & 31, chunk = u & 31
                 *reinterpret_cast<v4u *>(hl + x * TILE_BYTES + (u >> 10) * (32 * CH * 2) + lds_unit((u >> 5) & 31, u & 31)) = inflight[i];
             }
+            if (TRAIN) store_saves(x_done);
             __syncthreads();
         };
         // one tile-step: gates = W h(t-1) + xproj(t); [flag the tile published one compute ago]; cell update; publish h(t)
@@ -218,15 +246,14 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
                 *(__attribute__((address_space(1))) v4f *)(p.out + row * p.ldo + dir * Hh + U0) = hv;
                 if (t == len[x] - 1)                               // h_n = h after the last step of the sequence
                     *(__attribute__((address_space(1))) v4f *)(p.h_n + (int64_t)(s_base + 32 * x + r) * 2 * Hh + dir * Hh + U0) = hv;
-                if (TRAIN) {        // activated gates replace this row's xproj (already consumed), c saved
-                    float *gs = p.xproj + row * ldx + xcol;
-                    *(__attribute__((address_space(1))) v4f *)(gs) = si;
-                    *(__attribute__((address_space(1))) v4f *)(gs + Hh) = sf;
-                    *(__attribute__((address_space(1))) v4f *)(gs + 2 * Hh) = tg;
-                    *(__attribute__((address_space(1))) v4f *)(gs + 3 * Hh) = so;
-                    *(__attribute__((address_space(1))) v4f *)(p.cbuf + row * 2 * Hh + dir * Hh + U0) = cn;
+                if (TRAIN) {        // parked in the lane's own LDS slots until store_saves
+                    *reinterpret_cast<v4f *>(sv) = si;
+                    *reinterpret_cast<v4f *>(sv + SAVE_PLANE) = sf;
+                    *reinterpret_cast<v4f *>(sv + 2 * SAVE_PLANE) = tg;
+                    *reinterpret_cast<v4f *>(sv + 3 * SAVE_PLANE) = so;
                 }
             }
+            if (TRAIN) { sv_row = row; sv_active = active; }
             // publish (finished sequences re-publish their last h): 8 bytes per plane, write-through
             char *slab = p.xh + slab_off(ebase + t + 1, x);
             const int so_ = r * (CH * 2) + U0 * 2;
@@ -234,6 +261,10 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
                                __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store((gu64 *)(slab + 32 * CH * 2 + so_), ((unsigned long long)pl_[1] << 32) | pl_[0], __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
+            // TRAIN: a wait the compiler SEES (the asm drain it does not), where the poll's first test waits anyway.  Without it
+            // the compiler takes the xproj loads for pending still on the paths into the next compute and puts a small vmcnt
+            // in front of that compute's loads, which would hold the wave until most of store_saves' stores are acknowledged.
+            if (TRAIN) __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0)
         };
         // publish -> flag lags one compute.  Schedule of compute k = t * NT + x (tile x, step t): inside it, flag tile
         // (x - 1) % NT; after it, fetch tile (x + 1) % NT [its epoch: the last one it published].
@@ -254,7 +285,9 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
                     compute(x, t, tq >= 0 ? xq : -1, ebase + tq + 1);
                     if (do_fetch) {
                         fetch_issue(xf, ebase + tf + 1);
-                        fetch_land(xf);
+                        fetch_land(xf, x);
+                    } else if (TRAIN) {
+                        store_saves(x);                            // the first and the last compute of a chunk
                     }
                 } else {
                     compute(0, t, -1, 0);
@@ -262,7 +295,8 @@ __device__ __forceinline__ void lstm_rec_coop_body(const CoopParams &p, const in
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __syncthreads();
                     if (tid == 0) __hip_atomic_store(flag_of(0, j), ebase + t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (t + 1 < lmax) { fetch_issue(0, ebase + t + 1); fetch_land(0); }
+                    if (t + 1 < lmax) { fetch_issue(0, ebase + t + 1); fetch_land(0, 0); }
+                    else if (TRAIN) store_saves(0);
                 }
             }
         }
@@ -397,11 +431,11 @@ static int coop_prepare(const stair_lstm_args &a, hipStream_t s, CoopParams &p, 
 static void coop_attrs() {
     bool &attr_set = coop_device().rec_attrs;
     if (attr_set) return;
-#define C_ATTR(TR_, NT_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_kernel<TR_, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, NT_ * TILE_BYTES + 64);
+#define C_ATTR(TR_, NT_) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_kernel<TR_, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rec_lds_bytes(TR_, NT_));
     C_ATTR(false, 1) C_ATTR(false, 2) C_ATTR(true, 1) C_ATTR(true, 2)
 #undef C_ATTR
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_pair_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 * TILE_BYTES + 64);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_pair_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 * TILE_BYTES + 64);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_pair_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rec_lds_bytes(false, 1));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lstm_rec_coop_pair_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rec_lds_bytes(true, 1));
     attr_set = true;
 }
 
@@ -414,8 +448,8 @@ int launch_lstm_rec_coop(const stair_lstm_args &a, hipStream_t s) {
         int gpd = 0;
         coop_geometry(a.n, nt, gpd);
         const int nb = coop_blocks(gpd);
-        const size_t sh = (size_t)nt * TILE_BYTES + 64;
         const bool tr = a.cbuf != nullptr;
+        const size_t sh = rec_lds_bytes(tr, nt);
         const bool ok = nt == 1 ? (tr ? coop_fits(&lstm_rec_coop_kernel<true, 1>, 0, nb, sh) : coop_fits(&lstm_rec_coop_kernel<false, 1>, 1, nb, sh))
                                 : (tr ? coop_fits(&lstm_rec_coop_kernel<true, 2>, 2, nb, sh) : coop_fits(&lstm_rec_coop_kernel<false, 2>, 3, nb, sh));
         if (!ok) return -1;
@@ -423,8 +457,8 @@ int launch_lstm_rec_coop(const stair_lstm_args &a, hipStream_t s) {
     if (int rc = coop_prepare(a, s, p, nt, blocks)) return rc;
     STAIR_ACCT_MFMA("lstm_rec_coop", 0, 2ll * 2 * a.rows * 4 * CH * CH);
 #define C_LAUNCH(NT_)                                                                                                              \
-    if (a.cbuf) hipLaunchKernelGGL((lstm_rec_coop_kernel<true, NT_>), dim3(blocks), dim3(512), NT_ * TILE_BYTES + 64, s, p);        \
-    else hipLaunchKernelGGL((lstm_rec_coop_kernel<false, NT_>), dim3(blocks), dim3(512), NT_ * TILE_BYTES + 64, s, p);
+    if (a.cbuf) hipLaunchKernelGGL((lstm_rec_coop_kernel<true, NT_>), dim3(blocks), dim3(512), rec_lds_bytes(true, NT_), s, p);     \
+    else hipLaunchKernelGGL((lstm_rec_coop_kernel<false, NT_>), dim3(blocks), dim3(512), rec_lds_bytes(false, NT_), s, p);
     if (nt == 1) { C_LAUNCH(1) } else { C_LAUNCH(2) }
 #undef C_LAUNCH
     STAIR_LAUNCH_CHECK();
@@ -442,15 +476,15 @@ int launch_lstm_rec_coop_pair(const stair_lstm_args &a, const stair_lstm_args &b
     if (nta != 1 || ntb != 1) return -1;
     if (coop_blocks(ga) + coop_blocks(gb) > coop_cu_count()) return -1;
     coop_attrs();
-    if (a.cbuf ? !coop_fits(&lstm_rec_coop_pair_kernel<true>, 4, coop_blocks(ga) + coop_blocks(gb), TILE_BYTES + 64)
-               : !coop_fits(&lstm_rec_coop_pair_kernel<false>, 5, coop_blocks(ga) + coop_blocks(gb), TILE_BYTES + 64)) return -1;
+    if (a.cbuf ? !coop_fits(&lstm_rec_coop_pair_kernel<true>, 4, coop_blocks(ga) + coop_blocks(gb), rec_lds_bytes(true, 1))
+               : !coop_fits(&lstm_rec_coop_pair_kernel<false>, 5, coop_blocks(ga) + coop_blocks(gb), rec_lds_bytes(false, 1))) return -1;
     CoopParams pa, pb;
     int blocks_a = 0, blocks_b = 0;
     if (int rc = coop_prepare(a, s, pa, nta, blocks_a)) return rc;
     if (int rc = coop_prepare(b, s, pb, ntb, blocks_b)) return rc;
     STAIR_ACCT_MFMA("lstm_rec_coop_pair", 0, 2ll * 2 * (a.rows + b.rows) * 4 * CH * CH);
-    if (a.cbuf) hipLaunchKernelGGL(lstm_rec_coop_pair_kernel<true>, dim3(blocks_a + blocks_b), dim3(512), 1 * TILE_BYTES + 64, s, pa, pb, blocks_a);
-    else hipLaunchKernelGGL(lstm_rec_coop_pair_kernel<false>, dim3(blocks_a + blocks_b), dim3(512), 1 * TILE_BYTES + 64, s, pa, pb, blocks_a);
+    if (a.cbuf) hipLaunchKernelGGL(lstm_rec_coop_pair_kernel<true>, dim3(blocks_a + blocks_b), dim3(512), rec_lds_bytes(true, 1), s, pa, pb, blocks_a);
+    else hipLaunchKernelGGL(lstm_rec_coop_pair_kernel<false>, dim3(blocks_a + blocks_b), dim3(512), rec_lds_bytes(false, 1), s, pa, pb, blocks_a);
     STAIR_LAUNCH_CHECK();
     return 0;
 }
