@@ -568,6 +568,16 @@ int stair_cosine_topk(const float *queries, int64_t ldq, const int32_t *q_idx, c
                                workspace but live in a caller-owned buffer of stair_projection_floats floats, handed over with
                                stair_plan_set_projection before the first pass.  Their layout depends on the batch SHAPE alone, so
                                stair_encoders_project can fill the buffer before the plan exists (see there). */
+#define STAIR_PLAN_VIDEO_ENCODED 8 /* flags: the clips of this batch were encoded BEFORE (stair_encode_clips): the plan has no video encoder.  Node
+                               table, slots, levels and common subexpressions are those of the plan without the flag; the workspace has no
+                               region that only the video encoder needs (its input projection, W_ih planes, cooperative slabs, h_n).  The
+                               encodings are handed over with stair_plan_set_encoded_video before the first pass; stair_plan_run_flags then
+                               ignores `video` (may be NULL) and, in place of the video projection, recurrence and zero tail, ONE launch
+                               (gather_encoded_video_kernel) copies clip v's video_len[v] rows into map slot v and writes exact zeros
+                               behind them; the text encoder runs alone.  With STAIR_PLAN_EXT_PROJECTION the caller's buffer holds the text
+                               projection only: stair_projection_floats / stair_encoders_project with n_videos = 0 (video may be NULL).
+                               Inference only: combined with STAIR_PLAN_TRAIN every stair_plan_build* fails (a plan of encoded clips has no
+                               encoder to send gradients to). */
 int stair_plan_build(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
                      const int32_t *span_lo, const int32_t *span_hi, const int32_t *q_off, int32_t T,
                      int32_t flags, stair_plan **out);
@@ -706,6 +716,31 @@ int64_t stair_projection_floats(const stair_ctx *ctx, int32_t n_videos, int32_t 
 int stair_encoders_project(stair_ctx *ctx, const void *video, int32_t video_is_bf16, int32_t n_videos, int32_t T,
                            const float *question, int64_t question_rows, float *buf, int64_t buf_floats, stair_stream stream);
 int stair_plan_set_projection(const stair_ctx *ctx, stair_plan *plan, float *buf, int64_t buf_floats);
+/* Encode once, ask many: the video bi-LSTM (module_net.py:74, encode_video :160-163) of n clips on its own, and plans that read its
+ * result instead of running it.
+ *   stair_encode_clips   runs the video encoder exactly as a plan's pass does -- the same input projection (fp32 rows, or bf16 rows with
+ *                        video_is_bf16: V % 32 == 0, bf16x3 mode) and the same recurrence selection, in the context's matmul mode, reading
+ *                        the bound weights at execution time -- on video [n, T, V].  video_len (DEVICE int32 [n], or NULL: every clip has
+ *                        T frames) gives each clip's frames, 1 .. T, padding rows finite.  Clip i's [video_len[i], H] rows are written at
+ *                        out + i * out_rows_cap * H with exact zeros in the rows behind them up to out_rows_cap (>= T); out is device fp32,
+ *                        16-byte aligned.  workspace: 256-byte aligned device scratch of stair_encode_clips_ws_bytes(ctx, n, T,
+ *                        out_rows_cap) bytes (-1 on bad input), free again when the stream has passed the call; its first word is a status
+ *                        word like stair_plan_info.status_off: cleared by the call, 1 when a cooperative recurrence timed out (the rows
+ *                        then hold NaN).  n * out_rows_cap must stay below 2^31: encode a library in chunks.
+ *   stair_plan_set_encoded_video   hands a STAIR_PLAN_VIDEO_ENCODED plan its clips: plan clip v's encoding is the [rows_cap, H] fp32 rows at
+ *                        enc + rows[v] * clip_stride_floats (enc device, 16-byte aligned; clip_stride_floats % 4 == 0, >= rows_cap * H; rows a
+ *                        HOST array of n_videos entries, any order, repeats allowed, each inside the caller's cache -- the library
+ *                        cannot check the upper end).  The clip's own length is the plan's video_len[v] (T when the plan is not ragged);
+ *                        a video_len[v] > rows_cap is refused.  Host-only: nothing is enqueued, the rows travel with the plan's index image
+ *                        (the next stair_plan_run_flags, or stair_plan_upload for a captured plan -- call it before that upload).
+ *                        stair_plan_run_flags refuses to run such a plan before this call.  Lifetime: the cache memory must stay alive
+ *                        and UNMODIFIED until the stream has passed every pass (and every replay of a captured pass) of the plan; the
+ *                        library keeps the pointer, not a copy.  The encodings are those of the weights and the matmul mode they were
+ *                        made with: after either changes, encode again. */
+int64_t stair_encode_clips_ws_bytes(const stair_ctx *ctx, int32_t n, int32_t T, int32_t out_rows_cap);
+int stair_encode_clips(stair_ctx *ctx, const void *video, int32_t video_is_bf16, int32_t n, int32_t T, const int32_t *video_len,
+                       float *out, int32_t out_rows_cap, void *workspace, int64_t workspace_bytes, stair_stream stream);
+int stair_plan_set_encoded_video(stair_plan *plan, const float *enc, int64_t clip_stride_floats, int32_t rows_cap, const int32_t *rows);
 int stair_plan_run_flags(stair_ctx *ctx, stair_plan *plan, const float *video, const float *question,
                          void *workspace, int64_t workspace_bytes, float *logits, int32_t *argmax, int32_t flags,
                          stair_stream stream);

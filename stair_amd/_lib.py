@@ -243,6 +243,10 @@ SIGNATURES = [
     ('stair_encoders_project', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                           C.c_void_p]),
     ('stair_plan_set_projection', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    ('stair_encode_clips_ws_bytes', C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    ('stair_encode_clips', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_int64, C.c_void_p]),
+    ('stair_plan_set_encoded_video', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, c_int32_p]),
     ('stair_plan_run_flags', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p]),
 ]

@@ -253,6 +253,36 @@ __global__ void zero_pad_frames_kernel(float *base, const int32_t *pairs, int T,
     for (int i = L * rowlen + threadIdx.x; i < T * rowlen; i += blockDim.x) p[i] = 0.0f;
 }
 
+// Encoded clips into [T_dst, H] tiles (STAIR_PLAN_VIDEO_ENCODED plans: cached encodings into the plan's first n_vid map slots;
+// stair_encode_clips: a chunk's encodings into cache rows of another row capacity).  Tile v = dst + v * dst_stride receives the first
+// min(len[v], src_rows) (len NULL: src_rows) rows of src + (rows ? rows[v] : v) * src_stride -- a source clip holds src_rows rows, nothing behind
+// them is read -- and exact zeros in the rows behind them up to T_dst - 1: the destination is
+// shared memory that holds an earlier batch's data, and the frames behind a clip's end read as zero everywhere downstream.
+// th4 = T_dst * H / 4, h4 = H / 4; every access is one 16-byte load or store of a 256-byte aligned row.  Grid (clips, chunks).
+__global__ void __launch_bounds__(256) gather_encoded_video_kernel(const float *__restrict__ src, int64_t src_stride, const int32_t *__restrict__ rows,
+                                                                     const int32_t *__restrict__ len, float *__restrict__ dst, int64_t dst_stride,
+                                                                     int th4, int h4, int src_rows) {
+    const int v = blockIdx.x;
+    const int live4 = min(min(len ? len[v] : src_rows, src_rows) * h4, th4);         // float4 elements that are data
+    const float4 *s = reinterpret_cast<const float4 *>(src + (int64_t)(rows ? rows[v] : v) * src_stride);
+    float4 *d = reinterpret_cast<float4 *>(dst + (int64_t)v * dst_stride);
+    // (measured at 2048 clips of 64 x 512: 120 us either way with this loop and with every lane's 8 loads issued before its first store)
+    for (int e = blockIdx.y * blockDim.x + threadIdx.x; e < th4; e += gridDim.y * blockDim.x)
+        d[e] = e < live4 ? s[e] : float4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+
+// the caller has checked: rows[v] inside the source, H % 4 == 0, strides % 4 == 0 and >= the clips' rows, 16-byte aligned bases
+static int launch_gather_encoded_video(const float *src, int64_t src_stride, const int32_t *rows, const int32_t *len, float *dst,
+                                       int64_t dst_stride, int n, int T_dst, int H, int src_rows, hipStream_t s) {
+    if (n <= 0) return 0;
+    const int th4 = T_dst * H / 4;
+    STAIR_ACCT("gather_encoded_video", 2ll * n * T_dst * H * 4);
+    hipLaunchKernelGGL(gather_encoded_video_kernel, dim3(n, (th4 + 2047) / 2048), dim3(256), 0, s, src, src_stride, rows, len, dst, dst_stride,
+                       th4, H / 4, src_rows);
+    STAIR_LAUNCH_CHECK();
+    return 0;
+}
+
 constexpr int OP_SPAN = 50;      // pseudo op: span mean (level 0)
 
 struct Node {
@@ -533,7 +563,7 @@ static ProjLayout proj_layout(const stair_config &g, int64_t n_vid, int64_t T, i
     L.xpv = take("xpv", n_vid * T * 4 * H);
     L.xpt = take("xpt", rows_q * 4 * H);
     L.bias = take("bias", 2 * 4 * H);
-    L.wplanes = g.video_size % 32 == 0 ? take("wplanes", 4 * H * g.video_size) : 0;
+    L.wplanes = g.video_size % 32 == 0 && n_vid > 0 ? take("wplanes", 4 * H * g.video_size) : 0;     // (no clips: a plan of encoded clips, or the text projection alone)
     L.wplanes_t = take("wplanes_t", 4 * H * Ep);
     L.xplanes_t = take("xplanes_t", std::max<int64_t>(rows_q, 1) * Ep);
     L.total = at - base;
@@ -665,7 +695,14 @@ struct stair_plan {
     float *proj = nullptr;
     ProjLayout pj = {};             // the projections' regions as offsets from proj_base(): the workspace, or the caller's buffer
     float *proj_base(float *ws) const { return ext_proj ? proj : ws; }
-    std::vector<Region> regions;    // every region of the workspace, recorded as the builder assigns it (stair_plan_regions)
+    // STAIR_PLAN_VIDEO_ENCODED: no video encoder.  The clips' encodings live in caller-owned memory (stair_plan_set_encoded_video): clip v's
+    // [enc_rows_cap, H] rows at enc + idx[off_encrows + v] * enc_stride; one gather launch puts them into the map slots 0 .. n_vid - 1
+    bool enc_video = false;
+    const float *enc = nullptr;
+    int64_t enc_stride = 0, off_encrows = 0;
+    int32_t enc_rows_cap = 0;
+    int proj_vid() const { return enc_video ? 0 : n_vid; }      // the clips whose input projection the plan lays out and runs
+    std::vector<Region> regions;   // every region of the workspace, recorded as the builder assigns it (stair_plan_regions)
     // the next `nfloats` floats of the workspace, aligned to `align` floats; recorded under `name` unless that is null
     int64_t take(const char *name, int64_t nfloats, int64_t align, int32_t index = -1) {
         total = align_up(total, align);
@@ -1174,6 +1211,7 @@ int build_index_image(stair_plan *pl, const int32_t *q_off) {
         pl->off_lenv = push(pl->vlen);
         pl->off_pad_map = push(pl->pad_map);
         pl->off_pad_att = push(pl->pad_att);
+        if (pl->enc_video) pl->off_encrows = push(std::vector<int32_t>(pl->n_vid, 0));      // cache rows of the clips: stair_plan_set_encoded_video
     }
     std::vector<int32_t *> vec_fix;
     if (pl->train) {
@@ -1267,20 +1305,20 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
     pl->o_att = pl->take("att", (int64_t)std::max(pl->n_att, 1) * T, 64);
     pl->o_tok = pl->take("tok", (int64_t)pl->rows_q * H, 64);
     pl->o_qfeat = pl->take("qfeat", (int64_t)n * H, 64);
-    pl->o_vhn = pl->take("vhn", (int64_t)pl->n_vid * H, 64);
+    pl->o_vhn = pl->take("vhn", (int64_t)pl->proj_vid() * H, 64);      // (a plan of encoded clips runs no video encoder: no vhn, xpv, wplanes, coop)
     // input projections of the two encoders: xproj (the gates of a training plan), bias sums, W_ih planes of the video encoder (bf16
     // features: 2 x [4H, V] bf16), and the text encoder's projection as a plane GEMM (W_ih and the token rows as zero-padded hi / lo
     // planes, counted in floats) -- one block with the layout of proj_layout, here or in the caller's buffer (ext_proj)
     if (pl->ext_proj) {
-        pl->pj = proj_layout(ctx->cfg, pl->n_vid, T, pl->rows_q);
+        pl->pj = proj_layout(ctx->cfg, pl->proj_vid(), T, pl->rows_q);
     } else {
-        pl->pj = proj_layout(ctx->cfg, pl->n_vid, T, pl->rows_q, align_up(pl->total, 64), &pl->regions);
+        pl->pj = proj_layout(ctx->cfg, pl->proj_vid(), T, pl->rows_q, align_up(pl->total, 64), &pl->regions);
         pl->total = align_up(pl->total, 64) + pl->pj.total;
     }
     pl->o_wpack = pl->take("wpack", 2 * 2 * H * H, 64);       // 8*Hh*Hh floats per encoder
     pl->coop_bytes = std::max(lstm_coop_ws_bytes(pl->n_vid), lstm_coop_ws_bytes(n));
     if (pl->train) pl->coop_bytes = std::max(pl->coop_bytes, std::max(lstm_coop_bwd_ws_bytes(pl->n_vid), lstm_coop_bwd_ws_bytes(n)));
-    pl->o_coop = pl->take("coop", (pl->coop_bytes + 3) / 4, 64);   // exchange slabs + flags of the cooperative recurrence (video encoder)
+    pl->o_coop = pl->take("coop", pl->enc_video ? 0 : (pl->coop_bytes + 3) / 4, 64);   // exchange slabs + flags of the cooperative recurrence (video encoder)
     pl->o_coop2 = pl->take("coop2", (pl->coop_bytes + 3) / 4, 64); // the text encoder's: the two recurrences share a launch when both fit on the chip
     pl->o_splitk = pl->take("splitk", kSplitKFloats, 64);      // partial sums of split-K launches (<= 64 output tiles x 16 pieces)
     pl->o_tmpA = pl->take("tmpA", (int64_t)std::max(pl->maxI, 1) * T * H, 64);
@@ -1499,6 +1537,9 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     pl->T = T;
     pl->train = (flags & STAIR_PLAN_TRAIN) != 0;
     pl->ext_proj = (flags & STAIR_PLAN_EXT_PROJECTION) != 0;
+    pl->enc_video = (flags & STAIR_PLAN_VIDEO_ENCODED) != 0;
+    STAIR_CHECK(!(pl->enc_video && pl->train), "STAIR_PLAN_VIDEO_ENCODED cannot be combined with STAIR_PLAN_TRAIN: a plan of encoded clips has no "
+                                               "video encoder to send gradients to (training on cached encodings is not supported)");
     const int ntok = prog_off[n];
     pl->nodes.assign(ntok, Node());
     pl->roots.assign(n, -1);
@@ -1805,7 +1846,8 @@ extern "C" int64_t stair_projection_floats(const stair_ctx *ctx, int32_t n_video
 extern "C" int stair_encoders_project(stair_ctx *ctx, const void *video, int32_t video_is_bf16, int32_t n_videos, int32_t T,
                                       const float *question, int64_t question_rows, float *buf, int64_t buf_floats,
                                       stair_stream stream) {
-    STAIR_CHECK(ctx && video && question && buf, "null argument");
+    STAIR_CHECK(ctx && question && buf, "null argument");
+    STAIR_CHECK(video || n_videos == 0, "null argument");        // n_videos == 0: the text projection alone (STAIR_PLAN_VIDEO_ENCODED plans)
     STAIR_CHECK(n_videos >= 0 && T >= 1 && question_rows >= 0, "bad shape");
     STAIR_CHECK((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "projection buffer must be 256-byte aligned");
     PolicyScope policy_scope(&ctx->policy);
@@ -1821,8 +1863,106 @@ extern "C" int stair_encoders_project(stair_ctx *ctx, const void *video, int32_t
     enc_input(t, g, 1, question, false, (int32_t)question_rows, 1, (int32_t)question_rows);     // (no plan: ONE sequence of all token rows; a run
     enc_projection(a, g, W, 0, buf, L);                                                           // has n of at most max_q rows)
     enc_projection(t, g, W, 1, buf, L);
-    if (int rc = launch_lstm_project(a, s)) return rc;
+    if (n_videos > 0)
+        if (int rc = launch_lstm_project(a, s)) return rc;
     return launch_lstm_project(t, s);
+}
+
+// The encodings of a STAIR_PLAN_VIDEO_ENCODED plan's clips.  Host-only: records the cache and writes the clips' cache rows into the plan's
+// index image, which reaches the device with the next upload (stair_plan_run_flags, or stair_plan_upload for a captured plan).
+extern "C" int stair_plan_set_encoded_video(stair_plan *pl, const float *enc, int64_t clip_stride_floats, int32_t rows_cap,
+                                            const int32_t *rows) {
+    STAIR_CHECK(pl && enc && rows, "null argument");
+    STAIR_CHECK(pl->enc_video, "plan was not built with STAIR_PLAN_VIDEO_ENCODED");
+    const int64_t H = pl->cfg.hidden_size;
+    STAIR_CHECK((reinterpret_cast<uintptr_t>(enc) & 15) == 0 && clip_stride_floats % 4 == 0, "encodings must be 16-byte aligned, clip stride a multiple of 4 floats");
+    STAIR_CHECK(rows_cap >= 1 && clip_stride_floats >= (int64_t)rows_cap * H, "clip stride smaller than rows_cap * hidden_size");
+    for (int v = 0; v < pl->n_vid; ++v) {
+        STAIR_CHECK(pl->vlen[v] <= rows_cap, "video_len[" + std::to_string(v) + "] = " + std::to_string(pl->vlen[v]) +
+                                             " frames exceed the cache's rows_cap = " + std::to_string(rows_cap));
+        STAIR_CHECK(rows[v] >= 0, "rows[" + std::to_string(v) + "] is negative");
+    }
+    if (pl->pin.p && pl->pin_ev) STAIR_HIP(hipEventSynchronize(pl->pin_ev));      // an upload of the old image may still be reading the pinned copy
+    for (int v = 0; v < pl->n_vid; ++v) {
+        pl->idx[pl->off_encrows + v] = rows[v];
+        if (pl->pin.p) pl->pin.p[pl->off_encrows + v] = rows[v];
+    }
+    pl->enc = enc; pl->enc_stride = clip_stride_floats; pl->enc_rows_cap = rows_cap;
+    return 0;
+}
+
+// Workspace of stair_encode_clips, in floats from its (256-byte aligned) base: [status word | sequence offsets | h_n | projection block of
+// n clips and no token rows | packed W_hh | cooperative slabs | the chunk's [n, T, H] rows when the output keeps another row capacity]
+namespace {
+struct EncodeLayout { int64_t status, seq, hn, proj, wpack, coop, tmp, total; ProjLayout pj; int64_t coop_bytes; };
+EncodeLayout encode_layout(const stair_config &g, int64_t n, int64_t T, bool staged) {
+    const int64_t H = g.hidden_size;
+    EncodeLayout L;
+    int64_t at = 0;
+    auto take = [&](int64_t len) { const int64_t o = at; at += align_up(len, 64); return o; };
+    L.status = take(64);
+    L.seq = take(n + 1);
+    L.hn = take(n * H);
+    L.pj = proj_layout(g, n, T, 0, at);
+    L.proj = at; at += L.pj.total;
+    L.wpack = take(2 * H * H);
+    L.coop_bytes = lstm_coop_ws_bytes((int)n);
+    L.coop = take((L.coop_bytes + 3) / 4);
+    L.tmp = take(staged ? n * T * H : 0);
+    L.total = at;
+    return L;
+}
+__global__ void encode_seq_off_kernel(int32_t *seq_off, int n, int T) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= n) seq_off[i] = i * T;
+}
+}  // namespace
+
+extern "C" int64_t stair_encode_clips_ws_bytes(const stair_ctx *ctx, int32_t n, int32_t T, int32_t out_rows_cap) {
+    if (!ctx || n < 0 || T < 1 || out_rows_cap < T || (int64_t)n * std::max(T, out_rows_cap) >= (1ll << 31)) return -1;
+    return encode_layout(ctx->cfg, n, T, out_rows_cap != T).total * (int64_t)sizeof(float);
+}
+
+// The video encoder of a plan's pass on its own: the same argument blocks (enc_input / enc_projection), the same launchers and the same
+// kernel selection as stair_plan_run_flags, for n clips of T frames; the rows go to caller-owned memory with out_rows_cap rows per clip.
+extern "C" int stair_encode_clips(stair_ctx *ctx, const void *video, int32_t video_is_bf16, int32_t n, int32_t T, const int32_t *video_len,
+                                  float *out, int32_t out_rows_cap, void *workspace, int64_t workspace_bytes, stair_stream stream) {
+    STAIR_CHECK(ctx && video && out && workspace, "null argument");
+    STAIR_CHECK(n >= 1 && T >= 1, "n and T must be positive");
+    STAIR_CHECK(out_rows_cap >= T, "out_rows_cap must be at least T");
+    STAIR_CHECK((int64_t)n * out_rows_cap < (1ll << 31), "too many rows for one call: encode in chunks");
+    STAIR_CHECK((reinterpret_cast<uintptr_t>(workspace) & 255) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+                "workspace must be 256-byte aligned, out 16-byte aligned");
+    PolicyScope policy_scope(&ctx->policy);
+    const stair_config &g = ctx->cfg;
+    const int H = g.hidden_size;
+    STAIR_CHECK(!video_is_bf16 || g.video_size % 32 == 0, "bf16 clip features need video_size % 32 == 0");
+    const bool staged = out_rows_cap != T;
+    const EncodeLayout L = encode_layout(g, n, T, staged);
+    STAIR_CHECK(workspace_bytes >= L.total * (int64_t)sizeof(float), "workspace too small (stair_encode_clips_ws_bytes)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Weights W;
+    if (resolve(ctx, W, false)) return 1;
+    float *ws = static_cast<float *>(workspace);
+    int32_t *seq_off = reinterpret_cast<int32_t *>(ws + L.seq);
+    if (int rc = launch_zero(ws + L.status, 64 * sizeof(uint32_t), s)) return rc;
+    hipLaunchKernelGGL(encode_seq_off_kernel, dim3((n + 256) / 256), dim3(256), 0, s, seq_off, n, T);
+    STAIR_LAUNCH_CHECK();
+    stair_lstm_args a = {};
+    enc_input(a, g, 0, video, video_is_bf16 != 0, n * T, n, T);
+    enc_projection(a, g, W, 0, ws, L.pj);
+    a.seq_off = seq_off; a.seq_len = video_len;
+    for (int d = 0; d < 2; ++d) a.w_hh[d] = W.enc[0][4 * d + 1];
+    a.whh_pack_ws = ws + L.wpack;
+    a.coop_ws = ws + L.coop; a.coop_ws_bytes = L.coop_bytes;
+    a.status = reinterpret_cast<uint32_t *>(ws + L.status);
+    a.ldo = H;
+    a.out = staged ? ws + L.tmp : out; a.h_n = ws + L.hn;
+    if (int rc = launch_lstm_project(a, s)) return rc;
+    if (int rc = launch_lstm_recur(a, s)) return rc;
+    if (staged)     // rows of T frames -> rows of out_rows_cap frames, zeros behind each clip's own length
+        return launch_gather_encoded_video(ws + L.tmp, (int64_t)T * H, nullptr, video_len, out, (int64_t)out_rows_cap * H, n, out_rows_cap, H, T, s);
+    return 0;
 }
 
 // The buffer of a STAIR_PLAN_EXT_PROJECTION plan (>= stair_projection_floats of the plan's batch shape); it must stay alive and untouched
@@ -1831,7 +1971,7 @@ extern "C" int stair_plan_set_projection(const stair_ctx *ctx, stair_plan *pl, f
     STAIR_CHECK(ctx && pl && buf, "null argument");
     STAIR_CHECK(pl->ext_proj, "plan was not built with STAIR_PLAN_EXT_PROJECTION");
     STAIR_CHECK((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "projection buffer must be 256-byte aligned");
-    STAIR_CHECK(buf_floats >= proj_layout(pl->cfg, pl->n_vid, pl->T, pl->rows_q).total, "projection buffer too small (stair_projection_floats)");
+    STAIR_CHECK(buf_floats >= proj_layout(pl->cfg, pl->proj_vid(), pl->T, pl->rows_q).total, "projection buffer too small (stair_projection_floats)");
     pl->proj = buf;
     return 0;
 }
@@ -1845,7 +1985,9 @@ extern "C" int stair_plan_run(stair_ctx *ctx, stair_plan *pl, const float *video
 extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float *video, const float *question,
                                     void *workspace, int64_t workspace_bytes, float *logits, int32_t *argmax,
                                     int32_t flags, stair_stream stream) {
-    STAIR_CHECK(ctx && pl && video && question && workspace, "null argument");
+    STAIR_CHECK(ctx && pl && question && workspace, "null argument");
+    STAIR_CHECK(video || pl->enc_video, "null argument");
+    STAIR_CHECK(!pl->enc_video || pl->enc, "plan built with STAIR_PLAN_VIDEO_ENCODED: call stair_plan_set_encoded_video first");
     PolicyScope policy_scope(&ctx->policy);
     STAIR_CHECK(workspace_bytes >= pl->total * (int64_t)sizeof(float), "workspace too small");
     STAIR_CHECK((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
@@ -1895,28 +2037,36 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
         STAIR_CHECK(!pl->ext_proj || pl->proj, "plan built with STAIR_PLAN_EXT_PROJECTION: call stair_plan_set_projection first");
         STAIR_CHECK(!(flags & STAIR_RUN_PROJECTED) || pl->ext_proj, "STAIR_RUN_PROJECTED needs a STAIR_PLAN_EXT_PROJECTION plan");
         STAIR_CHECK(!(flags & STAIR_RUN_VIDEO_BF16) || V % 32 == 0, "bf16 clip features need video_size % 32 == 0");
-        enc_input(a, g, 0, video, (flags & STAIR_RUN_VIDEO_BF16) != 0, pl->n_vid * T, pl->n_vid, T);
         enc_input(t, g, 1, question, false, pl->rows_q, n, pl->max_q);
-        for (int e = 0; e < 2; ++e) {
-            enc_projection(e == 0 ? a : t, g, W, e, pl->proj_base(ws), pl->pj);
-            enc_recurrence(e == 0 ? a : t, pl, W, e, ws, didx);
-        }
-        a.out = map; a.h_n = ws + pl->o_vhn; a.cbuf = pl->train ? ws + pl->o_cv : nullptr;
+        enc_projection(t, g, W, 1, pl->proj_base(ws), pl->pj);
+        enc_recurrence(t, pl, W, 1, ws, didx);
         t.out = tok; t.h_n = qfeat; t.cbuf = pl->train ? ws + pl->o_ct : nullptr;
-
-        // both input projections, then the two recurrences -- in ONE launch while all their workgroups fit on the chip
-        // (csrc/lstm_coop.hip, lstm_rec_coop_pair_kernel), else one after the other
-        if (flags & STAIR_RUN_PROJECTED) {
-            RUN(launch_lstm_zero_tail(a, s));        // (the part of the projection step that writes the plan's own arena)
-        } else {
-            RUN(launch_lstm_project(a, s));
-            RUN(launch_lstm_project(t, s));
-        }
-        const int rc_pair = launch_lstm_rec_coop_pair(a, t, s);
-        if (rc_pair > 0) return rc_pair;
-        if (rc_pair < 0) {
-            RUN(launch_lstm_recur(a, s));
+        if (pl->enc_video) {
+            // STAIR_PLAN_VIDEO_ENCODED: the clips were encoded before (stair_encode_clips).  In place of the video projection, recurrence
+            // and zero tail ONE launch copies each clip's rows from the caller's cache into its map slot; the text encoder runs alone
+            if (!(flags & STAIR_RUN_PROJECTED)) RUN(launch_lstm_project(t, s));
+            RUN(launch_gather_encoded_video(pl->enc, pl->enc_stride, didx + pl->off_encrows, didx + pl->off_lenv, map, TH, pl->n_vid, T, H, pl->enc_rows_cap, s));
             RUN(launch_lstm_recur(t, s));
+        } else {
+            enc_input(a, g, 0, video, (flags & STAIR_RUN_VIDEO_BF16) != 0, pl->n_vid * T, pl->n_vid, T);
+            enc_projection(a, g, W, 0, pl->proj_base(ws), pl->pj);
+            enc_recurrence(a, pl, W, 0, ws, didx);
+            a.out = map; a.h_n = ws + pl->o_vhn; a.cbuf = pl->train ? ws + pl->o_cv : nullptr;
+
+            // both input projections, then the two recurrences -- in ONE launch while all their workgroups fit on the chip
+            // (csrc/lstm_coop.hip, lstm_rec_coop_pair_kernel), else one after the other
+            if (flags & STAIR_RUN_PROJECTED) {
+                RUN(launch_lstm_zero_tail(a, s));        // (the part of the projection step that writes the plan's own arena)
+            } else {
+                RUN(launch_lstm_project(a, s));
+                RUN(launch_lstm_project(t, s));
+            }
+            const int rc_pair = launch_lstm_rec_coop_pair(a, t, s);
+            if (rc_pair > 0) return rc_pair;
+            if (rc_pair < 0) {
+                RUN(launch_lstm_recur(a, s));
+                RUN(launch_lstm_recur(t, s));
+            }
         }
     }
 

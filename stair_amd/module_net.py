@@ -28,7 +28,7 @@ from ._lib import PlanInfo, StairConfig, StairError, check, lib
 
 VAL_STR, VAL_VEC, VAL_MAP, VAL_ATT, VAL_FRAME, VAL_PAIR = range(6)
 RUN_INDEX_RESIDENT, RUN_VIDEO_BF16, RUN_PROJECTED = 1, 2, 4          # stair_plan_run_flags / stair_plan_backward flags (include/stair_hip.h)
-PLAN_EXT_PROJECTION = 4                                              # stair_plan_build* flag
+PLAN_EXT_PROJECTION, PLAN_VIDEO_ENCODED = 4, 8                       # stair_plan_build* flags
 
 
 class L2Normalize(nn.Module):
@@ -98,6 +98,9 @@ class BatchResult:
         self._prog_off, self._programs = prog_off, programs
         self._video, self._question = video, question
         self.question_frames = None          # [n] frames per question when the batch mixes clip lengths, else None (all info.T)
+        # a pass on cached encodings (run_programs(clips=...)): the cache and its tensor, kept alive for the plan (it holds their
+        # address), and the cache row of every plan clip (map slot v = cache row clip_rows[v]); video is None then
+        self._clips = self._enc = self.clip_rows = None
 
     def status_word(self):
         """The plan's status word (int32 view of one workspace element): 0 = every pass on this workspace since run_programs
@@ -268,7 +271,7 @@ class CapturedPlan:
     def __init__(self, res):
         self.result = res
         model, info = res._model, res.info
-        dev = res._video.device
+        dev = res._question.device
         self._ws = torch.empty((info.workspace_bytes + 3) // 4, dtype=torch.float32, device=dev)
         self._proj = None
         if getattr(res, '_proj', None) is not None:       # the plan keeps its projections outside the workspace: a private buffer too
@@ -289,11 +292,12 @@ class CapturedPlan:
 
     def _enqueue(self, stream):
         res = self.result
-        check(lib.stair_plan_run_flags(res._model._ctx, res._plan, C.c_void_p(res._video.data_ptr()),
+        video = res._video              # None: a plan of cached encodings (the index image uploaded above names their rows)
+        check(lib.stair_plan_run_flags(res._model._ctx, res._plan, C.c_void_p(video.data_ptr() if video is not None else None),
                                        C.c_void_p(res._question.data_ptr()), C.c_void_p(self._ws.data_ptr()),
                                        self._ws.numel() * 4, C.c_void_p(self.logits.data_ptr()),
                                        C.c_void_p(self.pred.data_ptr()),
-                                       RUN_INDEX_RESIDENT | (RUN_VIDEO_BF16 if res._video.dtype == torch.bfloat16 else 0),
+                                       RUN_INDEX_RESIDENT | (RUN_VIDEO_BF16 if video is not None and video.dtype == torch.bfloat16 else 0),
                                        C.c_void_p(stream.cuda_stream)))
 
     def replay(self):
@@ -412,8 +416,39 @@ class VideoNMN(nn.Module):
         return self._ws
 
     # ---------------------------------------------------------------------------------------
+    def _run_cached_args(self, clips, video, video_index, video_len, n, train, dropout):
+        """run_programs(clips=cache): checks, then (cache rows of the plan's clips, clip of every question, the clips' frames, T)."""
+        if video is not None or video_len is not None:
+            raise ValueError('a pass on cached clips takes video=None and no video_len: the cache holds the encodings and their lengths')
+        if train:
+            raise ValueError('training on cached encodings is not supported (the plan has no video encoder to send gradients to)')
+        if dropout is not None and dropout[0] > 0:
+            raise ValueError('dropout is a training-mode operation; a pass on cached clips is inference')
+        if video_index is None:
+            raise ValueError('video_index is required with clips=: the cache row of every question\'s clip')
+        clips.check()
+        rows = np.ascontiguousarray(np.asarray(video_index, dtype=np.int32))
+        if rows.shape != (n,) or n == 0 or rows.min() < 0 or rows.max() >= len(clips):
+            raise ValueError('video_index must hold one row of the cache (0 .. %d) per question' % (len(clips) - 1))
+        if clips.hidden_size != self.config['hidden_size'] or clips.device != next(self.parameters()).device:
+            raise ValueError('the clip cache belongs to another configuration or device')
+        # every distinct row is ONE clip of the plan (order of first use), so that questions about one clip share its nodes
+        uniq, first, index = np.unique(rows, return_index=True, return_inverse=True)
+        order = np.argsort(first, kind='stable')
+        rank = np.empty_like(order)
+        rank[order] = np.arange(len(order))
+        used = np.ascontiguousarray(uniq[order].astype(np.int32))
+        index = np.ascontiguousarray(rank[index].astype(np.int32))
+        lens = np.ascontiguousarray(clips.lengths[used])
+        T = int(lens.max())
+        if self.config['max_video_length'] <= 32:       # Linear(T,T) Temporal nets fix T (modules.py:266-277): the reference crashes on any other clip
+            T = self.config['max_video_length']
+            if bool((lens != T).any()):
+                raise ValueError('Linear-Temporal configurations (max_video_length <= 32) need every clip at max_video_length = %d frames' % T)
+        return used, index, lens, T
+
     def run_programs(self, programs, spans, video, question, q_lens, train=False, video_index=None, dropout=None, video_len=None,
-                     before_run=None, cse=True):
+                     before_run=None, cse=True, clips=None):
         """Batched pass.  programs: list of token lists; spans: list of {pos: (lo, hi)}; video
         [n,T,V] and question [sum(q_lens), E] float32 on the GPU.  Returns a BatchResult.
 
@@ -434,8 +469,17 @@ class VideoNMN(nn.Module):
         dropout is active: the reference draws one mask per question and occurrence, a shared node would be dropped once for all.
         before_run (optional): called with the BatchResult after the plan is built (node table, slots and offsets are
         known) and BEFORE the pass is enqueued -- host work that only needs the plan (the loss driver's index arrays)
-        then overlaps the previous step's GPU work instead of sitting between this step's forward and backward."""
+        then overlaps the previous step's GPU work instead of sitting between this step's forward and backward.
+        clips (optional, a ClipCache of encode_clips): the clips were encoded before.  video is None, video_index [n] (required)
+        names the CACHE ROW of every question's clip, in any order and with repeats; every distinct row becomes one clip of the
+        plan (BatchResult.clip_rows), which runs no video encoder: one launch copies the cached rows into the map arena
+        (STAIR_PLAN_VIDEO_ENCODED).  The plan's T is the longest clip used (max_video_length for the Linear-Temporal
+        configurations, which admit no other length).  Inference only: train=True and dropout raise ValueError, and so does a
+        cache whose encoder weights or matmul mode are no longer the model's (ClipCache.check)."""
         n = len(programs)
+        if clips is not None:
+            return self._run_cached(programs, spans, question, q_lens, before_run, cse, clips,
+                                    *self._run_cached_args(clips, video, video_index, video_len, n, train, dropout))
         if video_index is not None:
             video_index = np.ascontiguousarray(np.asarray(video_index, dtype=np.int32))
             if video_index.shape != (n,):
@@ -514,6 +558,101 @@ class VideoNMN(nn.Module):
             res.logits = ws[info.logits_off: info.logits_off + n * A].view(n, A).clone()    # (n x A floats) that survives the next step
         return res
 
+    def _run_cached(self, programs, spans, question, q_lens, before_run, cse, clips, used, index, lens, T):
+        """The pass of run_programs on a ClipCache: `used` = cache rows of the plan's clips, `index` = clip of every question."""
+        n, dev = len(programs), question.device
+        ops._req(question, 'question')
+        self._bind_weights()
+        stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        proj = None
+        if self.early_projection and question.shape[0] > 0:       # the text projection alone, ahead of the plan (n_videos = 0)
+            nf = int(lib.stair_projection_floats(self._ctx, 0, T, question.shape[0]))
+            proj = self._projection(nf, dev)
+            check(lib.stair_encoders_project(self._ctx, None, 0, 0, T, C.c_void_p(question.data_ptr()), question.shape[0],
+                                             C.c_void_p(proj.data_ptr()), proj.numel(), stream()))
+        compiled = [self._programs.get(p, sp) for p, sp in zip(programs, spans)]
+        prog_off, tokens, lo, hi, q_off = frontend.pack_batch(compiled, q_lens)
+        if question.shape[0] != int(q_off[-1]):
+            raise ValueError('question rows (%d) != sum(q_lens) (%d)' % (question.shape[0], int(q_off[-1])))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        ragged = not bool((lens == T).all())
+        plan = C.c_void_p()
+        check(lib.stair_plan_build_ragged(self._ctx, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), len(used), ip(index),
+                                          ip(lens) if ragged else None, T,
+                                          PLAN_VIDEO_ENCODED | (0 if cse else 2) | (PLAN_EXT_PROJECTION if proj is not None else 0), C.byref(plan)))
+        try:
+            info = PlanInfo()
+            check(lib.stair_plan_get_info(plan, C.byref(info)))
+            enc = clips.enc
+            check(lib.stair_plan_set_encoded_video(plan, C.c_void_p(enc.data_ptr()), clips.rows_cap * clips.hidden_size, clips.rows_cap, ip(used)))
+            ws = self._workspace(info.workspace_bytes, dev)
+            if proj is not None:
+                check(lib.stair_plan_set_projection(self._ctx, plan, C.c_void_p(proj.data_ptr()), proj.numel()))
+            logits = torch.empty(n, self.config['answer_vocab_length'], dtype=torch.float32, device=dev)
+            pred = torch.empty(n, dtype=torch.int32, device=dev)
+        except Exception:
+            lib.stair_plan_destroy(plan)
+            raise
+        res = BatchResult(self, plan, info, ws, logits, pred, prog_off, programs, None, question)      # owns the plan from here on
+        res._proj, res._clips, res._enc, res.clip_rows = proj, clips, enc, used
+        if ragged:
+            res.question_frames = lens[index]
+        if before_run is not None:
+            before_run(res)
+        check(lib.stair_plan_run_flags(self._ctx, plan, None, C.c_void_p(question.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel() * 4,
+                                       C.c_void_p(logits.data_ptr()), C.c_void_p(pred.data_ptr()), RUN_PROJECTED if proj is not None else 0,
+                                       stream()))
+        return res
+
+    def _matmul_mode_now(self):
+        """The matmul mode this model's passes run in: the context's override, else the process-wide setting."""
+        v = C.c_int32(-1)
+        check(lib.stair_ctx_get_option(self._ctx, self.OPTIONS['matmul_mode'], C.byref(v)))
+        mode = v.value if v.value >= 0 else lib.stair_get_matmul_mode()
+        return {v: k for k, v in self.MATMUL_MODES.items()}[mode]
+
+    def _clip_stamp(self):
+        """(matmul mode, state of the video-encoder weights): storage address and torch version counter of each tensor.  Every write
+        torch knows of moves a counter -- load_state_dict, an optimizer step, an in-place update under no_grad -- and Trainer.step
+        reports its native Adam update to the counters (torch.autograd.graph.increment_version); writes through `.data` or a raw
+        pointer do not."""
+        sd = dict(self.named_parameters())
+        return self._matmul_mode_now(), tuple((sd[k].data_ptr(), sd[k]._version) for k in self._weight_names if '.video_encoder.' in k)
+
+    def _encode_chunk(self, video, lens, out):
+        """stair_encode_clips of one padded chunk [n, T, V] (fp32 or bf16, on the device) into out = [n, rows_cap, H] cache rows."""
+        ops._req(video, 'video', torch.bfloat16 if video.dtype == torch.bfloat16 else torch.float32)
+        n, T, V = video.shape
+        if V != self.config['video_size']:
+            raise ValueError('clips must have video_size = %d features per frame' % self.config['video_size'])
+        if video.dtype == torch.bfloat16 and V % 32:
+            raise ValueError('bf16 clip features need video_size % 32 == 0')
+        self._bind_weights()
+        nbytes = int(lib.stair_encode_clips_ws_bytes(self._ctx, n, T, out.shape[1]))
+        if nbytes < 0:
+            raise ValueError('chunk of %d clips x %d frames is too large for one call: lower batch_size' % (n, T))
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=video.device)
+        dlen = None if bool((lens == T).all()) else torch.from_numpy(lens).to(video.device)
+        check(lib.stair_encode_clips(self._ctx, C.c_void_p(video.data_ptr()), 1 if video.dtype == torch.bfloat16 else 0, n, T,
+                                     C.c_void_p(dlen.data_ptr() if dlen is not None else None), C.c_void_p(out.data_ptr()), out.shape[1],
+                                     C.c_void_p(ws.data_ptr()), ws.numel() * 4, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        if int(ws[:1].view(torch.int32).item()) != 0:      # the call's status word (one read-back per chunk of a one-time job)
+            raise StairError('a cooperative LSTM hand-off timed out while encoding clips (its workgroups were not co-resident: another '
+                             'queue on this GPU?); the encodings of this chunk hold NaN.  STAIR_LSTM_COOP=0 selects the one-workgroup kernels')
+
+    def encode_clips(self, clips, ids=None, video_len=None, batch_size=1024):
+        """Run the video encoder once over a library of clips and keep the result: a ClipCache (stair_amd/clip_cache.py) for
+        run_programs(clips=...), forward_batch(clip_cache=...) and the evaluate drivers.  clips: a list of [L_i, V] tensors, or
+        a padded [N, T, V] tensor with video_len; fp32, or bf16 (the stored clip-feature format).  ids: one hashable per clip
+        (forward_batch looks clips up by the questions' 'video_id'); default: the row numbers.  The encodings are those a plan's
+        own encoder pass computes (stair_encode_clips: the same kernels, in this model's matmul mode), [N, max_video_length, H]
+        fp32 with zeros behind each clip's frames.  cache.add(...) appends more clips later."""
+        from .clip_cache import ClipCache
+        dev = next(self.parameters()).device
+        cache = ClipCache(self.config['max_video_length'], self.config['hidden_size'], self._encode_chunk, self._clip_stamp, dev)
+        cache.add(clips, ids=ids, video_len=video_len, batch_size=batch_size)
+        return cache
+
     def logits(self, programs, spans, video, question, q_lens, video_index=None, video_len=None, dropout=None, cse=True):
         """[n, A] logits of a batch (arguments as for run_programs) with a torch autograd graph: when grad mode is on and any
         parameter, `video` or `question` requires grad, the result has a grad_fn whose backward runs the native reverse pass
@@ -529,7 +668,7 @@ class VideoNMN(nn.Module):
         call = (programs, spans, q_lens, video_index, video_len, dropout, cse)
         return PlanLogits.apply(self, call, video, question, *params)
 
-    def forward_batch(self, batch, train=False, share_videos=True, dropout=None, cse=True):
+    def forward_batch(self, batch, train=False, share_videos=True, dropout=None, cse=True, clip_cache=None):
         """batch: list of question dicts in the reference layout (dataset.py:191-233).  Clips may differ in their
         number of frames (they are padded to the longest of the batch and run with their own lengths, see run_programs);
         Linear-Temporal configurations (max_video_length <= 32) need every clip at max_video_length, like the reference.
@@ -537,8 +676,18 @@ class VideoNMN(nn.Module):
 
         Questions about the same clip share one encoder pass.  AGQADataset hands every question of a video the
         same `self.video_feats[video_id]` tensor (dataset.py:183), so clips are told apart by the memory their
-        `video_features` occupy (or by a `video_id` entry, when every dict carries one)."""
+        `video_features` occupy (or by a `video_id` entry, when every dict carries one).
+
+        clip_cache (a ClipCache of encode_clips): the clips are looked up by d['video_id'] and not encoded again (their
+        'video_features' are not read); an id the cache does not hold raises KeyError naming it."""
         dev = next(self.parameters()).device
+        if clip_cache is not None:
+            rows = clip_cache.rows([d['video_id'] for d in batch])
+            qs = [torch.as_tensor(d['question']) for d in batch]
+            question = torch.cat(qs).to(dev, torch.float32).contiguous()
+            return self.run_programs([d['nmn_program_list'] for d in batch], [d['prog_str_to_question_tokens'] for d in batch], None,
+                                     question, [q.shape[0] for q in qs], train=train, video_index=rows, dropout=dropout, cse=cse,
+                                     clips=clip_cache)
         clips, index = [], None
         if share_videos and len(batch) > 1:
             by_id = all('video_id' in d for d in batch)

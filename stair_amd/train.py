@@ -208,6 +208,7 @@ class Trainer:
             nb = (p.numel() + SEG - 1) // SEG
             seg_of_block[offs[i] // SEG: offs[i] // SEG + nb] = i
         self.seg_of_block = seg_of_block.to(dev)
+        self._params = [params[nme] for nme in names]
         self.steps = torch.zeros(len(names), device=dev)     # per-tensor Adam step counts
         self.touched = torch.zeros(len(names), dtype=torch.int32, device=dev)
         self._mask_ring = _PinnedRing(len(names))
@@ -339,6 +340,9 @@ class Trainer:
             check(lib.stair_adam_step_scaled(*adam_args, C.c_void_p(self.grad_norm.data_ptr() + 4), stream))
         else:
             check(lib.stair_adam_step(*adam_args, stream))
+        # the kernel wrote the parameters through their storage: tell torch, as an in-place torch update would (version counters --
+        # what autograd's saved tensors and a ClipCache's staleness check go by)
+        torch.autograd.graph.increment_version(self._params)
         if len(self._status) < 16:
             host = torch.empty(1, dtype=torch.int32).pin_memory()
         else:                                                 # the oldest entry's buffer is reused: look at it first
