@@ -170,6 +170,8 @@ class _ForcedMasks:
     rows of a saved tile / attention row are the clip's.  Collected on the way:
       sites, flips     ReLU sites compared and disagreements.  Plain sites: (z > 0) != mask.  ReLU + Dropout sites: C set where the
                        oracle's z <= 0 (the other side is what dropout does)
+      flip_reach       (no dropout) the largest oracle |pre-activation| at a disagreement, over max(1, max of that tensor's
+                       activation): a forward comparison at tolerance tol leaves room for a flip only where this is below tol
       kept[kind]       [entries whose oracle pre-activation is positive by more than `bound(ref)`, those of them with C set]
       plain_zero[kind] exact zeros at outputs the reference does NOT drop, where the oracle's value is positive beyond the bound
       record[(i, k)]   (C, positive-beyond-bound) of dropout call k of token i ('decoder': the decoder's), for mask statistics"""
@@ -188,7 +190,7 @@ class _ForcedMasks:
     def __init__(self, res, qi, program, p=None):
         self.res, self.qi, self.program, self.p = res, qi, program, p
         self.order = [i for i in range(len(program) - 1, -1, -1) if program[i] in O.ARITY]      # the interpreter's module calls
-        self.queue, self.flips, self.sites = [], 0, 0
+        self.queue, self.flips, self.sites, self.flip_reach = [], 0, 0, 0.0
         self.dqueue, self.kept, self.plain_zero, self.record = [], {}, {}, {}
         self.token = None
 
@@ -266,7 +268,10 @@ class _ForcedMasks:
                 self._count(kind, pos, m)
                 self._pending = (m, pos, kind)
             else:
-                self.flips += int(((zd > 0) != m).sum())
+                differ = (zd > 0) != m
+                self.flips += int(differ.sum())
+                if bool(differ.any()):
+                    self.flip_reach = max(self.flip_reach, float(zd[differ].abs().max()) / max(1.0, float(zd.max())))
                 if plain_site:
                     name = self.program[self.token] if self.token != 'decoder' else 'decoder'
                     self.plain_zero[name] = self.plain_zero.get(name, 0) + int((~m & (zd > self.bound(zd.clamp_min(0)))).sum())

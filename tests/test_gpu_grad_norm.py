@@ -196,10 +196,10 @@ LR, B1, B2, EPS, MAX_NORM = 1e-3, 0.9, 0.999, 1e-8, 1.0
 STEP_NORMS = (10.0, 0.5, 1.0 / 0.9)                                       # coefficients ~0.1, exactly 1, ~0.9
 
 
-def _adam(flat, p, g, m, v, touched, steps, guard, scale, scaled_entry=True):
+def _adam(flat, p, g, m, v, touched, steps, guard, scale, scaled_entry=True, weight_decay=0.0):
     from stair_amd._lib import check, lib
     args = (P(p), P(g), P(m), P(v), P(flat.seg_of_block), P(touched), P(steps), C.c_float(LR), C.c_float(B1), C.c_float(B2),
-            C.c_float(EPS), C.c_float(0.0), flat.n, P(guard))
+            C.c_float(EPS), C.c_float(weight_decay), flat.n, P(guard))
     if scaled_entry:
         check(lib.stair_adam_step_scaled(*args, P(scale), _stream()))
     else:
@@ -219,15 +219,17 @@ def _adam_problem():
     return flat, params, grads
 
 
-def test_scaled_adam_matches_torch_clip_then_adam():
-    """Adam is almost invariant to a constant gradient scale, so the coefficient changes strongly from step to step (~0.1, 1, ~0.9)
-    and the moments are compared too.  exp_avg: the coefficient's 2e-6 enters each term once -> rtol 1e-5 of the terms' magnitude
-    (= of the entry itself after the first step, where there is one term; later steps add terms of either sign, and a relative error
-    per TERM is what the kernel owes); exp_avg_sq: twice, all terms positive -> rtol 2e-5 of the entry; parameters 1e-6 absolute."""
+def _scaled_adam_against_torch(weight_decay):
+    """Three steps of stair_grad_norm + stair_adam_step_scaled on _adam_problem() against clip_grad_norm_ + torch.optim.Adam.
+
+    With weight_decay the gradient Adam sees is coef * g + weight_decay * p, two terms of either sign: what the kernel owes is a
+    relative error per term, so the bounds are taken of the terms' magnitude |coef g| + weight_decay |p| (`mag`), not of their
+    sum -- exp_avg 1e-5 * sum of (1 - b1) mag, exp_avg_sq 2e-5 * sum of (1 - b2) |coef g + weight_decay p| mag (the square's error
+    is twice the entry times the entry's error).  Without decay both reduce to the bounds of the entry itself, which are kept."""
     flat, params, grads = _adam_problem()
     ref_p = [torch.nn.Parameter(x.clone()) for x in params]
     live = [q for i, q in enumerate(ref_p) if i != UNTOUCHED]
-    opt = torch.optim.Adam(live, lr=LR, betas=(B1, B2), eps=EPS)
+    opt = torch.optim.Adam(live, lr=LR, betas=(B1, B2), eps=EPS, weight_decay=weight_decay)
 
     p = flat.fill(params, pad=0.0).to(DEV)
     m, v = torch.zeros(flat.n, device=DEV), torch.zeros(flat.n, device=DEV)
@@ -238,18 +240,20 @@ def test_scaled_adam_matches_torch_clip_then_adam():
     from stair_amd._lib import check, lib
     coefs = []
     term_mag = [torch.zeros(n_) for n_ in ADAM_NUMELS]                     # sum of |terms| that entered exp_avg
+    sq_mag = [torch.zeros(n_) for n_ in ADAM_NUMELS]                       # sum of |entry| x |terms| that entered exp_avg_sq
     for it, gs in enumerate(grads):
         for i, q in enumerate(ref_p):
             q.grad = None if i == UNTOUCHED else gs[i].clone()
         ref_norm = torch.nn.utils.clip_grad_norm_(live, MAX_NORM)
         ref_coef = min(1.0, MAX_NORM / (float(ref_norm) + 1e-6))
+        p_before = [q.detach().clone() for q in ref_p]
         opt.step()
         g = flat.fill(gs).to(DEV)                                         # NaN padding: the norm must not see it
         check(lib.stair_grad_norm(P(g), flat.n, P(flat.first_d), P(flat.numel_d), len(ADAM_NUMELS), C.c_float(MAX_NORM), P(scratch),
                                   P(seg_norm), P(out), P(guard), _stream()))
         steps += touched.float()
         g_before = g.clone()
-        _adam(flat, p, g, m, v, touched, steps, guard, out[1:])
+        _adam(flat, p, g, m, v, touched, steps, guard, out[1:], weight_decay=weight_decay)
         torch.cuda.synchronize()
         coefs.append(float(out[1]))
         assert abs(float(out[0]) - float(ref_norm)) <= 4e-6 * float(ref_norm)      # two fp32 evaluations, 2e-6 each
@@ -264,14 +268,46 @@ def test_scaled_adam_matches_torch_clip_then_adam():
                 assert torch.equal(pc[sl], params[i]) and float(mc[sl].abs().max()) == 0.0 and float(vc[sl].abs().max()) == 0.0
                 continue
             st = opt.state[q]
-            term_mag[i] = B1 * term_mag[i] + (1 - B1) * ref_coef * gs[i].abs()
+            mag = ref_coef * gs[i].abs() + weight_decay * p_before[i].abs()
+            entry = ref_coef * gs[i] + weight_decay * p_before[i]
+            term_mag[i] = B1 * term_mag[i] + (1 - B1) * mag
+            sq_mag[i] = B2 * sq_mag[i] + (1 - B2) * entry.abs() * mag
             assert bool(((mc[sl] - st['exp_avg']).abs() <= 1e-5 * term_mag[i]).all()), (it, i)
-            if it == 0:
-                torch.testing.assert_close(mc[sl], st['exp_avg'], rtol=1e-5, atol=0.0)
-            torch.testing.assert_close(vc[sl], st['exp_avg_sq'], rtol=2e-5, atol=0.0)
+            assert bool(((vc[sl] - st['exp_avg_sq']).abs() <= 2e-5 * sq_mag[i]).all()), (it, i)
+            if weight_decay == 0.0:                                       # one term per step: the bounds are of the entry itself
+                if it == 0:
+                    torch.testing.assert_close(mc[sl], st['exp_avg'], rtol=1e-5, atol=0.0)
+                torch.testing.assert_close(vc[sl], st['exp_avg_sq'], rtol=2e-5, atol=0.0)
             assert float((pc[sl] - q.detach()).abs().max()) <= 1e-6, (it, i)
     print('coefficients', coefs)
     assert 0.09 < coefs[0] < 0.11 and coefs[1] == 1.0 and 0.85 < coefs[2] < 0.95
+    return flat, params, grads, coefs, m.cpu()
+
+
+def test_scaled_adam_matches_torch_clip_then_adam():
+    """Adam is almost invariant to a constant gradient scale, so the coefficient changes strongly from step to step (~0.1, 1, ~0.9)
+    and the moments are compared too.  exp_avg: the coefficient's 2e-6 enters each term once -> rtol 1e-5 of the terms' magnitude
+    (= of the entry itself after the first step, where there is one term; later steps add terms of either sign, and a relative error
+    per TERM is what the kernel owes); exp_avg_sq: twice, all terms positive -> rtol 2e-5 of the entry; parameters 1e-6 absolute."""
+    _scaled_adam_against_torch(0.0)
+
+
+def test_scaled_adam_with_weight_decay_adds_the_decay_to_the_clipped_gradient():
+    """The same problem with weight_decay = 0.01 against torch.optim.Adam(weight_decay=0.01) after clip_grad_norm_: torch clips g,
+    then Adam adds weight_decay * p to the CLIPPED gradient.  The first step (coefficient ~0.1) tells the two orders apart: had the
+    kernel scaled g + weight_decay * p, every exp_avg entry would be off by (1 - b1) (1 - coef) weight_decay |p| -- shown here to
+    exceed the bound in nearly every entry, so the comparison inside _scaled_adam_against_torch cannot pass by luck."""
+    wd = 0.01
+    flat, params, grads, coefs, _ = _scaled_adam_against_torch(wd)
+    n = far = 0
+    for i, (pp, gg) in enumerate(zip(params, grads[0])):
+        if i == UNTOUCHED:
+            continue
+        wrong_order = (1 - B1) * (1 - coefs[0]) * wd * pp.abs()          # |exp_avg error| of "add the decay, then scale" at step 1
+        bound = 1e-5 * (1 - B1) * (coefs[0] * gg.abs() + wd * pp.abs())
+        n, far = n + pp.numel(), far + int((wrong_order > 10 * bound).sum())
+    print('entries where the other order is > 10 bounds away: %d of %d' % (far, n))
+    assert far > 0.99 * n
 
 
 def test_null_scale_is_stair_adam_step_and_a_set_guard_changes_nothing():

@@ -8,8 +8,26 @@ the oracle's gradient is identically zero -- a program that never reads the clip
 weight is exactly 1 -- the kernels' must be exact zeros.  The yardstick is the reference side alone: the oracle in fp32 against
 the oracle in fp64 differs per question by at most 3e-7 (logits), 7e-7 (d_video) and 1.2e-6 (d_question) relative on this corpus.
 
-One oracle pass (forward + autograd, CPU, a few seconds) per geometry, shared by the tests of that geometry (_geometry)."""
+One oracle pass (forward + autograd, CPU, a few seconds) per geometry, shared by the tests of that geometry (_geometry).
+
+Hidden size 512, default bf16x3 products -- the fused tile operators (packed and segmented tiles), the grouped vector-level
+launches, backward tile chains with first-touch stores and fan-in staging rows: the path bench.py times.  There the oracle
+differentiates through the ReLU masks of the HIP pass (_masked_geometry, helpers._ForcedMasks) for EVERY cell, because at this
+width the plain oracle cannot be the yardstick: on the 371 cells (T = 24, V = 128, seed 0) the oracle in fp32 and in fp64 already
+take different sides of one ReLU kink among 21 210 624 sites (cell `AttnVideo X HI <- AttnVideo video HI`, fp64 pre-activation
+8e-5 of the forward bound), which moves that cell's d_video by 6.6e-3 of its maximum and Filter.param.objects.3.bias of the
+batch sum by 3.7e-4, while no cell without a flip differs by more than 2e-4 per question (logits 4.5e-7, d_question 8.5e-7;
+d_video is identically zero in 34 cells at this width).  Forced masks leave the oracle's forward values as they are, so the
+same pass gives the node values, and given equal masks the bounds are the file's: nodes 1e-4, gradients 2e-4 per question.
+The flips are conditions, not measurements:
+  - more than 2e7 sites are compared on the full corpus (every [frames, H] mask of every map-level module on the small ones);
+  - fewer than 1e-4 of them disagree (the share test_full_size_gradients_are_strict_given_the_same_relu_masks allows);
+  - at every disagreement the oracle's |pre-activation| is below the forward bound of that tensor, 1e-4 * max(1, max|ref|):
+    an activation that passed the forward check cannot differ in sign anywhere else, so a gradient cannot be made to fit by a
+    mask the kernels had no right to.
+Shared clips at this width are checked GPU against GPU (sharing, cse=False, and the expanded batch the oracle has judged)."""
 import functools
+import time
 
 import pytest
 import torch
@@ -37,6 +55,10 @@ def _tiny(L):
     return dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, answer_vocab_length=16, max_video_length=L, object_types=10)
 
 
+def _wide(L):
+    return dict(_tiny(L), hidden_size=512)
+
+
 # name -> (config, T, cells, clips shared (cell k on clip k % 3), frames per question or None)
 GEOMETRIES = {
     'conv': lambda: (_tiny(40), 24, PC.cells(), False, None),                       # Conv1d Temporal nets, one 64-row tile per clip
@@ -44,10 +66,17 @@ GEOMETRIES = {
     'linear8': lambda: (_tiny(8), 8, PC.map_frame_att_cells(), False, None),         # Linear Temporal nets, 8 clips per packed tile
     'long70': lambda: (_tiny(100), 70, PC.map_frame_att_cells(), False, None),       # two segments, the second of 6 rows
     'ragged': lambda: (_tiny(40), 24, PC.map_frame_att_cells(), False, (3, 17, 24)),
-    # the reference's hidden size (fused tile operators, grouped vector-level launches: the bit-reproducible step); no oracle
-    'h512': lambda: (dict(_tiny(40), hidden_size=512), 24, PC.cells(), False, None),
-    'h512_shared': lambda: (dict(_tiny(40), hidden_size=512), 24, PC.cells(), True, None),
+    # the reference's hidden size (fused tile operators, grouped vector-level launches: the bit-reproducible step).  Own clips: the
+    # oracle under the HIP pass's masks (_masked_geometry); shared clips: GPU against GPU
+    'h512': lambda: (_wide(40), 24, PC.cells(), False, None),
+    'h512_shared': lambda: (_wide(40), 24, PC.cells(), True, None),
+    'linear8_h512': lambda: (_wide(8), 8, PC.map_frame_att_cells(), False, None),    # 8 clips per packed tile
+    'long70_h512': lambda: (_wide(100), 70, PC.map_frame_att_cells(), False, None),  # two segments, the second of 6 rows
+    'ragged_h512': lambda: (_wide(40), 24, PC.map_frame_att_cells(), False, (3, 17, 24)),
 }
+MASKED = ['h512', 'linear8_h512', 'long70_h512', 'ragged_h512']
+ZERO_D_VIDEO_CELLS_H512 = 34   # as ZERO_D_VIDEO_CELLS, geometry 'h512'
+MAP_LEVEL = ('Filter', 'FilterFrame', 'HasItem', 'Localize', 'Superlative', 'Temporal')     # each saves a [frames, H] ReLU mask
 
 
 class Geometry:
@@ -70,7 +99,7 @@ def _geometry(name):
     g.clips = [leaf(g.qs[c]['video_features']) for c in range(3)] if g.shared else None
     g.index = [k % 3 for k in range(n)] if g.shared else None
     g.logits, g.steps, g.d_video, g.d_question = [], [], [], []
-    if name.startswith('h512'):
+    if 'h512' in name:           # the oracle of these needs a HIP pass's masks: _masked_geometry
         return g
     for k, q in enumerate(g.qs):
         v = g.clips[k % 3] if g.shared else leaf(q['video_features'][:g.frames[k]] if g.frames else q['video_features'])
@@ -120,10 +149,11 @@ def f32():
 
 
 # ---- the HIP side --------------------------------------------------------------------------------------------------------------
-def _inputs(g):
-    """(programs, spans, video [n or 3, T, V] zero-padded behind a short clip's frames, question rows, q_lens, video_len)"""
+def _inputs(g, expand=False):
+    """(programs, spans, video [n or 3, T, V] zero-padded behind a short clip's frames, question rows, q_lens, video_len);
+    expand: every question of a shared geometry gets a copy of its clip"""
     if g.shared:
-        video = torch.stack([c.detach() for c in g.clips])
+        video = torch.stack([g.clips[c].detach() for c in (g.index if expand else range(3))])
     else:
         video = torch.stack([torch.as_tensor(q['video_features']) for q in g.qs])
         if g.frames:
@@ -133,16 +163,17 @@ def _inputs(g):
             question.to(DEV).contiguous(), [q['question'].shape[0] for q in g.qs], g.frames)
 
 
-def _run(model, g, train=False, cse=True):
-    progs, spans, video, question, q_lens, frames = _inputs(g)
-    return model.run_programs(progs, spans, video, question, q_lens, train=train, video_index=g.index, video_len=frames, cse=cse)
+def _run(model, g, train=False, cse=True, expand=False):
+    progs, spans, video, question, q_lens, frames = _inputs(g, expand)
+    return model.run_programs(progs, spans, video, question, q_lens, train=train, video_index=None if expand else g.index,
+                              video_len=frames, cse=cse)
 
 
-def _train_pass(model, g, cse=True):
+def _train_pass(model, g, cse=True, expand=False):
     """One training pass of the batch with the custom loss: (result, d_video, d_question, {parameter: gradient}) on the host"""
     for p in model.parameters():
         p.grad = torch.zeros_like(p)
-    res = _run(model, g, train=True, cse=cse)
+    res = _run(model, g, train=True, cse=cse, expand=expand)
     lg = res.logits.clone().requires_grad_(True)
     _custom(lg, g.R.to(DEV)).backward()
     dv = torch.full(res._video.shape, float('nan'), dtype=torch.float32, device=DEV)      # both are OVERWRITTEN by the pass
@@ -352,3 +383,187 @@ def test_cell_batch_training_pass_is_bit_reproducible(name):
     assert not differ, differ
     assert torch.equal(runs[0][0], runs[1][0]), 'd_video'
     assert torch.equal(runs[0][1], runs[1][1]), 'd_question'
+
+
+# ---- (f) hidden size 512, default product mode: the oracle under the HIP pass's masks ------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _masked_geometry(name):
+    """A geometry of MASKED with the oracle on it, every question differentiated through the ReLU masks of the HIP pass: read from
+    a fresh forward run of the training plan before any backward pass touches its workspace, as _forced_oracle does.  Forward
+    values are the oracle's own.  Also g.w[n].grad, the parameter gradients summed over the batch; g.hip_logits, the logits of the
+    run the masks were read from (the forward pass at this width is reproducible bit for bit, so a test's own training pass must
+    give the same ones -- asserted there -- and hence the same masks); g.sites, g.flips; g.flip_reach, (the largest oracle
+    |pre-activation| at a flip / max(1, max of that activation), the cell) ; g.seconds, the oracle's wall time.
+    One intra-op thread: a cell takes 55 ms that way and 123 ms with 16 threads.  Computed once; nobody writes to it."""
+    from stair_amd import ops
+    assert ops.get_matmul_mode() == 'bf16x3'
+    g = _geometry.__wrapped__(name)         # a Geometry of its own: _geometry(name) stays without an oracle
+    assert not g.shared
+    model = _model(g.config, SEED)
+    res = _run(model, g, train=True)
+    g.hip_logits = res.logits.cpu().clone()
+    g.sites, g.flips, g.flip_reach = 0, 0, (0.0, '')
+    leaf = lambda a: torch.as_tensor(a).float().clone().requires_grad_(True)
+    threads, t0 = torch.get_num_threads(), time.perf_counter()
+    torch.set_num_threads(1)
+    try:
+        for k, (q, c) in enumerate(zip(g.qs, g.cells)):
+            v, qq = leaf(q['video_features'][:g.frames[k]] if g.frames else q['video_features']), leaf(q['question'])
+            fm = _ForcedMasks(res, k, q['nmn_program_list'])
+            r = fm.forward(g.w, g.config, dict(q, video_features=v, question=qq), return_res_by_step=False,
+                           return_result_of_each_step=True, explicit_lstm=True)
+            _custom(r['logits'].unsqueeze(0), g.R[k:k + 1]).backward()
+            g.logits.append(r['logits'].detach())
+            g.steps.append([s.detach() if isinstance(s, torch.Tensor) else None for _, s in r['result_of_each_step']])
+            g.d_video.append(v.grad if v.grad is not None else torch.zeros_like(v))
+            g.d_question.append(qq.grad)
+            g.sites, g.flips, g.flip_reach = g.sites + fm.sites, g.flips + fm.flips, max(g.flip_reach, (fm.flip_reach, c.name))
+    finally:
+        torch.set_num_threads(threads)
+    g.seconds = time.perf_counter() - t0
+    g.n_zero = sum(float(d.abs().max()) == 0.0 for d in g.d_video)
+    print('%s: oracle under the HIP masks: %d cells in %.1f s, %d ReLU sites, %d flips, largest |pre-activation| / bound at a flip '
+          '%.3g (%s), %d cells with an all-zero d_video' % (name, len(g.cells), g.seconds, g.sites, g.flips, g.flip_reach[0] / 1e-4,
+                                                          g.flip_reach[1], g.n_zero))
+    return g
+
+
+@pytest.fixture(scope='module', params=MASKED)
+def wide(request):
+    return _masked_geometry(request.param)
+
+
+def _fused_train_pass(g):
+    """a training pass of a fresh model on the fused path (asserted), whose forward values are those the masks were read from"""
+    from stair_amd import ops
+    assert ops.get_matmul_mode() == 'bf16x3'
+    model = _model(g.config, SEED)
+    with ops.kernel_accounting() as acct:
+        res, dv, dq, grads = _train_pass(model, g)
+    assert 'tile_mlp' in acct.table and 'vec_group' in acct.table, sorted(acct.table)
+    assert res.info.n_questions == len(g.cells) == (371 if g.name == 'h512' else 74)
+    assert torch.equal(res.logits.cpu(), g.hip_logits), 'this pass is not the pass the masks were read from'
+    return model, res, dv, dq, grads
+
+
+def test_fused_path_every_cell_node_matches_oracle(wide):
+    g = wide
+    model, res, dv, dq, grads = _fused_train_pass(g)
+    _check_forward(res, g, 1e-4)
+
+
+def test_fused_path_relu_flips_stay_inside_the_forward_bound(wide):
+    """the conditions under which the gradient tests below mean anything (module docstring)"""
+    g = wide
+    frames = lambda k: g.frames[k] if g.frames else g.T
+    floor = 2e7 if g.name == 'h512' else sum(frames(k) * g.config['hidden_size'] * sum(t in MAP_LEVEL for t in c.program)
+                                            for k, c in enumerate(g.cells))
+    print('%s: %d ReLU sites (at least %d wanted), %d flips, largest |pre-activation| / bound at a flip %.3g (%s)'
+          % (g.name, g.sites, floor, g.flips, g.flip_reach[0] / 1e-4, g.flip_reach[1]))
+    assert g.sites > floor > 0
+    assert g.flips < 1e-4 * g.sites
+    assert g.flip_reach[0] < 1e-4, g.flip_reach
+
+
+def test_fused_path_every_cell_input_gradients_match_oracle(wide):
+    g = wide
+    assert g.name not in FORCED_MASKS           # every cell of these is under the masks already
+    model, res, dv, dq, grads = _fused_train_pass(g)
+    n_zero = _check_input_gradients(model, g, dv, dq)
+    assert n_zero == g.n_zero
+    if g.name == 'h512':
+        assert n_zero == ZERO_D_VIDEO_CELLS_H512
+
+
+def _check_param_gradients_by_family(g, grads):
+    """_check_param_gradients with the rule of test_full_size_gradients_are_strict_given_the_same_relu_masks for the tensors of
+    fewer than 64 elements: 2e-4 of the largest gradient entry of their FAMILY (the layers of one net: `a.b.N.weight` -> `a.b`).
+    Those are the filters and scalar biases of Temporal's relate nets, sums over frames and cells with heavy cancellation, whose
+    terms carry the bf16x3 products' 4e-6 each.  One of them needs the rule: on the 371 cells the 1-element
+    Temporal.relate.after.2.bias (-2.64e-3) is 1.08e-6 off, 2.04 x the bound of its own value; 1.33e-6 (2.53 x) with the tile
+    operators switched off, 8.2e-8 (0.156 x) in exact-fp32 mode under that mode's masks -- product rounding, not a lost term;
+    every other tensor is below 0.23 x its own bound.  Every tensor of 64 elements and more keeps _check_params' bound of its own
+    largest entry (floor 1e-3, as there); a weight no cell reaches holds exact zeros."""
+    family_max = {}
+    for n in g.names:
+        if g.w[n].grad is not None:
+            fam = n.rsplit('.', 2)[0]
+            family_max[fam] = max(family_max.get(fam, 0.0), float(g.w[n].grad.abs().max()))
+    worst, worst_small, fails = (0.0, ''), (0.0, 0.0, ''), []
+    assert set(grads) >= set(g.names)
+    for n in g.names:
+        ref, got = g.w[n].grad, grads[n].float().cpu()
+        if ref is None:
+            assert float(got.abs().max()) == 0.0, (n, 'no cell reaches it: exact zeros')
+            continue
+        small = ref.numel() < 64
+        err = float((got - ref).abs().max())
+        own = REL * max(float(ref.abs().max()), 1e-3)
+        bound = REL * max(family_max[n.rsplit('.', 2)[0]], 1e-3) if small else own
+        if small:
+            worst_small = max(worst_small, (err / bound, err / own, n))
+        else:
+            worst = max(worst, (err / bound, n))
+        if not err < bound:
+            fails.append((n, err, bound))
+    print('%s: parameter gradients: worst error / bound %.3g at %s; tensors of < 64 elements, by family: %.3g (%.3g of its own '
+          'bound) at %s' % ((g.name,) + worst + worst_small))
+    assert not fails, fails
+
+
+def test_fused_path_parameter_gradients_match_oracle(wide):
+    g = wide
+    model, res, dv, dq, grads = _fused_train_pass(g)
+    _check_param_gradients_by_family(g, grads)
+
+
+# ---- (g) shared clips at hidden size 512: sharing, no sharing and the expanded batch, GPU against GPU ---------------------------------
+def test_fused_path_shared_clips_equal_the_expanded_batch():
+    """Three clips, cell k on clip k % 3: the batch with common subexpressions shared, with cse=False, and expanded (every question
+    owns a copy of its clip: the code test_fused_path_* hold to the oracle).  Forward values are row-independent on this path: every
+    node and the logits are bit-equal, so the ReLU masks are equal and what is left between the gradients is the order of sums:
+    d_question per question, d_video summed per clip and every parameter gradient within 2e-4 of the tensor's largest entry."""
+    from stair_amd import ops
+    assert ops.get_matmul_mode() == 'bf16x3'
+    g = _geometry('h512_shared')
+    runs = {}
+    for how in ('cse', 'no_cse', 'expanded'):
+        model = _model(g.config, SEED)
+        with ops.kernel_accounting() as acct:
+            res, dv, dq, grads = _train_pass(model, g, cse=how != 'no_cse', expand=how == 'expanded')
+        assert 'tile_mlp' in acct.table and 'vec_group' in acct.table, sorted(acct.table)
+        assert not torch.isnan(dv).any() and not torch.isnan(dq).any()
+        if how == 'expanded':
+            assert res._video.shape[0] == len(g.cells)
+            dv = torch.zeros(3, *dv.shape[1:]).index_add_(0, torch.tensor(g.index), dv)
+        else:
+            assert (res.info.n_aliased > 0) == (how == 'cse') and res._video.shape[0] == 3
+        if how == 'cse':
+            assert res.info.n_map_stage > 0 and res.info.n_vec_stage > 0 and res.info.n_att_stage > 0
+        nodes = [[res.node(q, i).detach().cpu().clone() for i, t in enumerate(c.program) if t in O.ARITY] for q, c in enumerate(g.cells)]
+        runs[how] = (res.logits.cpu().clone(), nodes, dv, dq, grads)
+        del res
+    ref = runs['expanded']
+    assert sum(len(x) for x in ref[1]) == sum(t in O.ARITY for c in g.cells for t in c.program)
+    assert float(ref[2].abs().max()) > 0
+    for how in ('cse', 'no_cse'):
+        got = runs[how]
+        assert torch.equal(got[0], ref[0]), (how, 'logits')
+        for q, (a, b) in enumerate(zip(got[1], ref[1])):
+            for k, (x, y) in enumerate(zip(a, b)):
+                assert torch.equal(x, y), (how, g.cells[q], 'module node %d' % k)
+        worst = (0.0, '')
+        for q in range(len(g.cells)):
+            err, bound = _err(got[3][_rows(g, q)], ref[3][_rows(g, q)])
+            worst = max(worst, (err / bound if bound else float(err > 0), '%s d_question' % g.cells[q]))
+            assert err < bound or err == bound == 0.0, (how, g.cells[q], 'd_question', err, bound)
+        for c in range(3):
+            err, bound = _err(got[2][c], ref[2][c])
+            worst = max(worst, (err / bound, 'd_video of clip %d' % c))
+            assert err < bound, (how, 'd_video of clip %d' % c, err, bound)
+        for n, r in ref[4].items():
+            err, bound = _err(got[4][n].cpu(), r.cpu())
+            if bound:
+                worst = max(worst, (err / bound, n))
+            assert err < bound or err == bound == 0.0, (how, n, err, bound)
+        print('h512_shared, %s against the expanded batch: worst error / bound %.3g at %s' % ((how,) + worst))
