@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define STAIR_ABI_VERSION 6
+#define STAIR_ABI_VERSION 7
 
 typedef struct stair_ctx stair_ctx;
 typedef struct stair_plan stair_plan;
@@ -354,15 +354,9 @@ typedef struct stair_tile_mlp_args {
     const float *act_mask[3]; float act_scale;
     const float *in_mask; int64_t in_mask_gstride; const int32_t *in_mask_idx; float in_scale; int32_t x_broadcast;
     float *save_in;
-    /* vector-level modules (modules.py:15-37 Compare / Equals, :59-72 Xor, :102-120 ToAction, :141-159 Exists): the "tile" is 64
-     * INSTANCES, one [H] row each, and the first layer runs on a concatenation that is never materialised for the GEMM:
-     *   vec_pack         0 off; 1: [a, b]; 2: [|a - b|, a, b]; 3: [a, b, a * b] with a = pk_a + pk_a_idx[i] * H, b = pk_b + pk_b_idx[i] * H
-     *                    (i = 0 .. vec_cnt - 1; cnt must be (vec_cnt + 63) / 64).  W[0] holds 2 or 3 consecutive [H, H] plane
-     *                    images, one per H-wide column block of the [H, 2H | 3H] weight (stair_pack_wfrag_ld); the layer
-     *                    accumulates over them.  X, x_gstride, x_idx, T are ignored.
-     *   cat_save         optional [vec_cnt, 2H | 3H]: the concatenated rows (what the weight-gradient product needs)
-     *   save[l]          [vec_cnt, H]
-     *   tail STORE_ROWS  row i of the last layer -> out + out_row_idx[i] * out_gstride */
+    /* RETIRED with ABI 7: the vector-level form (Compare / Equals / Xor / ToAction / Exists as tiles of 64 instances; stair_vec_group runs
+     * these modules).  The fields keep their place in the struct; a launch with vec_pack != 0 is refused, and so is tail
+     * STAIR_TILE_STORE_ROWS.  Leave them zero. */
     int32_t vec_pack; const float *pk_a, *pk_b; const int32_t *pk_a_idx, *pk_b_idx; int32_t vec_cnt;
     float *cat_save; const int32_t *out_row_idx;
     /* Temporal's backward as ONE chain per tile (autograd of modules.py:310-327, y = LayerNorm(ReLU(Lin(r_t feat_t)))); ABI 5:
@@ -471,9 +465,6 @@ int stair_tile_work_items(int64_t *items, int32_t reset);
 /* W [N, K] fp32 row-major -> planes: [N/32][K/16][hi, lo][64 lanes][8 bf16] (2 * N * K * 2 bytes, 16-byte aligned);
  * N % 32 == 0, K % 16 == 0.  transpose != 0: W is stored [K, N] and the planes are those of W^T (backward chains). */
 int stair_pack_wfrag(const float *W, void *planes, int32_t N, int32_t K, int32_t transpose, stair_stream stream);
-/* The same for a [N, K] column block of a wider row-major matrix (row stride ld floats): the H-wide blocks of a vector-level
- * module's [H, 2H | 3H] first-layer weight. */
-int stair_pack_wfrag_ld(const float *W, int64_t ld, void *planes, int32_t N, int32_t K, stair_stream stream);
 /* Measurement aid: while on, every tile-operator launch is bracketed by HIP events on its stream; stair_tile_timing_read waits for
  * them and returns the summed device time (ms) and the number of launches since stair_tile_timing(1) (bench.py's
  * roofline_tile_operator: the kernel's live time without a profiler).  Not thread-safe; off by default. */

@@ -16,7 +16,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('STAIR_LIB_PATH') or os.path.join(_HERE, 'lib', 'libstair_hip.so')   # override: kernel experiments
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
 
@@ -153,7 +153,6 @@ SIGNATURES = [
     ('stair_tile_work_items', C.c_int, [C.POINTER(C.c_int64), C.c_int32]),
     ('stair_tile_mlp_fwd', C.c_int, [C.POINTER(TileMlpArgs), C.c_void_p]),
     ('stair_pack_wfrag', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    ('stair_pack_wfrag_ld', C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     ('stair_tile_timing', C.c_int, [C.c_int32]),
     ('stair_tile_timing_read', C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     ('stair_gemm_f32', C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),

@@ -438,11 +438,11 @@ enum : uint8_t { KS = 1 << STAIR_VAL_STR, KV = 1 << STAIR_VAL_VEC, KM = 1 << STA
 enum { OUT_AS_FIRST = -1 };      // the output has the kind of operand 0, which operand 1 must share (And / XorFrame)
 // gradient arenas (build_grad_fanin); FAN_SUB: that of the bucket's `sub` kind (And / XorFrame)
 enum { FAN_NONE = -1, FAN_VEC = 0, FAN_MAP = 1, FAN_ATT = 2, FAN_SUB = 3 };
-// The one concatenation of two operand rows a vector-level module feeds its first layer, under its three spellings: the pack
-// kernel's, the grouped launch's and the tile operator's.
+// The one concatenation of two operand rows a vector-level module feeds its first layer, under its two spellings: the pack
+// kernel's and the grouped launch's.
 enum VecIn { IN_CAT2, IN_XOR, IN_EXISTS };       // cat[a, b], cat[|a - b|, a, b], cat[a, b, a * b]
-struct VecInForm { PackMode pack; int vg, vec_pack; };
-const VecInForm kVecIn[] = {{PACK_CAT2, VG_IN_CAT2, 1}, {PACK_XOR, VG_IN_XOR, 2}, {PACK_EXISTS, VG_IN_EXISTS, 3}};
+struct VecInForm { PackMode pack; int vg; };
+const VecInForm kVecIn[] = {{PACK_CAT2, VG_IN_CAT2}, {PACK_XOR, VG_IN_XOR}, {PACK_EXISTS, VG_IN_EXISTS}};
 // The regions a bucket may own, in the order layout_workspace takes them: `per_row`: one piece per row of the secondary count
 // (Bucket::nrows) instead of per instance; a piece is (T if t) x (H if h) floats.
 struct SaveRegion { const char *name; int64_t Bucket::*off; bool per_row, t, h; };
@@ -1759,8 +1759,7 @@ VgProblem vg_fwd(int rows, const float *a, const int32_t *ia, int64_t lda, const
     p.kred = 512; p.W = Wm; p.ldw = ldw; p.bias = bias; p.N = N; p.act = act; p.out = out; p.io = io; p.ldo = ldo;
     return p;
 }
-// the context option STAIR_OPT_VEC_GROUP = 0 keeps the per-module pack -> GEMM -> reduction sequences (and the tile form for large
-// buckets)
+// the context option STAIR_OPT_VEC_GROUP = 0 keeps the per-module pack -> GEMM -> reduction sequences, at every bucket size
 bool vec_group_on() { return policy_or(STAIR_OPT_VEC_GROUP, 1) != 0; }
 
 // ---- the argument blocks of encoder e (0: video, 1: text), filled in one place for stair_encoders_project, the forward run and the
@@ -2088,15 +2087,10 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
             if (need[i]) { src[cnt_w] = WIX.wf[i]->lin(W).w; dst[cnt_w] = const_cast<void *>(WF(i)); ++cnt_w; }
         if (cnt_w) RUN(launch_pack_wfrag_many(src, dst, cnt_w, H, H, s));
     }
-    // vector-level modules on the tile operator (64 instances per tile; STAIR_TILE_VEC=0: the pack -> GEMM -> reduction sequences)
-    // Policy (measured, ms per batch, fused / unfused): 2048 questions, buckets of 205..1044 instances: training 17.91 / 17.96,
-    // inference 5.61 / 5.73; 128 questions, 13..66 instances: training 5.06 / 5.01 -- one workgroup carries a tile's whole
-    // [64 x 1536 x 512] first layer (3 x 17 us) where the split-K GEMM spreads it over 64 workgroups (13 us), so the tile form
-    // pays only when a bucket fills several tiles.  STAIR_TILE_VEC = minimum instances per bucket (0: never).
-    const int vec_min = env_int("STAIR_TILE_VEC", 128);      // read per pass: tests switch it
     // The row-wise Linear layers of a level -- vector-level modules, Filter's dense layer, Localize's keyword rows, the decoder -- as
     // problems of ONE launch before the level's tile operators (first layers, keyword rows) and ONE after them (second layers, the
-    // dense layers on the pooled rows): csrc/vec_group.hip.  Takes precedence over the tile form of the vector-level modules.
+    // dense layers on the pooled rows): csrc/vec_group.hip.  Otherwise (STAIR_OPT_VEC_GROUP = 0, another hidden size or matmul
+    // mode) they run the pack -> GEMM -> reduction sequences.
     const bool grouped = fused && vec_group_usable(H) && vec_group_on();
     std::vector<VgProblem> vg1, vg2;
     // [512 x 512] blocks of a row-wise weight as planes: slot + (output block) * nseg + (input segment); blocks of a [N, nseg * 512] matrix
@@ -2117,33 +2111,6 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
                         }
         if (cnt_w) RUN(launch_pack_wfrag_many(src, dst, cnt_w, H, H, s, false, ld));
     }
-    auto fused_vec_for = [&](const Bucket &b) { return !grouped && fused && dp <= 0.0f && vec_min > 0 && b.cnt >= vec_min; };
-    const bool fused_vec = !grouped && fused && dp <= 0.0f && vec_min > 0;
-    if (fused_vec) {
-        bool has[32] = {};
-        for (const Bucket &b : pl->buckets) if (fused_vec_for(b) && b.op >= 0 && b.op < 32) has[b.op] = true;
-        const float *src[16];
-        void *dst[16];
-        int ld[16], cnt_w = 0;
-        for (int slot = WF_COUNT; slot < WV_FD; ++slot)          // (the slots below WV_FD: the vector-level modules' own layers)
-            if (const WeightRow *v = WIX.wv[slot])
-                if (has[v->op])
-                    for (int j = 0; j < v->nseg; ++j) { src[cnt_w] = v->lin(W).w + (int64_t)j * H; dst[cnt_w] = const_cast<void *>(WF(slot + j)); ld[cnt_w] = v->nseg * H; ++cnt_w; }
-        if (cnt_w) RUN(launch_pack_wfrag_many(src, dst, cnt_w, H, H, s, false, ld));
-    }
-    // a vector-level module as queued tile work: first layer over the never-materialised concatenation of the operand rows
-    // a = vec[ia[i]], b = vec[ib[i]], optional second layer, row i -> vec[io[i]]
-    auto vec_module = [&](const Bucket &b, int pack, const int32_t *ia, const int32_t *ib, const int32_t *io, int slot0, const Lin &l0,
-                          int slot3, const Lin *l3, float *cat_sv, float *hid_sv) {
-        stair_tile_mlp_args a = {};
-        a.vec_pack = pack; a.vec_cnt = b.cnt; a.cnt = (b.cnt + 63) / 64; a.T = 64; a.H = H; a.ln_eps = 1e-5f;
-        a.pk_a = vec; a.pk_a_idx = ia; a.pk_b = vec; a.pk_b_idx = ib;
-        a.W[0] = WF(slot0); a.bias[0] = l0.b; a.act[0] = 1; a.n_layers = 1;
-        if (l3) { a.W[1] = WF(slot3); a.bias[1] = l3->b; a.act[1] = 1; a.n_layers = 2; }
-        if (pl->train) { a.cat_save = cat_sv; if (l3) a.save[0] = hid_sv; }
-        a.tail = STAIR_TILE_STORE_ROWS; a.out = vec; a.out_gstride = H; a.out_row_idx = io;
-        return a;
-    };
     // len_: the clips' frames (ragged plans), passed by the bucket's TileLen rule
     auto tile_args = [&](const int32_t *x_idx, int cnt_, const int32_t *len_, TileLen rule = LEN_OF_LONG_CLIPS) {
         stair_tile_mlp_args a = {};
@@ -2221,10 +2188,6 @@ extern "C" int stair_plan_run_flags(stair_ctx *ctx, stair_plan *pl, const float 
                         vg2.back().wplanes = WF(r3->wv);
                         if (m.vec_drops > 1) vg_drop(vg2.back(), 1);
                     }
-                    break;
-                }
-                if (fused_vec_for(b)) {
-                    if (phase == 1) tile_queue.push_back(vec_module(b, in.vec_pack, Ia, Ib, I2, r0.wv, l0, r3 ? r3->wv : 0, l3, cat, l3 ? hid : nullptr));
                     break;
                 }
                 RUN(launch_pack(in.pack, vec, Ia, vec, Ib, cat, c, H, s));

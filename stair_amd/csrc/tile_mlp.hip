@@ -60,6 +60,9 @@ __device__ __forceinline__ int tm_swz(int R) {
     return ((q0 ^ q1) << 1) | q1;
 }
 
+// The kernel forms (the KIND of tile_mlp_kernel); a launch carries buckets of one form, and a level's launches go out in this order
+enum TileKind { KIND_FWD = 0, KIND_TEMPORAL_BWD = 1, KIND_CHAIN = 2, KIND_COUNT = 3 };
+
 constexpr int TM_MAXB = 8;           // module buckets one launch can carry (the argument block stays under the 4 KB kernarg limit)
 // One bucket's arguments as the kernel sees them: stair_tile_mlp_args with the fields that only ONE kernel form reads overlaid
 // (a launch carries buckets of one form), so that eight buckets still fit the 4 KB argument block.  Same names as the public struct.
@@ -82,14 +85,11 @@ struct TmArg {
     float *save_in;
     int32_t acc_exclusive;
     union {
-        struct {            // KIND 1: vector-level tiles
-            int32_t vec_pack, vec_cnt; const float *pk_a, *pk_b; const int32_t *pk_a_idx, *pk_b_idx; float *cat_save; const int32_t *out_row_idx;
-        };
-        struct {            // KIND 2: Temporal's backward chain
+        struct {            // KIND_TEMPORAL_BWD: Temporal's backward chain
             float *dgamma, *dbeta; const float *adj_feat; int64_t adj_feat_gstride; const int32_t *adj_feat_idx;
             const float *adj_rs; const int32_t *adj_rs_idx; float *adj_drs;
         };
-        struct {            // KIND 0: relu' bit masks of the map-level operators and their chains
+        struct {            // KIND_FWD, KIND_CHAIN: relu' bit masks of the map-level operators and their chains
             unsigned long long *save_bits[3]; const unsigned long long *act_bits[3]; const unsigned long long *in_bits;
             uint16_t drop_site[3];       // forward launches: 1 + dropout site behind layer l's activation (0: none)
         };
@@ -102,7 +102,7 @@ struct TileGeom {
     bool walk;                   // the bucket hands out INSTANCES: the SUM_ROWS walk of a split launch (one workgroup, all segments)
     int items; int64_t tiles;    // work items of the bucket, and its tiles (they differ only under walk)
 };
-static TmArg tm_arg(const stair_tile_mlp_args &a, int kind, const TileGeom &g) {
+static TmArg tm_arg(const stair_tile_mlp_args &a, TileKind kind, const TileGeom &g) {
     TmArg t = {};
     t.pack = g.S > 1 ? g.S : g.P;        // (a launch packs or splits, never both: at most one of them is above 1)
     t.X = a.X; t.x_gstride = a.x_gstride; t.x_idx = a.x_idx; t.row_scale = a.row_scale; t.rs_idx = a.rs_idx;
@@ -114,10 +114,7 @@ static TmArg tm_arg(const stair_tile_mlp_args &a, int kind, const TileGeom &g) {
     t.cnt = a.cnt; t.T = a.T; t.H = a.H; t.act_scale = a.act_scale;
     t.in_mask = a.in_mask; t.in_mask_gstride = a.in_mask_gstride; t.in_mask_idx = a.in_mask_idx; t.in_scale = a.in_scale;
     t.x_broadcast = a.x_broadcast; t.save_in = a.save_in; t.acc_exclusive = a.acc_exclusive;
-    if (kind == 1) {
-        t.vec_pack = a.vec_pack; t.vec_cnt = a.vec_cnt; t.pk_a = a.pk_a; t.pk_b = a.pk_b; t.pk_a_idx = a.pk_a_idx; t.pk_b_idx = a.pk_b_idx;
-        t.cat_save = a.cat_save; t.out_row_idx = a.out_row_idx;
-    } else if (kind == 2) {
+    if (kind == KIND_TEMPORAL_BWD) {
         t.dgamma = a.dgamma; t.dbeta = a.dbeta; t.adj_feat = a.adj_feat; t.adj_feat_gstride = a.adj_feat_gstride; t.adj_feat_idx = a.adj_feat_idx;
         t.adj_rs = a.adj_rs; t.adj_rs_idx = a.adj_rs_idx; t.adj_drs = a.adj_drs;
     } else {
@@ -131,7 +128,7 @@ struct TmParams {
     TmArg a[TM_MAXB];                // the buckets of one program level: independent of each other, so their tiles share one launch
     int first[TM_MAXB + 1];          // work item w belongs to bucket b with first[b] <= w < first[b + 1]; its tile is w - first[b]
     int nb;
-    long long *fx_g, *fx_b;          // KIND 2: fixed-point shadows of d gamma / d beta (NULL: float atomics into a[0].dgamma / dbeta)
+    long long *fx_g, *fx_b;          // KIND_TEMPORAL_BWD: fixed-point shadows of d gamma / d beta (NULL: float atomics into a[0].dgamma / dbeta)
     unsigned drop_thresh; float drop_inv_keep; unsigned long long drop_seed;    // forward launches under dropout (drop_thresh 0: none)
     unsigned *counter;               // work queue: counter[0] = head, counter[1] = workgroups that have left the queue.  Both words are
                                      // zero between launches (the last workgroup to leave puts them back); NULL: tiles are dealt out round robin
@@ -150,18 +147,13 @@ __device__ __forceinline__ void tm_split8(const v4f a, const v4f b, bf16x8 &hi, 
     }
 }
 
-// NT: the tile's own traffic (input rows, masks, saved activations, output rows) is streamed with the non-temporal hint, so that
+// The tile's own traffic (input rows, masks, saved activations, output rows) is streamed with the non-temporal hint, so that
 // it does not push the weight planes -- which every workgroup of the XCD re-reads for every tile -- out of the 4 MB L2.
-template <bool NT>
-__device__ __forceinline__ v4f tm_ld(const float *p) {
-    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p));
-    return *reinterpret_cast<const v4f *>(p);
-}
-template <bool NT>
-__device__ __forceinline__ void tm_st(float *p, const v4f v) {
-    if (NT) __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(p));
-    else *reinterpret_cast<v4f *>(p) = v;
-}
+// With the first version of the kernel plain accesses were faster (saves 273 -> 290 us per 1024 tiles); now that a layer is bound
+// by the weight stream from L2, keeping the streamed tiles from displacing the weight planes pays: 17.02 -> 16.89 ms per
+// 2048-question step (three A/B pairs on one box), neutral at 128 questions and in inference.
+__device__ __forceinline__ v4f tm_ld(const float *p) { return __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p)); }
+__device__ __forceinline__ void tm_st(float *p, const v4f v) { __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(p)); }
 
 // a stage boundary: the workgroup barrier, and nothing scheduled across it (hipcc otherwise hoists the next stage's loads over the
 // barrier into the previous stage, where the accumulators are still live: spills)
@@ -180,12 +172,12 @@ __device__ __forceinline__ int tm_fresh_v(int v) {
 
 #define TM_SYNC() do { __builtin_amdgcn_sched_barrier(0); __syncthreads(); __builtin_amdgcn_sched_barrier(0); } while (0)
 
-// KIND 0: map-level forward operators; 1: vector-level tiles (64 instances per tile); 2: Temporal's backward chain (the LayerNorm
-// adjoint on the way in, the row-scale adjoint on the way out); 3: the map-level backward chains (relu' masks on the way in and
-// between the layers, broadcast input, dZ saves, accumulation).  Kernels of their own: what one form needs in registers and code
-// the others do not pay for (one kernel for everything kept 250+ registers live across the tile loop and spilled).
+// KIND_FWD: map-level forward operators; KIND_TEMPORAL_BWD: Temporal's backward chain (the LayerNorm adjoint on the way in, the
+// row-scale adjoint on the way out); KIND_CHAIN: the map-level backward chains (relu' masks on the way in and between the layers,
+// broadcast input, dZ saves, accumulation).  Kernels of their own: what one form needs in registers and code the others do not
+// pay for (one kernel for everything kept 250+ registers live across the tile loop and spilled).
 //
-// PACK (forms 0, 2, 3): a tile holds P = 64 / T instances of a bucket whose clips have T <= 32 frames -- tile w = instances
+// PACK: a tile holds P = 64 / T instances of a bucket whose clips have T <= 32 frames -- tile w = instances
 // P w .. min(P w + P, cnt) - 1, row R of the tile = frame R % T of instance P w + R / T, and a bucket has ceil(cnt / P) work items.
 // Every [cnt, T, H] buffer (save, save_in, act_mask, rs_out, the dropout element number) is then ONE run of rows for the tile, and
 // the MFMA loop does not know: only the indexed lookups (x_idx, rs_idx, in_mask_idx, out_idx, adj_*_idx, extra, len, pair_*) and
@@ -194,7 +186,7 @@ __device__ __forceinline__ int tm_fresh_v(int v) {
 // Rows of instances >= cnt and rows >= P T do not exist: their entries point at row 0 of the tile (read, zeroed, never written).
 // The relu' bit masks stay indexed by TILE number: a packed chain reads what the packed forward launch of the same bucket wrote.
 //
-// SPLIT (forms 0, 2, 3): an instance of T > 64 frames runs as S = ceil(T / 64) SEGMENTS, segment g = frames 64 g .. min(64 g + 64, T) - 1,
+// SPLIT: an instance of T > 64 frames runs as S = ceil(T / 64) SEGMENTS, segment g = frames 64 g .. min(64 g + 64, T) - 1,
 // and a bucket has cnt S tiles (tile = instance * S + segment; TmArg::pack carries S).  Every row of a tile belongs to ONE instance, so
 // nothing of the packed forms' tables is needed: the instance's lookups (x_idx, out_idx, extra, pair_*, len) are shared by its
 // segments, every [cnt, T, H] buffer and every per-frame array is entered 64 g rows / frames further on, and the MFMA loop does
@@ -206,10 +198,9 @@ __device__ __forceinline__ int tm_fresh_v(int v) {
 // the relu' bits, rs_out, and the rows / values of the STORE, LAYERNORM, COSINE and ROWDOT_SIGMOID tails; a chain tail that would
 // ADD adds nothing, one that stores first (STAIR_TILE_STORE_FIRST) stores zeros.  These are frames behind the clip's end: no
 // operator mixes them into a live frame and a plan zeroes them in its node outputs at the end of the pass anyway.
-template <bool NT, int KIND, bool PACK = false, bool SPLIT = false>
+template <TileKind KIND, bool PACK = false, bool SPLIT = false>
 __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
-    static_assert(!PACK || KIND != 1, "vector-level tiles hold 64 instances already");
-    static_assert(!SPLIT || (KIND != 1 && !PACK), "segments are a map-level form of their own");
+    static_assert(!SPLIT || !PACK, "segments are a form of their own");
     static_assert((kTileSplitMaxFrames + TM_ROWS - 1) / TM_ROWS <= 3, "the segment quotient below is written for S <= 3");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float *F = reinterpret_cast<float *>(lds);
@@ -221,10 +212,10 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #define TM_PK_LIVE 0x200
 #define TM_PK_FIRST 0x400
 #define TM_PK_S(arr_, row_) __builtin_amdgcn_readfirstlane((arr_)[row_])
-    // KIND 2: d gamma / d beta of the workgroup's tiles, column tid, as 64-bit fixed point (common.h): integer sums do not depend on
+    // KIND_TEMPORAL_BWD: d gamma / d beta of the workgroup's tiles, column tid, as 64-bit fixed point (common.h): integer sums do not depend on
     // which workgroup the queue gave which tile, so the parameter gradients are bit-identical from run to run
-    __shared__ long long tb_acc[KIND == 2 ? 2 * TM_H : 2];
-    if (KIND == 2) { tb_acc[threadIdx.x] = 0; tb_acc[TM_H + threadIdx.x] = 0; }
+    __shared__ long long tb_acc[KIND == KIND_TEMPORAL_BWD ? 2 * TM_H : 2];
+    if (KIND == KIND_TEMPORAL_BWD) { tb_acc[threadIdx.x] = 0; tb_acc[TM_H + threadIdx.x] = 0; }
     // the lane id comes from mbcnt wherever it is needed (EXEC is all ones there): threadIdx.x kept alive across the persistent
     // loop, beside 250+ live registers, went to scratch, and a kernel with ANY scratch pays for its setup at every launch
 #define TM_LANE() ((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)))
@@ -266,7 +257,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
         // SPLIT: `inst` is the TILE number (what the relu' bits are indexed by), `ii` the instance whose lookups the tile shares,
         // sfr0 its first frame; T (below) the rows of the segment that exist
         const int nsg = SPLIT ? p.pack : 1;
-        const bool walk = SPLIT && KIND == 0 && p.tail == STAIR_TILE_SUM_ROWS;
+        const bool walk = SPLIT && KIND == KIND_FWD && p.tail == STAIR_TILE_SUM_ROWS;
         const int item = w - pp.first[bsel];
         // (S <= 3: the quotient by shift / multiply-high on the scalar unit, not the vector unit's division sequence)
         const int ii = SPLIT ? (walk || nsg == 1 ? item : (nsg == 2 ? item >> 1 : (int)(__umulhi((unsigned)item, 0xAAAAAAABu) >> 1))) : item;
@@ -293,17 +284,14 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
         }
 
 
-        // rows of this tile: the T frames of a module instance, or (vector-level modules) up to 64 INSTANCES of one row each
-        const int vpack = KIND == 1 ? p.vec_pack : 0;    // the vector-level form is a kernel of its own (registers)
+        // rows of this tile: the T frames of a module instance
         // packed tiles: `inst` is the TILE number, pkI0 its first instance, pkN the instances it holds; T = the rows that exist
         const int pkI0 = PACK ? inst * p.pack : 0;
         const int pkN = PACK ? min(p.pack, p.cnt - pkI0) : 1;
-        const int T = PACK ? pkN * p.T : (vpack ? min(TM_ROWS, p.vec_cnt - TM_ROWS * inst) : (SPLIT ? min(TM_ROWS, p.T - sfr0) : p.T));
-        const int Ts = vpack ? TM_ROWS : p.T;            // rows between two tiles in the [cnt, T, H] save / mask buffers
+        const int T = PACK ? pkN * p.T : (SPLIT ? min(TM_ROWS, p.T - sfr0) : p.T);
         // first row of the tile in the [cnt, T, H] buffers
-#define TM_ROWBASE (PACK ? (int64_t)pkI0 * p.T : (SPLIT ? (int64_t)ii * p.T + sfr0 : (int64_t)inst * Ts))
-        const int nseg = vpack == 0 ? 1 : (vpack == 1 ? 2 : 3);
-        const bool xbc = KIND == 3 && p.x_broadcast;
+#define TM_ROWBASE (PACK ? (int64_t)pkI0 * p.T : (SPLIT ? (int64_t)ii * p.T + sfr0 : (int64_t)inst * p.T))
+        const bool xbc = KIND == KIND_CHAIN && p.x_broadcast;
         if (PACK) {
             if (wave == 0) {                             // lane R looks up what row R needs
                 const int R = TM_LANE();
@@ -315,24 +303,24 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 const int ln = p.len ? p.len[i] : Tc;
                 const bool live = ex && (!xbc || tt < ln);          // a broadcast row fills the clip's own frames only
                 int oraw = p.out_idx ? p.out_idx[i] : i;
-                const bool fst = KIND >= 2 && (oraw & STAIR_TILE_STORE_FIRST) != 0;
-                if (KIND >= 2) oraw &= ~STAIR_TILE_STORE_FIRST;
+                const bool fst = KIND != KIND_FWD && (oraw & STAIR_TILE_STORE_FIRST) != 0;
+                if (KIND != KIND_FWD) oraw &= ~STAIR_TILE_STORE_FIRST;
                 pk_tf[R] = (live ? tt : 0) | (tt << 16) | (live ? TM_PK_LIVE : 0) | (fst ? TM_PK_FIRST : 0);
                 pk_xi[R] = p.x_idx ? p.x_idx[i] : i;
                 pk_oi[R] = oraw;
                 pk_len[R] = ln;
-                if (KIND == 0) {
+                if (KIND == KIND_FWD) {
                     pk_sc[R] = p.row_scale ? p.row_scale[(int64_t)(p.rs_idx ? p.rs_idx[i] : i) * Tc + tt] : 1.0f;
                     pk_ex[R] = p.extra ? p.extra[i] : 0.f;
                     pk_pf[R] = p.tail == STAIR_TILE_COSINE ? p.pair_first[i] : 0;
                     pk_pc[R] = p.tail == STAIR_TILE_COSINE ? p.pair_cnt[i] : 0;
                 }
-                if (KIND == 2 || KIND == 3) pk_mi[R] = p.in_mask_idx ? p.in_mask_idx[i] : i;
-                if (KIND == 2) {
+                if (KIND == KIND_TEMPORAL_BWD || KIND == KIND_CHAIN) pk_mi[R] = p.in_mask_idx ? p.in_mask_idx[i] : i;
+                if (KIND == KIND_TEMPORAL_BWD) {
                     pk_fi[R] = p.adj_feat_idx ? p.adj_feat_idx[i] : i;
                     pk_ri[R] = p.adj_rs_idx ? p.adj_rs_idx[i] : i;
                 }
-                if (KIND >= 2) {
+                if (KIND != KIND_FWD) {
                     const unsigned long long notfirst = __ballot(ex && !fst);
                     if (R == 0) pk_allfirst = notfirst == 0ull ? 1 : 0;
                 }
@@ -342,59 +330,14 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
         // ---- the input tile: fp32 rows -> (row scale) -> bf16 hi / lo image ------------------------------------------
         // (SPLIT: the bases enter the instance's rows / per-frame values at the segment's first frame; a broadcast input is one row)
         const float *x = PACK ? nullptr : tm_fresh(p.X + (int64_t)(p.x_idx ? __builtin_amdgcn_readfirstlane(p.x_idx[ii]) : ii) * p.x_gstride + (SPLIT && !xbc ? (int64_t)sfr0 * TM_H : 0));
-        const float *rsrow = PACK ? nullptr : (KIND == 0 && p.row_scale ? p.row_scale + (int64_t)(p.rs_idx ? __builtin_amdgcn_readfirstlane(p.rs_idx[ii]) : ii) * (SPLIT ? p.T : T) + sfr0 : nullptr);
-        const bool has_rs = PACK ? (KIND == 0 && p.row_scale != nullptr) : rsrow != nullptr;
+        const float *rsrow = PACK ? nullptr : (KIND == KIND_FWD && p.row_scale ? p.row_scale + (int64_t)(p.rs_idx ? __builtin_amdgcn_readfirstlane(p.rs_idx[ii]) : ii) * (SPLIT ? p.T : T) + sfr0 : nullptr);
+        const bool has_rs = PACK ? (KIND == KIND_FWD && p.row_scale != nullptr) : rsrow != nullptr;
         // (a NULL must stay a visible NULL: through tm_fresh the forward kernel kept the whole mask path, and its registers)
-        const float *imask = PACK ? ((KIND == 2 || KIND == 3) && p.in_mask ? p.in_mask : nullptr)
-                                  : ((KIND == 2 || KIND == 3) && p.in_mask ? tm_fresh(p.in_mask + (int64_t)(p.in_mask_idx ? __builtin_amdgcn_readfirstlane(p.in_mask_idx[ii]) : ii) * p.in_mask_gstride + (SPLIT ? (int64_t)sfr0 * TM_H : 0)) : nullptr);
+        const float *imask = PACK ? ((KIND == KIND_TEMPORAL_BWD || KIND == KIND_CHAIN) && p.in_mask ? p.in_mask : nullptr)
+                                  : ((KIND == KIND_TEMPORAL_BWD || KIND == KIND_CHAIN) && p.in_mask ? tm_fresh(p.in_mask + (int64_t)(p.in_mask_idx ? __builtin_amdgcn_readfirstlane(p.in_mask_idx[ii]) : ii) * p.in_mask_gstride + (SPLIT ? (int64_t)sfr0 * TM_H : 0)) : nullptr);
         const int Lrows = PACK ? T : (SPLIT ? (xbc ? seg_len : T)
                                             : (xbc ? (p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T) : T));     // a broadcast row fills the clip's own frames only
-        // vector-level modules: row t of the tile is H-wide block `seg` of the concatenation built from the two operand rows
-        // of instance 64 inst + t (never materialised for the GEMM; cat_save keeps it for the weight gradient)
-        auto build_vec_image = [&](const int seg) {
-            const int c8 = tm_fresh_v(lane);          // (row wave + 8 j, columns 8 c8 .. +7); offsets computed here, see above
-#pragma unroll 1
-            for (int half = 0; half < 2; ++half) {
-                v4f a0[4], a1[4], b0[4], b1[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {         // all operand rows of four instances first, then the arithmetic
-                    const int t = wave + 8 * (4 * half + j);
-                    const int64_t i = (int64_t)TM_ROWS * inst + (t < T ? t : 0);
-                    const float *ar = p.pk_a + (int64_t)(p.pk_a_idx ? __builtin_amdgcn_readfirstlane(p.pk_a_idx[i]) : i) * TM_H + 8 * c8;
-                    const float *br = p.pk_b + (int64_t)(p.pk_b_idx ? __builtin_amdgcn_readfirstlane(p.pk_b_idx[i]) : i) * TM_H + 8 * c8;
-                    a0[j] = *reinterpret_cast<const v4f *>(ar); a1[j] = *reinterpret_cast<const v4f *>(ar + 4);
-                    b0[j] = *reinterpret_cast<const v4f *>(br); b1[j] = *reinterpret_cast<const v4f *>(br + 4);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int t = wave + 8 * (4 * half + j);
-                    v4f a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-                    if (t < T) {
-                        if (vpack == 1) { a = seg == 0 ? a0[j] : b0[j]; b = seg == 0 ? a1[j] : b1[j]; }
-                        else if (vpack == 2) {
-                            if (seg == 0) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) { a[e] = fabsf(a0[j][e] - b0[j][e]); b[e] = fabsf(a1[j][e] - b1[j][e]); }
-                            } else { a = seg == 1 ? a0[j] : b0[j]; b = seg == 1 ? a1[j] : b1[j]; }
-                        } else {
-                            if (seg == 2) { a = a0[j] * b0[j]; b = a1[j] * b1[j]; }
-                            else { a = seg == 0 ? a0[j] : b0[j]; b = seg == 0 ? a1[j] : b1[j]; }
-                        }
-                        if (p.cat_save) {
-                            float *d = p.cat_save + (((int64_t)TM_ROWS * inst + t) * nseg + seg) * TM_H + 8 * c8;
-                            *reinterpret_cast<v4f *>(d) = a; *reinterpret_cast<v4f *>(d + 4) = b;
-                        }
-                    }
-                    bf16x8 hi, lo;
-                    tm_split8(a, b, hi, lo);
-                    const int off = (c8 >> 2) * TM_STAGE + (t * 4 + ((c8 & 3) ^ tm_swz(t))) * 16;
-                    *reinterpret_cast<bf16x8 *>(lds + off) = hi;
-                    *reinterpret_cast<bf16x8 *>(lds + off + 4096) = lo;
-                }
-            }
-        };
-        if (vpack) build_vec_image(0);
-        else if (KIND == 2) {
+        if (KIND == KIND_TEMPORAL_BWD) {
             // Temporal's backward (autograd of modules.py:283,327: y = LayerNorm(a), a = ReLU(Lin(r_t feat_t))): the incoming gradient
             // rows dY = X go through the adjoint of LayerNorm at the saved rows a = in_mask and through relu'(a) on their way into the
             // image; what is written there (and kept: save_in) is dZ of the dense layer.  Thread (wave, lane) carries columns
@@ -413,10 +356,10 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     const int ts = PACK ? (TM_PK_S(pk_tf, t) & 63) : (t < T ? t : 0);
                     const float *xrow = PACK ? p.X + (int64_t)TM_PK_S(pk_xi, t) * p.x_gstride : x;
                     const float *yrow = PACK ? p.in_mask + (int64_t)TM_PK_S(pk_mi, t) * p.in_mask_gstride : ysv;
-                    xa[j] = tm_ld<NT>(xrow + (int64_t)ts * TM_H + 8 * c8);
-                    xb[j] = tm_ld<NT>(xrow + (int64_t)ts * TM_H + 8 * c8 + 4);
-                    ya[j] = tm_ld<NT>(yrow + (int64_t)ts * TM_H + 8 * c8);
-                    yb[j] = tm_ld<NT>(yrow + (int64_t)ts * TM_H + 8 * c8 + 4);
+                    xa[j] = tm_ld(xrow + (int64_t)ts * TM_H + 8 * c8);
+                    xb[j] = tm_ld(xrow + (int64_t)ts * TM_H + 8 * c8 + 4);
+                    ya[j] = tm_ld(yrow + (int64_t)ts * TM_H + 8 * c8);
+                    yb[j] = tm_ld(yrow + (int64_t)ts * TM_H + 8 * c8 + 4);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -457,7 +400,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     const int t = wave + 8 * j;
                     if (t < T) {
                         float *d = p.save_in + (TM_ROWBASE + t) * TM_H + 8 * c8;
-                        tm_st<NT>(d, dz[j][0]); tm_st<NT>(d + 4, dz[j][1]);
+                        tm_st(d, dz[j][0]); tm_st(d + 4, dz[j][1]);
                     }
                 }
             }
@@ -492,7 +435,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             const int c8 = lane;
             // relu' of a saved activation as ONE bit per element (8 bytes per thread and tile instead of 256: the forward pass wrote
             // them in this thread's own (row, column) order, save_bits)
-            const unsigned long long ibits = (KIND == 3 && p.in_bits) ? p.in_bits[(int64_t)inst * TM_H + 64 * wave + c8] : 0ull;
+            const unsigned long long ibits = (KIND == KIND_CHAIN && p.in_bits) ? p.in_bits[(int64_t)inst * TM_H + 64 * wave + c8] : 0ull;
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
                 v4f xa[4], xb[4], ma[4], mb[4];
@@ -503,13 +446,13 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     const int ts = PACK ? (TM_PK_S(pk_tf, t) & 63) : (t < Lrows ? t : 0);
                     const float *xrow = PACK ? p.X + (int64_t)TM_PK_S(pk_xi, t) * p.x_gstride : x;
                     const float *xr = xrow + (xbc ? 0 : (int64_t)ts * TM_H) + 8 * c8;
-                    xa[j] = tm_ld<NT>(xr);
-                    xb[j] = tm_ld<NT>(xr + 4);
+                    xa[j] = tm_ld(xr);
+                    xb[j] = tm_ld(xr + 4);
                     sc[j] = PACK ? (has_rs ? pk_sc[t] : 1.0f) : (rsrow ? rsrow[ts] : 1.0f);
                     if (imask) {
                         const float *mrow = PACK ? p.in_mask + (int64_t)TM_PK_S(pk_mi, t) * p.in_mask_gstride : imask;
-                        ma[j] = tm_ld<NT>(mrow + (int64_t)ts * TM_H + 8 * c8);
-                        mb[j] = tm_ld<NT>(mrow + (int64_t)ts * TM_H + 8 * c8 + 4);
+                        ma[j] = tm_ld(mrow + (int64_t)ts * TM_H + 8 * c8);
+                        mb[j] = tm_ld(mrow + (int64_t)ts * TM_H + 8 * c8 + 4);
                     }
                 }
 #pragma unroll
@@ -520,7 +463,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     if (imask) {              // backward chains: the incoming gradient times relu'(saved activation) (x in_scale)
 #pragma unroll
                         for (int i = 0; i < 4; ++i) { a[i] = ma[j][i] > 0.f ? a[i] * p.in_scale : 0.f; b[i] = mb[j][i] > 0.f ? b[i] * p.in_scale : 0.f; }
-                    } else if (KIND == 3 && p.in_bits) {
+                    } else if (KIND == KIND_CHAIN && p.in_bits) {
                         const unsigned m = (unsigned)(ibits >> (8 * (4 * half + j))) & 0xffu;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) { a[i] = (m >> i) & 1u ? a[i] * p.in_scale : 0.f; b[i] = (m >> (4 + i)) & 1u ? b[i] * p.in_scale : 0.f; }
@@ -533,13 +476,13 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     *reinterpret_cast<bf16x8 *>(lds + off) = hi;
                     *reinterpret_cast<bf16x8 *>(lds + off + 4096) = lo;
                 }
-                if (KIND == 3 && p.save_in) {
+                if (KIND == KIND_CHAIN && p.save_in) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int t = wave + 8 * (4 * half + j);
                         if (t < T) {
                             float *d = p.save_in + (TM_ROWBASE + t) * TM_H + 8 * c8;
-                            tm_st<NT>(d, xa[j]); tm_st<NT>(d + 4, xb[j]);
+                            tm_st(d, xa[j]); tm_st(d + 4, xb[j]);
                         }
                     }
                 }
@@ -556,22 +499,15 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
             // ---- Z^T[n][t] += W[n][k] tile[t][k]: this wave's 64 weight rows straight from HBM / L2 in fragment order ----
-            // (a vector-level module's first layer: once per H-wide block of the concatenated input, into the same accumulators)
-            for (int seg = 0; seg < (ph == 0 ? nseg : 1); ++seg) {
-                if (seg > 0) {
-                    TM_SYNC();              // every wave has finished reading the previous block's image
-                    build_vec_image(seg);
-                    TM_SYNC();
-                }
-                const bf16x8 *wq = static_cast<const bf16x8 *>(p.W[ph]) + (int64_t)seg * (TM_H * TM_H * 2 / 8) + (int64_t)(2 * wave) * TM_KS * 2 * 64 + lane;
-                bf16x8 wf[4][2][2];
+            const bf16x8 *wq = static_cast<const bf16x8 *>(p.W[ph]) + (int64_t)(2 * wave) * TM_KS * 2 * 64 + lane;
+            bf16x8 wf[4][2][2];
 #define TM_LOADW(slot_, ks_)                                                                                  \
     _Pragma("unroll") for (int nt_ = 0; nt_ < 2; ++nt_)                                                       \
         _Pragma("unroll") for (int pl_ = 0; pl_ < 2; ++pl_)                                                   \
             wf[slot_][nt_][pl_] = wq[((nt_ * TM_KS + (ks_)) * 2 + pl_) * 64];
-                TM_LOADW(0, 0) TM_LOADW(1, 1) TM_LOADW(2, 2)
-                // tile fragments are read one k step ahead as well (the LDS round trip hides behind the previous step's MFMAs)
-                bf16x8 zh[2][2], zl[2][2];
+            TM_LOADW(0, 0) TM_LOADW(1, 1) TM_LOADW(2, 2)
+            // tile fragments are read one k step ahead as well (the LDS round trip hides behind the previous step's MFMAs)
+            bf16x8 zh[2][2], zl[2][2];
 #define TM_LOADZ(set_, ks_)                                                                                   \
     {                                                                                                         \
         const char *sb_ = lds + ((ks_) >> 1) * TM_STAGE;                                                      \
@@ -581,46 +517,45 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             zl[set_][tt_] = *reinterpret_cast<const bf16x8 *>(sb_ + 4096 + (offT[tt_] ^ cx_));                \
         }                                                                                                     \
     }
-                TM_LOADZ(0, 0)
-                for (int ks0 = 0; ks0 < TM_KS; ks0 += 4) {
+            TM_LOADZ(0, 0)
+            for (int ks0 = 0; ks0 < TM_KS; ks0 += 4) {
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int ks = ks0 + u;
-                        if (ks + 3 < TM_KS) { TM_LOADW((u + 3) & 3, ks + 3) }
-                        if (ks + 1 < TM_KS) { TM_LOADZ((u + 1) & 1, ks + 1) }
-                        // the loads stay ABOVE this step's MFMAs: hipcc otherwise sinks each weight load to just before its use three
-                        // steps later (fewer live registers), and every k step then waits out an L2 round trip
-                        __builtin_amdgcn_sched_barrier(0);
-                        // product-major order: four independent accumulators between two MFMAs on the same one
+                for (int u = 0; u < 4; ++u) {
+                    const int ks = ks0 + u;
+                    if (ks + 3 < TM_KS) { TM_LOADW((u + 3) & 3, ks + 3) }
+                    if (ks + 1 < TM_KS) { TM_LOADZ((u + 1) & 1, ks + 1) }
+                    // the loads stay ABOVE this step's MFMAs: hipcc otherwise sinks each weight load to just before its use three
+                    // steps later (fewer live registers), and every k step then waits out an L2 round trip
+                    __builtin_amdgcn_sched_barrier(0);
+                    // product-major order: four independent accumulators between two MFMAs on the same one
 #pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
+                    for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                            for (int tt = 0; tt < 2; ++tt)
-                                acc[nt][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[u][nt][1], zh[u & 1][tt], acc[nt][tt], 0, 0, 0);
+                        for (int tt = 0; tt < 2; ++tt)
+                            acc[nt][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[u][nt][1], zh[u & 1][tt], acc[nt][tt], 0, 0, 0);
 #pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
+                    for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                            for (int tt = 0; tt < 2; ++tt)
-                                acc[nt][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[u][nt][0], zl[u & 1][tt], acc[nt][tt], 0, 0, 0);
+                        for (int tt = 0; tt < 2; ++tt)
+                            acc[nt][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[u][nt][0], zl[u & 1][tt], acc[nt][tt], 0, 0, 0);
 #pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
+                    for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                            for (int tt = 0; tt < 2; ++tt)
-                                acc[nt][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[u][nt][0], zh[u & 1][tt], acc[nt][tt], 0, 0, 0);
-                    }
+                        for (int tt = 0; tt < 2; ++tt)
+                            acc[nt][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[u][nt][0], zh[u & 1][tt], acc[nt][tt], 0, 0, 0);
                 }
+            }
 #undef TM_LOADZ
 #undef TM_LOADW
-            }
             // ---- bias + ReLU in the accumulator layout: lane (r, h) holds frame t = 32 tt + r, columns
             //      n = 64 wave + 32 nt + 8 q + 4 h + i for e = 4 q + i -- then the tile goes to LDS as fp32 rows ---------------
             const int lane_e = tm_fresh_v(lane), r_e = lane_e & 31, h_e = lane_e >> 5;     // offsets of this stage are computed HERE, not before the k loop
             const float *bias = p.bias[ph];
-            const int act = (KIND == 3 || p.act[ph] != 3) ? p.act[ph] : 0;          // act 3 (relu' of a saved activation) is the chains' (KIND 3)
+            const int act = (KIND == KIND_CHAIN || p.act[ph] != 3) ? p.act[ph] : 0;          // act 3 (relu' of a saved activation) is the chains' (KIND_CHAIN)
             const bool last = ph + 1 == p.n_layers;
-            const unsigned dsite = (KIND == 0 && pp.drop_thresh) ? p.drop_site[ph] : 0u;
+            const unsigned dsite = (KIND == KIND_FWD && pp.drop_thresh) ? p.drop_site[ph] : 0u;
             // between two layers of an inference plan nothing touches HBM: the accumulators go straight into the next image
-            const bool direct = !last && !p.save[ph] && !(KIND == 0 && p.save_bits[ph]) && act != 3 && !(KIND == 0 && p.mid_rowdot && ph == 1);
+            const bool direct = !last && !p.save[ph] && !(KIND == KIND_FWD && p.save_bits[ph]) && act != 3 && !(KIND == KIND_FWD && p.mid_rowdot && ph == 1);
             v4f bvs[2][4];                        // the lane's 32 bias values, loaded together (one round trip, behind the barrier)
             __builtin_amdgcn_sched_barrier(0);    // ... and not earlier: inside the k loop they would cost 32 registers
 #pragma unroll
@@ -643,7 +578,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                             z[i] = acc[nt][tt][4 * q + i] + bv[i];
                             if (act == 1) z[i] = fmaxf(z[i], 0.0f);
                         }
-                        if (KIND == 0 && dsite) {       // nn.Dropout behind this activation: the bits stair_dropout_fwd draws for the [cnt, T, H] rows
+                        if (KIND == KIND_FWD && dsite) {       // nn.Dropout behind this activation: the bits stair_dropout_fwd draws for the [cnt, T, H] rows
                             const unsigned long long e0 = ((PACK ? (unsigned long long)pkI0 : (unsigned long long)ii) * p.T + sfr0 + t) * p.H + (64 * wave + 32 * nt + 8 * q + 4 * h_e);
                             const unsigned long long bits4 = drop_hash4(pp.drop_seed, dsite - 1u, e0 >> 2);      // e0 % 4 == 0 (H % 4 == 0)
 #pragma unroll
@@ -668,12 +603,12 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 //      need, FilterFrame's attention; then the rows become the next layer's bf16 hi / lo operand image.
                 //      The rows are read into registers first: the image overlays the staging. -----------------------------------
                 float *sv = tm_fresh(p.save[ph]);
-                const float *amask = KIND == 3 && act == 3 && p.act_mask[ph] ? tm_fresh(p.act_mask[ph] + TM_ROWBASE * TM_H) : nullptr;
-                const unsigned long long *abits_p = KIND == 3 && act == 3 && !amask ? p.act_bits[ph] : nullptr;
+                const float *amask = KIND == KIND_CHAIN && act == 3 && p.act_mask[ph] ? tm_fresh(p.act_mask[ph] + TM_ROWBASE * TM_H) : nullptr;
+                const unsigned long long *abits_p = KIND == KIND_CHAIN && act == 3 && !amask ? p.act_bits[ph] : nullptr;
                 const unsigned long long abits = abits_p ? abits_p[(int64_t)inst * TM_H + 64 * wave + lane_e] : 0ull;
-                unsigned long long *svbits = KIND == 0 ? p.save_bits[ph] : nullptr;
+                unsigned long long *svbits = KIND == KIND_FWD ? p.save_bits[ph] : nullptr;
                 unsigned long long obits = 0ull;
-                const bool rowdot = KIND == 0 && p.mid_rowdot && ph == 1;
+                const bool rowdot = KIND == KIND_FWD && p.mid_rowdot && ph == 1;
                 v4f rowv[8][2];
                 // every global load of the stage first (the relu' masks of all eight rows, the row-dot weights): interleaved with
                 // the saves they ran one memory round trip per row
@@ -691,8 +626,8 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #pragma unroll
                         for (int jj = 0; jj < 4; ++jj) {
                             const int t = wave + 8 * (4 * half + jj), ts = t < T ? t : 0;
-                            mk[jj][0] = tm_ld<NT>(amask + (int64_t)ts * TM_H + 8 * lane_e);
-                            mk[jj][1] = tm_ld<NT>(amask + (int64_t)ts * TM_H + 8 * lane_e + 4);
+                            mk[jj][0] = tm_ld(amask + (int64_t)ts * TM_H + 8 * lane_e);
+                            mk[jj][1] = tm_ld(amask + (int64_t)ts * TM_H + 8 * lane_e + 4);
                         }
                     }
 #pragma unroll
@@ -716,7 +651,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                             }
                             if (sv) {
                                 float *d = sv + (TM_ROWBASE + t) * TM_H + 8 * lane_e;
-                                tm_st<NT>(d, a); tm_st<NT>(d + 4, b);
+                                tm_st(d, a); tm_st(d + 4, b);
                             }
                             if (rowdot) {         // FilterFrame: a_t = sigmoid(w[:H] . f_t + extra + b); the next layer runs on a_t f_t
                                 float d = 0.f;
@@ -750,10 +685,10 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
         if (svl)                                      // the last layer's rows for the backward pass (coalesced 2 KB rows)
             for (int t = wave; t < T; t += 8) {
                 float *dst = svl + (TM_ROWBASE + t) * TM_H;
-                tm_st<NT>(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane));
-                tm_st<NT>(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane));
+                tm_st(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane));
+                tm_st(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane));
             }
-        if (KIND == 0 && p.save_bits[p.n_layers - 1]) {     // relu' of the last layer's rows, in the order the chain's input stage reads them
+        if (KIND == KIND_FWD && p.save_bits[p.n_layers - 1]) {     // relu' of the last layer's rows, in the order the chain's input stage reads them
             unsigned long long obits = 0ull;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -766,10 +701,10 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             }
             p.save_bits[p.n_layers - 1][(int64_t)inst * TM_H + 64 * wave + lane] = obits;
         }
-        // backward chains (forms 2 and 3): bit STAIR_TILE_STORE_FIRST of an out_idx entry marks a target nothing has written yet
+        // backward chains (both forms): bit STAIR_TILE_STORE_FIRST of an out_idx entry marks a target nothing has written yet
         const int oraw = PACK ? 0 : (p.out_idx ? __builtin_amdgcn_readfirstlane(p.out_idx[ii]) : (int)ii);
-        const bool ofirst = KIND >= 2 && (oraw & STAIR_TILE_STORE_FIRST) != 0;
-        const int64_t oslot = KIND >= 2 ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
+        const bool ofirst = KIND != KIND_FWD && (oraw & STAIR_TILE_STORE_FIRST) != 0;
+        const int64_t oslot = KIND != KIND_FWD ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
         const int64_t orow0 = SPLIT ? (int64_t)sfr0 * TM_H : 0;       // the segment's first row in the instance's [T, H] target
         if (PACK) {
             // ---- the tails of a packed tile: the same arithmetic per row, every row at its own instance's targets ----------------
@@ -779,7 +714,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             // (row R's frame, and its tile in `out`: the entry of out_idx without the STORE_FIRST bit)
 #define TM_PK_T(row_) ((TM_PK_S(pk_tf, row_) >> 16) & 63)
 #define TM_PK_OUT(row_) (p.out + (int64_t)TM_PK_S(pk_oi, row_) * p.out_gstride)
-            if (KIND == 2) {
+            if (KIND == KIND_TEMPORAL_BWD) {
                 // ROWSCALE_ADJ (see the unpacked form below): d feat_t += r_t G_t, d r_t += G_t . feat_t, per row
                 __builtin_amdgcn_sched_barrier(0);
                 v4f f0[8], f1[8];
@@ -788,8 +723,8 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 for (int j = 0; j < 8; ++j) {           // every global load of the tail first
                     const int R = wave + 8 * j, ts = TM_PK_S(pk_tf, R) & 63;
                     const float *feat = p.adj_feat + (int64_t)TM_PK_S(pk_fi, R) * p.adj_feat_gstride + (int64_t)ts * TM_H;
-                    f0[j] = tm_ld<NT>(feat + 4 * lane);
-                    f1[j] = tm_ld<NT>(feat + 256 + 4 * lane);
+                    f0[j] = tm_ld(feat + 4 * lane);
+                    f1[j] = tm_ld(feat + 256 + 4 * lane);
                     rr[j] = p.adj_rs[(int64_t)TM_PK_S(pk_ri, R) * Tc + ts];
                 }
                 const bool allfirst = TM_PK_S(&pk_allfirst, 0) != 0;
@@ -863,17 +798,17 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     }
                 }
             } else
-            switch (KIND == 3 && p.tail != STAIR_TILE_ACCUMULATE ? (p.tail == STAIR_TILE_STORE ? STAIR_TILE_STORE : STAIR_TILE_NONE)
-                                                                 : (KIND != 3 && p.tail == STAIR_TILE_ACCUMULATE ? STAIR_TILE_NONE : p.tail)) {
+            switch (KIND == KIND_CHAIN && p.tail != STAIR_TILE_ACCUMULATE ? (p.tail == STAIR_TILE_STORE ? STAIR_TILE_STORE : STAIR_TILE_NONE)
+                                                                 : (KIND != KIND_CHAIN && p.tail == STAIR_TILE_ACCUMULATE ? STAIR_TILE_NONE : p.tail)) {
                 case STAIR_TILE_STORE:
                     for (int R = wave; R < T; R += 8) {
                         float *dst = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
-                        tm_st<NT>(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane));
-                        tm_st<NT>(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane));
+                        tm_st(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane));
+                        tm_st(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane));
                     }
                     break;
                 case STAIR_TILE_ACCUMULATE:
-                    if (KIND != 3) break;
+                    if (KIND != KIND_CHAIN) break;
                     if (TM_PK_S(&pk_allfirst, 0) != 0) {        // every instance of the tile stores: no target is read
                         for (int R = wave; R < T; R += 8) {
                             float *dst = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
@@ -919,7 +854,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     }
                     break;
                 case STAIR_TILE_SUM_ROWS: {               // one sum per instance, over its own frames, in frame order
-                    if (KIND == 3) break;
+                    if (KIND == KIND_CHAIN) break;
                     const int col = tm_fresh_v(TM_TID());
                     for (int sg = 0; sg < pkN; ++sg) {
                         const int R0 = sg * Tc;
@@ -931,7 +866,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     break;
                 }
                 case STAIR_TILE_COSINE: {                 // every instance against its own keyword rows
-                    if (KIND == 3) break;
+                    if (KIND == KIND_CHAIN) break;
                     for (int sg = 0; sg < pkN; ++sg) {
                         const int R0 = sg * Tc;
                         const int first = TM_PK_S(pk_pf, R0), cn = TM_PK_S(pk_pc, R0);
@@ -961,7 +896,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     break;
                 }
                 case STAIR_TILE_ROWDOT_SIGMOID: {
-                    if (KIND == 3) break;
+                    if (KIND == KIND_CHAIN) break;
                     const v4f w0 = *reinterpret_cast<const v4f *>(p.vw + 4 * lane), w1 = *reinterpret_cast<const v4f *>(p.vw + 256 + 4 * lane);
                     const float vb0 = p.vb[0];
                     for (int R = wave; R < T; R += 8) {
@@ -976,7 +911,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     break;
                 }
                 case STAIR_TILE_LAYERNORM: {
-                    if (KIND == 3) break;
+                    if (KIND == KIND_CHAIN) break;
                     const v4f g0 = *reinterpret_cast<const v4f *>(p.gamma + 4 * lane), g1 = *reinterpret_cast<const v4f *>(p.gamma + 256 + 4 * lane);
                     const v4f b0 = *reinterpret_cast<const v4f *>(p.beta + 4 * lane), b1 = *reinterpret_cast<const v4f *>(p.beta + 256 + 4 * lane);
                     for (int R = wave; R < T; R += 8) {
@@ -1002,7 +937,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #undef TM_PK_OUT
 #undef TM_PK_T
         } else
-        if (KIND == 2) {
+        if (KIND == KIND_TEMPORAL_BWD) {
             // tail ROWSCALE_ADJ: the staged rows are G = dZ W, the gradient of the SCALED input r_t feat_t of the dense layer:
             // d feat_t += r_t G_t (one dword per lane, 256 contiguous bytes per wave-instruction), d r_t += G_t . feat_t
             const float *feat = tm_fresh(p.adj_feat + (int64_t)(p.adj_feat_idx ? __builtin_amdgcn_readfirstlane(p.adj_feat_idx[ii]) : ii) * p.adj_feat_gstride + (SPLIT ? (int64_t)sfr0 * TM_H : 0));
@@ -1016,8 +951,8 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {           // every global load of the tail first
                 const int t = wave + 8 * j, ts = t < T ? t : 0;
-                f0[j] = tm_ld<NT>(feat + (int64_t)ts * TM_H + 4 * lane);
-                f1[j] = tm_ld<NT>(feat + (int64_t)ts * TM_H + 256 + 4 * lane);
+                f0[j] = tm_ld(feat + (int64_t)ts * TM_H + 4 * lane);
+                f1[j] = tm_ld(feat + (int64_t)ts * TM_H + 256 + 4 * lane);
                 rr[j] = rs[ts];
             }
             if (ofirst) {                           // first contribution to a tile the pass has not cleared: rows stored, the target not read
@@ -1074,25 +1009,17 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 }
             }
         } else
-        switch (KIND == 3 && p.tail != STAIR_TILE_ACCUMULATE ? (p.tail == STAIR_TILE_STORE ? STAIR_TILE_STORE : STAIR_TILE_NONE)
-                                                             : (KIND != 3 && p.tail == STAIR_TILE_ACCUMULATE ? STAIR_TILE_NONE : p.tail)) {
+        switch (KIND == KIND_CHAIN && p.tail != STAIR_TILE_ACCUMULATE ? (p.tail == STAIR_TILE_STORE ? STAIR_TILE_STORE : STAIR_TILE_NONE)
+                                                             : (KIND != KIND_CHAIN && p.tail == STAIR_TILE_ACCUMULATE ? STAIR_TILE_NONE : p.tail)) {
             case STAIR_TILE_STORE:
                 for (int t = wave; t < T; t += 8) {
                     float *dst = p.out + oslot * p.out_gstride + orow0 + (int64_t)t * TM_H;
-                    tm_st<NT>(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane));
-                    tm_st<NT>(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane));
-                }
-                break;
-            case STAIR_TILE_STORE_ROWS:               // vector-level modules: row t = instance 64 inst + t goes to its own slot
-                if (KIND != 1) break;
-                for (int t = wave; t < T; t += 8) {
-                    float *dst = p.out + (int64_t)p.out_row_idx[(int64_t)TM_ROWS * inst + t] * p.out_gstride;
-                    *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane);
-                    *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                    tm_st(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane));
+                    tm_st(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane));
                 }
                 break;
             case STAIR_TILE_ACCUMULATE:               // backward chains: dX added into a gradient tile several instances may share
-                if (KIND != 3) break;
+                if (KIND != KIND_CHAIN) break;
                 // one dword per lane, 256 contiguous bytes per wave-instruction: the shape float atomics run at full rate in
                 // (MI355X_MICROARCH.md "Global float atomics"; 16-byte-strided lanes spread an instruction over 1 KB)
                 if (ofirst) {
@@ -1136,7 +1063,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 }
                 break;
             case STAIR_TILE_SUM_ROWS: {               // Filter: sum over the clip's own frames (modules.py:374,376)
-                if (KIND == 3) break;
+                if (KIND == KIND_CHAIN) break;
                 const int L = SPLIT ? seg_len : (p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T);
                 const int col = tm_fresh_v(TM_TID());       // (not hoisted out of the tile loop: three values kept that way went to scratch)
                 float s = SPLIT && sgn > 0 ? walk_sum : 0.f;    // (SPLIT: the instance's frames in order, segment after segment)
@@ -1149,7 +1076,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 break;
             }
             case STAIR_TILE_COSINE: {                 // Localize: (cos(f_t, k_j) + 1) * 0.49, nn.CosineSimilarity eps 1e-8
-                if (KIND == 3) break;
+                if (KIND == KIND_CHAIN) break;
                 const int first = __builtin_amdgcn_readfirstlane(p.pair_first[ii]), cn = __builtin_amdgcn_readfirstlane(p.pair_cnt[ii]);
                 // pair-major: a keyword row (and its norm, and its attention slot) is fetched once, not once per frame
                 for (int j = 0; j < cn; ++j) {
@@ -1176,7 +1103,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 break;
             }
             case STAIR_TILE_ROWDOT_SIGMOID: {         // HasItem: sigmoid(w . row + b) (modules.py:131-137)
-                if (KIND == 3) break;
+                if (KIND == KIND_CHAIN) break;
                 const v4f w0 = *reinterpret_cast<const v4f *>(p.vw + 4 * lane), w1 = *reinterpret_cast<const v4f *>(p.vw + 256 + 4 * lane);
                 const float off = p.vb[0] + (p.extra ? p.extra[ii] : 0.f);
                 for (int t = wave; t < T; t += 8) {
@@ -1190,7 +1117,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 break;
             }
             case STAIR_TILE_LAYERNORM: {              // Temporal: LayerNorm over H, eps 1e-5, biased variance (modules.py:283,327)
-                if (KIND == 3) break;
+                if (KIND == KIND_CHAIN) break;
                 const v4f g0 = *reinterpret_cast<const v4f *>(p.gamma + 4 * lane), g1 = *reinterpret_cast<const v4f *>(p.gamma + 256 + 4 * lane);
                 const v4f b0 = *reinterpret_cast<const v4f *>(p.beta + 4 * lane), b1 = *reinterpret_cast<const v4f *>(p.beta + 256 + 4 * lane);
                 for (int t = wave; t < T; t += 8) {
@@ -1219,7 +1146,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
     // -- eager, or the same kernel node of a replayed hipGraph -- finds them at 0 without any memset in between.
     // (thread 0's last head ticket has RETURNED before it signs off -- it branched on the value -- so no fence is needed between the two)
     const int tid = TM_TID();
-    if (KIND == 2) {        // column tid of d gamma / d beta: written and read by this thread only, no barrier needed
+    if (KIND == KIND_TEMPORAL_BWD) {        // column tid of d gamma / d beta: written and read by this thread only, no barrier needed
         // an accumulator that left the fixed-point range (common.h fx_acc) makes its column NaN: added to the fp32 element, to which
         // the shadow's flush / the other workgroups' float atomics add as well
         const long long g = tb_acc[tid], b = tb_acc[TM_H + tid];
@@ -1242,7 +1169,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
 // tile (counted in TILES, cnt S per bucket, whatever the buckets' work items are); a live tile's workgroup leaves at once.  Zeros wherever the
 // tile's live form writes: the save / save_in rows and relu' bits, rs_out, the rows or values of the storing tails.  A chain tail
 // that adds has nothing to add; Filter's sum (SUM_ROWS) belongs to the live segments -- a clip of no frames at all gets its zero here.
-template <int KIND>
+template <TileKind KIND>
 __global__ __launch_bounds__(512) void tile_split_pad_kernel(TmParams pp) {
     int tile = blockIdx.x, b = 0;
     while (b + 1 < pp.nb && tile >= pp.a[b].cnt * pp.a[b].pack) { tile -= pp.a[b].cnt * pp.a[b].pack; ++b; }
@@ -1261,15 +1188,15 @@ __global__ __launch_bounds__(512) void tile_split_pad_kernel(TmParams pp) {
             *reinterpret_cast<v4f *>(base + (int64_t)t * TM_H + 256 + 4 * lane) = z4;
         }
     };
-    if (KIND >= 2 && p.save_in) zero_rows(p.save_in + row0 * TM_H);
+    if (KIND != KIND_FWD && p.save_in) zero_rows(p.save_in + row0 * TM_H);
     for (int l = 0; l < p.n_layers; ++l) {
         if (p.save[l]) zero_rows(p.save[l] + row0 * TM_H);
-        if (KIND == 0 && p.save_bits[l]) p.save_bits[l][(int64_t)tile * TM_H + tid] = 0ull;
+        if (KIND == KIND_FWD && p.save_bits[l]) p.save_bits[l][(int64_t)tile * TM_H + tid] = 0ull;
     }
     const int oraw = p.out_idx ? p.out_idx[ii] : ii;
-    const int64_t oslot = KIND >= 2 ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
-    if (KIND >= 2) {
-        const bool stores = (KIND == 2 || p.tail == STAIR_TILE_ACCUMULATE) ? (oraw & STAIR_TILE_STORE_FIRST) != 0 : p.tail == STAIR_TILE_STORE;
+    const int64_t oslot = KIND != KIND_FWD ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
+    if (KIND != KIND_FWD) {
+        const bool stores = (KIND == KIND_TEMPORAL_BWD || p.tail == STAIR_TILE_ACCUMULATE) ? (oraw & STAIR_TILE_STORE_FIRST) != 0 : p.tail == STAIR_TILE_STORE;
         if (stores) zero_rows(p.out + oslot * p.out_gstride + (int64_t)sfr0 * TM_H);
         return;
     }
@@ -1369,48 +1296,44 @@ bool tile_mlp_usable(int H, int T) {
     return on && H == TM_H && T >= 1 && T <= (g_tile_split.on() ? kTileSplitMaxFrames : TM_ROWS) && matmul_mode() == STAIR_MATMUL_BF16X3;
 }
 
-// Which kernel form a bucket runs (the KIND of tile_mlp_kernel): 3 a map-level backward chain, 1 vector-level tiles, 2 Temporal's
-// backward chain, 0 a map-level forward operator.  in_mask and save_in are chain options except under ln_bwd, whose own they are.
-// An argument set that names a chain option AND vec_pack / ln_bwd is a chain here, and tile_mlp_check refuses it as one.
-static int tile_kind(const stair_tile_mlp_args &a) {
+// Which kernel form a bucket runs: a map-level backward chain, Temporal's backward chain, or a map-level forward operator.
+// in_mask and save_in are chain options except under ln_bwd, whose own they are.
+// An argument set that names a chain option AND ln_bwd is a chain here, and tile_mlp_check refuses it as one.
+static TileKind tile_kind(const stair_tile_mlp_args &a) {
     bool chain = a.tail == STAIR_TILE_ACCUMULATE || a.in_bits || a.x_broadcast || (!a.ln_bwd && (a.in_mask || a.save_in));
     for (int l = 0; l < a.n_layers && l < 3; ++l) chain = chain || a.act[l] == 3;
-    return chain ? 3 : a.vec_pack ? 1 : a.ln_bwd ? 2 : 0;
+    return chain ? KIND_CHAIN : a.ln_bwd ? KIND_TEMPORAL_BWD : KIND_FWD;
 }
 
 // split: the launch runs the SPLIT form (one of its buckets has T > 64); a bucket of T <= 64 in it is one segment per instance.
 // Else short clips share a tile while pack_on: P = 64 / T instances whenever T <= 32.  The caller's cnt counts INSTANCES either way.
-static TileGeom tile_geom(int kind, const stair_tile_mlp_args &a, bool pack_on, bool split) {
+static TileGeom tile_geom(TileKind kind, const stair_tile_mlp_args &a, bool pack_on, bool split) {
     TileGeom g;
     g.S = split && a.T > TM_ROWS ? (a.T + TM_ROWS - 1) / TM_ROWS : 1;
-    g.P = !split && kind != 1 && pack_on && a.T >= 1 && a.T <= TM_ROWS / 2 ? TM_ROWS / a.T : 1;
+    g.P = !split && pack_on && a.T >= 1 && a.T <= TM_ROWS / 2 ? TM_ROWS / a.T : 1;
     g.tiles = split ? (int64_t)a.cnt * g.S : (a.cnt + g.P - 1) / g.P;
-    g.walk = split && kind == 0 && a.tail == STAIR_TILE_SUM_ROWS;
+    g.walk = split && kind == KIND_FWD && a.tail == STAIR_TILE_SUM_ROWS;
     g.items = g.walk ? a.cnt : (int)g.tiles;
     return g;
 }
 static stair_tile_mlp_args tile_frames(int cnt, int T) { stair_tile_mlp_args a = {}; a.cnt = cnt; a.T = T; return a; }
 // the most tiles a pass may run a map-level bucket as: nothing packed, segments whenever the clips are long
-int64_t tile_max_tiles(int cnt, int T) { return tile_geom(0, tile_frames(cnt, T), false, T > TM_ROWS).tiles; }
+int64_t tile_max_tiles(int cnt, int T) { return tile_geom(KIND_FWD, tile_frames(cnt, T), false, T > TM_ROWS).tiles; }
 
 // the kernel of every form, [plain / packed / split][KIND], and the pad kernel that goes ahead of a split form's ragged launches
-// (a table of its own, behind the other: the code object lists its kernels in the order they are first named).  The tile's own
-// traffic carries the non-temporal hint (NT) in every form but the vector-level one: with the first version of the kernel plain
-// accesses were faster (saves 273 -> 290 us per 1024 tiles); now that a layer is bound by the weight stream from L2, keeping the
-// streamed tiles from displacing the weight planes pays: 17.02 -> 16.89 ms per 2048-question step (three A/B pairs on one box),
-// neutral at 128 questions and in inference.
+// (a table of its own, behind the other: the code object lists its kernels in the order they are first named)
 enum { TF_PLAIN = 0, TF_PACKED = 1, TF_SPLIT = 2 };
 using TileKernel = void (*)(TmParams);
-static const TileKernel kTileKernels[3][4] = {
-    {tile_mlp_kernel<true, 0>, tile_mlp_kernel<false, 1>, tile_mlp_kernel<true, 2>, tile_mlp_kernel<true, 3>},
-    {tile_mlp_kernel<true, 0, true>, nullptr, tile_mlp_kernel<true, 2, true>, tile_mlp_kernel<true, 3, true>},
-    {tile_mlp_kernel<true, 0, false, true>, nullptr, tile_mlp_kernel<true, 2, false, true>, tile_mlp_kernel<true, 3, false, true>}};
-static const TileKernel kTileSplitPads[4] = {tile_split_pad_kernel<0>, nullptr, tile_split_pad_kernel<2>, tile_split_pad_kernel<3>};
+static const TileKernel kTileKernels[3][KIND_COUNT] = {
+    {tile_mlp_kernel<KIND_FWD>, tile_mlp_kernel<KIND_TEMPORAL_BWD>, tile_mlp_kernel<KIND_CHAIN>},
+    {tile_mlp_kernel<KIND_FWD, true>, tile_mlp_kernel<KIND_TEMPORAL_BWD, true>, tile_mlp_kernel<KIND_CHAIN, true>},
+    {tile_mlp_kernel<KIND_FWD, false, true>, tile_mlp_kernel<KIND_TEMPORAL_BWD, false, true>, tile_mlp_kernel<KIND_CHAIN, false, true>}};
+static const TileKernel kTileSplitPads[KIND_COUNT] = {tile_split_pad_kernel<KIND_FWD>, tile_split_pad_kernel<KIND_TEMPORAL_BWD>, tile_split_pad_kernel<KIND_CHAIN>};
 
 static int tile_mlp_check(const stair_tile_mlp_args &a) {
     STAIR_CHECK(a.H == TM_H, "the fused tile operators are built for hidden_size 512");
     STAIR_CHECK(a.n_layers >= 1 && a.n_layers <= 3, "1..3 layers");
-    if (a.vec_pack) {                     // vector-level modules: 64 instances per tile
+    if (a.vec_pack) {                     // the retired vector-level form (64 instances per tile): its fields are still checked, then refused below
         STAIR_CHECK(a.vec_pack >= 1 && a.vec_pack <= 3, "vec_pack: 1 [a, b], 2 [|a - b|, a, b], 3 [a, b, a * b]");
         STAIR_CHECK(a.pk_a && a.pk_b && a.vec_cnt >= 0 && a.cnt == (a.vec_cnt + TM_ROWS - 1) / TM_ROWS, "vector operands / cnt = ceil(vec_cnt / 64)");
         STAIR_CHECK(((reinterpret_cast<uintptr_t>(a.pk_a) | reinterpret_cast<uintptr_t>(a.pk_b) | reinterpret_cast<uintptr_t>(a.cat_save)) & 15) == 0, "vector operands must be 16-byte aligned");
@@ -1435,7 +1358,7 @@ static int tile_mlp_check(const stair_tile_mlp_args &a) {
         STAIR_CHECK(a.W[l] && (reinterpret_cast<uintptr_t>(a.W[l]) & 15) == 0, "weight planes (stair_pack_wfrag) missing or unaligned");
     for (int l = 0; l < a.n_layers; ++l) STAIR_CHECK(a.act[l] != 3 || a.act_mask[l] || a.act_bits[l], "act 3 multiplies by relu'(act_mask[l]) (or its bits, act_bits[l])");
     STAIR_CHECK(!(a.in_mask && a.in_bits), "in_mask or in_bits, not both");
-    if (tile_kind(a) == 3) {    // the backward chains are a kernel of their own: chain options do not mix with the forward operators' options
+    if (tile_kind(a) == KIND_CHAIN) {    // the backward chains are a kernel of their own: chain options do not mix with the forward operators' options
         STAIR_CHECK(!a.vec_pack && !a.ln_bwd, "chain options (act 3, in_mask, in_bits, x_broadcast, save_in, ACCUMULATE) are map-level");
         STAIR_CHECK(a.tail == STAIR_TILE_ACCUMULATE || a.tail == STAIR_TILE_STORE || a.tail == STAIR_TILE_NONE, "a backward chain ends in ACCUMULATE, STORE or NONE");
         STAIR_CHECK(!a.row_scale && !a.mid_rowdot && !a.save_bits[0] && !a.save_bits[1] && !a.save_bits[2], "a backward chain takes no row_scale / mid_rowdot / save_bits");
@@ -1458,6 +1381,8 @@ static int tile_mlp_check(const stair_tile_mlp_args &a) {
         case STAIR_TILE_NONE: break;
         default: STAIR_FAIL("unknown tail");
     }
+    // (last, so that a malformed set of the retired form is still refused with the message it always got)
+    STAIR_CHECK(!a.vec_pack, "the vector-level form of the tile operator is retired (ABI 7): stair_vec_group runs these modules");
     return 0;
 }
 
@@ -1475,19 +1400,18 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
     if (!attr_set[dev]) {
         for (const auto &forms : kTileKernels)
             for (TileKernel k : forms)
-                if (k) STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
+                STAIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS));
         int v = 256;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         cus[dev] = v;
         attr_set[dev] = true;
     }
-    auto rounds = [&](int x) { return args[x].n_layers + (args[x].vec_pack ? (args[x].vec_pack == 1 ? 1 : 2) : 0); };   // k loops per tile
     // decided here for the whole call
     const bool pack_on = g_tile_pack.on();
-    // map-level tiles, vector-level tiles, Temporal's backward chains and the map-level chains are four kernels (what one form needs
-    // in registers the others do not pay for): one launch per form a level has; stream-ordered, so they share the (self-resetting)
-    // queue words
-    for (int kind = 0; kind < 4; ++kind) {
+    // map-level tiles, Temporal's backward chains and the map-level chains are three kernels (what one form needs in registers the
+    // others do not pay for): one launch per form a level has; stream-ordered, so they share the (self-resetting) queue words
+    for (int k = 0; k < KIND_COUNT; ++k) {
+        const TileKind kind = static_cast<TileKind>(k);
         TmParams pp;
         pp.nb = 0; pp.counter = counter; pp.first[0] = 0; pp.fx_g = pp.fx_b = nullptr;
         pp.drop_thresh = 0; pp.drop_inv_keep = 1.0f; pp.drop_seed = 0;
@@ -1495,13 +1419,13 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
         for (int i = 0; i < n; ++i)
             if (args[i].cnt > 0 && tile_kind(args[i]) == kind) order[m++] = i;
         if (m == 0) continue;
-        if (kind == 2) {            // one accumulator pair per workgroup: the chains of a launch share their LayerNorm
+        if (kind == KIND_TEMPORAL_BWD) {            // one accumulator pair per workgroup: the chains of a launch share their LayerNorm
             for (int j = 1; j < m; ++j)
                 STAIR_CHECK(args[order[j]].dgamma == args[order[0]].dgamma && args[order[j]].dbeta == args[order[0]].dbeta,
                             "the Temporal chains of one launch must share dgamma / dbeta");
             pp.fx_g = det_shadow(args[order[0]].dgamma); pp.fx_b = det_shadow(args[order[0]].dbeta);
         }
-        if (kind == 0) {            // dropout behind the activations of a forward launch: one probability and seed per launch
+        if (kind == KIND_FWD) {            // dropout behind the activations of a forward launch: one probability and seed per launch
             for (int j = 0; j < m; ++j) {
                 const stair_tile_mlp_args &a = args[order[j]];
                 if (!(a.drop_p > 0.0f) || !(a.drop_site[0] | a.drop_site[1] | a.drop_site[2])) continue;
@@ -1512,11 +1436,11 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
                 pp.drop_thresh = th; pp.drop_inv_keep = 1.0f / (1.0f - a.drop_p); pp.drop_seed = a.drop_seed;
             }
         }
-        std::stable_sort(order, order + m, [&](int x, int y) { return rounds(x) > rounds(y); });    // long tiles first
+        std::stable_sort(order, order + m, [&](int x, int y) { return args[x].n_layers > args[y].n_layers; });    // long tiles (more k loops) first
         // clips of more than 64 frames (admitted by tile_mlp_check only while the segment switch is on) run as segments: the SPLIT
         // form for the whole launch
         bool packed = false, split = false, any_len = false;
-        for (int j = 0; j < m; ++j) split = split || (kind != 1 && args[order[j]].T > TM_ROWS);
+        for (int j = 0; j < m; ++j) split = split || args[order[j]].T > TM_ROWS;
         int64_t tiles = 0;
         for (int j = 0; j < m; ++j) {
             const stair_tile_mlp_args &a = args[order[j]];
@@ -1526,8 +1450,8 @@ int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *coun
             pp.a[j] = tm_arg(a, kind, g);
             pp.first[j + 1] = pp.first[j] + g.items;
             tiles += g.tiles;
-            const int64_t M = a.vec_pack ? a.vec_cnt : (int64_t)a.cnt * a.T;
-            const int kl = rounds(order[j]);
+            const int64_t M = (int64_t)a.cnt * a.T;
+            const int kl = a.n_layers;
             STAIR_ACCT_MFMA("tile_mlp", (M * TM_H * 2 + (int64_t)kl * TM_H * TM_H) * 4, 2 * M * TM_H * TM_H * kl);
         }
         for (int j = m; j < TM_MAXB; ++j) { pp.a[j] = pp.a[0]; pp.first[j + 1] = pp.first[m]; }
@@ -1561,11 +1485,11 @@ extern "C" int stair_set_tile_mlp(int32_t on) { stair::g_tile_on = on; return 0;
 
 extern "C" int stair_set_tile_pack(int32_t on) { stair::g_tile_pack.set_process(on); return 0; }
 
-extern "C" int32_t stair_tile_pack_factor(int32_t T) { return stair::tile_geom(0, stair::tile_frames(0, T), stair::g_tile_pack.process != 0, false).P; }
+extern "C" int32_t stair_tile_pack_factor(int32_t T) { return stair::tile_geom(stair::KIND_FWD, stair::tile_frames(0, T), stair::g_tile_pack.process != 0, false).P; }
 
 extern "C" int stair_set_tile_split(int32_t on) { stair::g_tile_split.set_process(on); return 0; }
 
-extern "C" int32_t stair_tile_segments(int32_t T) { return stair::tile_geom(0, stair::tile_frames(0, T), false, stair::g_tile_split.process != 0).S; }
+extern "C" int32_t stair_tile_segments(int32_t T) { return stair::tile_geom(stair::KIND_FWD, stair::tile_frames(0, T), false, stair::g_tile_split.process != 0).S; }
 
 extern "C" int stair_tile_work_items(int64_t *items, int32_t reset) {
     const int64_t v = reset ? stair::g_tile_work_items.exchange(0) : stair::g_tile_work_items.load();
@@ -1589,17 +1513,6 @@ extern "C" int stair_pack_wfrag(const float *W, void *planes, int32_t N, int32_t
     const float *w[1] = {W};
     void *o[1] = {planes};
     return stair::launch_pack_wfrag_many(w, o, 1, N, K, static_cast<hipStream_t>(stream), transpose != 0);
-}
-
-extern "C" int stair_pack_wfrag_ld(const float *W, int64_t ld, void *planes, int32_t N, int32_t K, stair_stream stream) {
-    if (!W || !planes) {
-        stair::set_error("stair_pack_wfrag_ld: null argument");
-        return 1;
-    }
-    const float *w[1] = {W};
-    void *o[1] = {planes};
-    const int l[1] = {(int)ld};
-    return stair::launch_pack_wfrag_many(w, o, 1, N, K, static_cast<hipStream_t>(stream), false, l);
 }
 
 extern "C" int stair_tile_timing(int32_t on) {

@@ -15,7 +15,7 @@ FAKE = C.c_void_p(256)             # aligned, non-null; never dereferenced becau
 def test_dlogits_backward_is_exported_and_bound():
     assert hasattr(lib, 'stair_plan_backward_dlogits')
     assert 'stair_plan_backward_dlogits' in {name for name, _, _ in _lib.SIGNATURES}
-    assert lib.stair_abi_version() == 6
+    assert lib.stair_abi_version() == 7
 
 
 def test_autograd_module_imports():

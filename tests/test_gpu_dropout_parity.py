@@ -22,7 +22,6 @@ One HIP pass and one oracle pass per configuration, shared by its checks.  Each 
 DROPOUT: (DESIGN.md section 4 has the table)."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -44,16 +43,16 @@ SITE_KINDS = {'ToAction.param.0', 'HasItem.param.0', 'HasItem.param.3', 'Exists.
               'FilterFrame.param.0', 'FilterFrame.param.3', 'FilterFrame.dense.0', 'decoder.0'}
 UNDROPPED = {'Superlative', 'Filter', 'Compare', 'Equals', 'Xor', 'ToAction'}       # outputs with a ReLU and no nn.Dropout behind it
 
-# name -> (config, T or per-form clip lengths, matmul mode, stair_set_tile_mlp, STAIR_TILE_VEC, oracle dtype)
+# name -> (config, T or per-form clip lengths, matmul mode, stair_set_tile_mlp, oracle dtype)
 CONFIGS = {
-    'full_fused': (dict(spec.DEFAULT_CONFIG), 64, 'bf16x3', -1, '1', torch.float64),
-    'full_fused_ragged': (dict(spec.DEFAULT_CONFIG), RAGGED_LENS, 'bf16x3', -1, '1', torch.float64),
-    'full_sequenced': (dict(spec.DEFAULT_CONFIG), 64, 'bf16x3', 0, None, torch.float64),
-    'tiny_conv_f32': (dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, max_video_length=64, **TINY), 40, 'f32', -1, None, torch.float64),
-    'tiny_conv_bf16x3': (dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, max_video_length=64, **TINY), 40, 'bf16x3', -1, None, torch.float64),
-    'tiny_linear_f32': (dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, max_video_length=24, **TINY), 24, 'f32', -1, None, torch.float64),
-    'tiny_linear_bf16x3': (dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, max_video_length=24, **TINY), 24, 'bf16x3', -1, None, torch.float64),
-    'h320_f32': (dict(spec.DEFAULT_CONFIG, hidden_size=320, video_size=128, max_video_length=40, **TINY), 33, 'f32', -1, None, torch.float64),
+    'full_fused': (dict(spec.DEFAULT_CONFIG), 64, 'bf16x3', -1, torch.float64),
+    'full_fused_ragged': (dict(spec.DEFAULT_CONFIG), RAGGED_LENS, 'bf16x3', -1, torch.float64),
+    'full_sequenced': (dict(spec.DEFAULT_CONFIG), 64, 'bf16x3', 0, torch.float64),
+    'tiny_conv_f32': (dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, max_video_length=64, **TINY), 40, 'f32', -1, torch.float64),
+    'tiny_conv_bf16x3': (dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, max_video_length=64, **TINY), 40, 'bf16x3', -1, torch.float64),
+    'tiny_linear_f32': (dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, max_video_length=24, **TINY), 24, 'f32', -1, torch.float64),
+    'tiny_linear_bf16x3': (dict(spec.DEFAULT_CONFIG, hidden_size=64, video_size=128, max_video_length=24, **TINY), 24, 'bf16x3', -1, torch.float64),
+    'h320_f32': (dict(spec.DEFAULT_CONFIG, hidden_size=320, video_size=128, max_video_length=40, **TINY), 33, 'f32', -1, torch.float64),
 }
 
 
@@ -171,11 +170,8 @@ def _run(name):
     forward under the next seed -- shared by the checks below."""
     from stair_amd import ops
     from stair_amd._lib import lib
-    config, T, matmul, tile_mlp, tile_vec, dtype = CONFIGS[name]
+    config, T, matmul, tile_mlp, dtype = CONFIGS[name]
     qs = _questions(config, T)
-    old_vec = os.environ.get('STAIR_TILE_VEC')
-    if tile_vec is not None:
-        os.environ['STAIR_TILE_VEC'] = tile_vec
     ops.set_matmul_mode(matmul)
     lib.stair_set_tile_mlp(tile_mlp)
     try:
@@ -205,11 +201,6 @@ def _run(name):
     finally:
         lib.stair_set_tile_mlp(-1)
         ops.set_matmul_mode('bf16x3')
-        if tile_vec is not None:
-            if old_vec is None:
-                del os.environ['STAIR_TILE_VEC']
-            else:
-                os.environ['STAIR_TILE_VEC'] = old_vec
     return out
 
 

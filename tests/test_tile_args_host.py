@@ -36,6 +36,8 @@ REFUSED = [
     ('vec_save_bits', dict(VEC, save_bits=(P[5],)), 'bit masks are a map-level option', 1),
     ('vec_act_bits', dict(VEC, act_bits=(P[5],)), 'act_bits belong to act 3', 1),
     ('vec_no_out', dict(VEC, out_row_idx=None), 'row-scatter tail: out, out_row_idx', 1),
+    # ... and a well-formed set of the retired form is refused last of all
+    ('vec_retired', dict(VEC), 'the vector-level form of the tile operator is retired (ABI 7): stair_vec_group runs these modules', 1),
     ('no_frames', dict(MAP, T=0), 'a tile holds 1..64 frames', 1),
     ('T65_split_off', dict(MAP, T=65, x_gstride=65 * 512), 'a tile holds 1..64 frames', 0),
     ('T142', dict(MAP, T=142, x_gstride=142 * 512), 'the tile operators take clips of at most 141 frames (64-row segments)', 1),
