@@ -100,6 +100,25 @@ int stair_ctx_set_weight(stair_ctx *ctx, int id, const float *dev_ptr, int64_t n
 /* Gradient buffer of weight `id` (same shape), needed only for stair_plan_backward; gradients are ACCUMULATED
  * into it, the caller zeroes it (optimizer.zero_grad(), train_module.py:411). */
 int stair_ctx_set_grad(stair_ctx *ctx, int id, float *dev_ptr, int64_t numel);
+/* Frozen weights (requires_grad = False in torch).  Every weight is trainable (1) when the context is created; on = 0 freezes weight
+ * `id` for every reverse pass from then on, on != 0 thaws it again.  For a frozen weight
+ *   - stair_plan_touched reports 0, so an optimizer that goes by that mask (stair_adam_step) leaves weight and moments alone;
+ *   - stair_plan_backward / stair_plan_backward_dlogits leave its bound gradient buffer untouched, bit for bit (it need not be
+ *     bound at all).  Where one launch produces a frozen and a trainable output together -- a Linear's dW beside its db -- the
+ *     frozen one goes to a discard region of the plan's workspace ("discard" in stair_plan_regions), which nothing reads;
+ *   - work that only it needed is not launched: a weight-gradient product whose outputs are all frozen; an encoder's whole block
+ *     (reverse recurrence, dW_ih / dW_hh / bias products, the fan-in into its clip tiles) when its eight tensors are frozen and
+ *     its input gradient (d_video / d_question) is not requested -- the other encoder's recurrence then runs alone; and, when no
+ *     weight the plan uses outside the decoder is trainable, no input gradient is requested and STAIR_BWD_KEEP_ARENAS is not set,
+ *     everything behind the decoder's own weight gradients: the arenas are not cleared and no program level is walked.
+ *     A requested input gradient overrides the skip: BPTT runs, the input gradient is produced, the weight products are dropped.
+ *     On the fused H = 512 path, while the video encoder's block is left out, the backward chains whose input tiles are all clip
+ *     tiles end in front of their last product (STAIR_TILE_NO_DX below): the gradient of a clip tile has no reader then.
+ * The stair_loss_* head weights follow the same rule on the caller's side: pass dW / db = NULL for a frozen head; d_vec / d_map are
+ * still injected.  Gradients of the trainable weights are those of the unfrozen pass, bit for bit.  Data-parallel training: the
+ * frozen set must be the same on every rank (the ranks exchange one bucket laid out by weight id; this is not checked). */
+int stair_ctx_set_trainable(stair_ctx *ctx, int id, int32_t on);
+int stair_ctx_get_trainable(const stair_ctx *ctx, int id, int32_t *on);
 
 /* Arithmetic of the large contractions (process-wide; default from the environment variable STAIR_MATMUL =
  * "f32" | "bf16x3" | "bf16", else bf16x3):
@@ -379,6 +398,13 @@ typedef struct stair_tile_mlp_args {
      * tile receives and that the tile was NOT cleared: the T rows are stored and the tile is not read (the slot is the entry without
      * the bit).  A stored row holds what the add would have left in a zeroed tile (-0 where that gave +0). */
 #define STAIR_TILE_STORE_FIRST 0x40000000
+    /* Backward chains (act 3 / in_mask / in_bits / x_broadcast / save_in launches; not the ln_bwd form): bit STAIR_TILE_NO_DX of out_idx[i]
+     * says that nobody reads the gradient of instance i's input tile: the chain's LAST product (dX = dZ W of the first forward layer) and
+     * its tail are not computed and the output tile is neither read nor written; every save before it (save_in, save[l]) is written as
+     * always.  The decision is per workgroup: an unpacked tile or a segment is one instance; a packed tile drops the product only when
+     * every instance it holds carries the bit (otherwise it is computed and added for all of them: the slot is the entry without the
+     * bit).  stair_plan_backward sets it on clip tiles while the video encoder's block is left out (stair_ctx_set_trainable). */
+#define STAIR_TILE_NO_DX 0x20000000
     /* relu' of a saved activation as ONE bit per element (4 KB per tile instead of a 128 KB read in the backward chain):
      *   save_bits[l]     [cnt][512] 64-bit words, written by a forward launch: word (i, 64 w + c), byte j, bit e = (layer l's
      *                    activation of TILE i, row w + 8 j, column 8 c + e) > 0.  Unpacked, tile i is instance i; a packed launch
@@ -747,7 +773,9 @@ int stair_plan_run_flags(stair_ctx *ctx, stair_plan *plan, const float *video, c
  * +-inf contribution, or one of whose contributions (a workgroup's partial sum) or whose sum of the pass has magnitude >= 2^18, comes
  * out NON-FINITE (NaN) -- never finite and wrong -- so stair_grad_norm's guard sees it; elements inside the range are bit for bit what
  * they would be without the checks.  (A sum of in-range contributions is caught as long as the true sum stays inside +-(2^20 - 2^18):
- * the 64-bit sum wraps at 2^20 gradient units.)  With STAIR_DETERMINISTIC=0 the sums are float atomics, with float's range. */
+ * the 64-bit sum wraps at 2^20 gradient units.)  With STAIR_DETERMINISTIC=0 the sums are float atomics, with float's range.
+ * Frozen weights (stair_ctx_set_trainable): their buffers are not written and the work only they needed is not launched, see there;
+ * the gradients of the trainable weights do not change by a bit. */
 int stair_plan_backward(stair_ctx *ctx, stair_plan *plan, const float *video, const float *question,
                         void *workspace, int64_t workspace_bytes, const int32_t *answers, float loss_scale,
                         float *loss_out, int32_t flags, stair_stream stream);
@@ -855,7 +883,8 @@ int stair_loss_filterframe_len(const float *map, float *d_map, const int32_t *sl
 int stair_plan_regions(stair_plan *plan, const stair_ctx *ctx, const char **names, int64_t *beg, int64_t *end, int32_t cap);
 
 /* touched[id] = 1 iff weight `id` receives a gradient from this plan (host array, count = stair_weight_count).
- * Parameters of modules that no program used keep grad == None in the reference and are skipped by Adam. */
+ * Parameters of modules that no program used keep grad == None in the reference and are skipped by Adam.  A frozen weight
+ * (stair_ctx_set_trainable) reports 0 whatever the programs use: what torch does with requires_grad = False. */
 int stair_plan_touched(const stair_ctx *ctx, const stair_plan *plan, int32_t *touched, int32_t count);
 
 /* torch.optim.Adam (train_module.py:326) over a flat fp32 parameter buffer of n floats.  Parameter tensors

@@ -133,6 +133,8 @@ SIGNATURES = [
     ('stair_weight_numel', C.c_int64, [C.c_void_p, C.c_int]),
     ('stair_ctx_set_weight', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ('stair_ctx_set_grad', C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    ('stair_ctx_set_trainable', C.c_int, [C.c_void_p, C.c_int, C.c_int32]),
+    ('stair_ctx_get_trainable', C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
     ('stair_set_matmul_mode', C.c_int, [C.c_int32]),
     ('stair_get_matmul_mode', C.c_int, []),
     ('stair_set_split_min_rows', C.c_int, [C.c_int32]),

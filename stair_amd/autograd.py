@@ -9,7 +9,10 @@ Semantics:
 
 * the parameters are INPUTS of the Function: their gradients go back through autograd, so ``torch.autograd.grad``, hooks and
   ``.grad`` accumulation over several ``backward()`` calls behave as for any module.  Parameters that no program of the batch uses
-  (``stair_plan_touched``) get ``None``, as unused modules do in the reference (train_module.py:408-410);
+  (``stair_plan_touched``) get ``None``, as unused modules do in the reference (train_module.py:408-410), and so do parameters
+  with ``requires_grad = False``: the forward call hands the flags to the context (``VideoNMN._sync_trainable``), and the reverse
+  pass then launches nothing that only they needed -- a frozen encoder costs no BPTT unless ``video`` / ``question`` asks for its
+  input gradient;
 * every differentiable call owns its workspace and projection buffer until its backward has run (the model's shared buffers are
   rewritten by the next batch), so several outstanding forwards may go backward together; the buffers are released afterwards;
 * a batch goes backward ONCE: BPTT overwrites the saved gates with their gradients.  A second backward through the same logits

@@ -177,6 +177,7 @@ int launch_lstm_recur(const stair_lstm_args &a, hipStream_t s);
 int launch_lstm_zero_tail(const stair_lstm_args &a, hipStream_t s);
 int launch_lstm_bwd_recur(const stair_lstm_bwd_args &a, hipStream_t s);
 int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, hipStream_t s);
+int launch_lstm_bwd_clear_tail(const stair_lstm_bwd_args &a, hipStream_t s);
 bool lstm_bwd_takes_coop(const stair_lstm_bwd_args &a);
 int64_t lstm_coop_bwd_ws_bytes(int n);
 int launch_gemm_bf16x3(const stair_gemm_args &a, hipStream_t s);

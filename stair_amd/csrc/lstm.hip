@@ -927,6 +927,17 @@ int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, hipStream_t s) {
     return 0;
 }
 
+// What is left of launch_lstm_bwd_weights when no weight gradient is wanted (a frozen encoder whose input gradient is): with padded
+// storage the gate-gradient rows past a sequence's length are cleared -- the input-gradient product runs over all rows -- and
+// nothing is copied (row_begin = rows)
+int launch_lstm_bwd_clear_tail(const stair_lstm_bwd_args &a, hipStream_t s) {
+    if (a.n == 0 || a.rows == 0 || !a.seq_len) return 0;
+    hipLaunchKernelGGL(lstm_hprev_kernel, dim3(a.n, (a.max_len + 7) / 8), dim3(256), 0, s, a.out, a.ldo, a.seq_off, a.seq_len, a.n, a.Hh, a.hprev_ws,
+                       a.gates, a.rows);
+    STAIR_LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_lstm_bwd(const stair_lstm_bwd_args &a, hipStream_t s) {
     if (int rc = launch_lstm_bwd_recur(a, s)) return rc;
     return launch_lstm_bwd_weights(a, s);

@@ -52,6 +52,7 @@ struct stair_ctx {
     std::vector<int64_t> numel;
     std::vector<const float *> ptr;
     std::vector<float *> gptr;           // gradient buffers (training), same ids
+    std::vector<char> trainable;         // stair_ctx_set_trainable: 0 = frozen (no gradient, no update, no work that only it needed); default 1
     std::unordered_map<std::string, int> by_name;
     // 64-bit fixed-point shadows of the weight gradients (common.h det_shadow): owned by the context, all zero between two backward
     // passes (the flush empties what it adds), so a pass does not start by clearing 8 bytes per parameter; `dirty`: a pass that did not
@@ -70,6 +71,7 @@ struct stair_ctx {
         numel.push_back(n);
         ptr.push_back(nullptr);
         gptr.push_back(nullptr);
+        trainable.push_back(1);
     }
     void lin(const std::string &prefix, int64_t out, int64_t in) {
         add(prefix + ".weight", out * in);
@@ -209,6 +211,19 @@ extern "C" int stair_ctx_set_grad(stair_ctx *ctx, int id, float *dev_ptr, int64_
     STAIR_CHECK(numel == ctx->numel[id], "numel mismatch for " + ctx->names[id]);
     STAIR_CHECK(dev_ptr && (reinterpret_cast<uintptr_t>(dev_ptr) & 15) == 0, "gradient pointer must be 16-byte aligned: " + ctx->names[id]);
     ctx->gptr[id] = dev_ptr;
+    return 0;
+}
+
+extern "C" int stair_ctx_set_trainable(stair_ctx *ctx, int id, int32_t on) {
+    STAIR_CHECK(ctx, "null ctx");
+    STAIR_CHECK(id >= 0 && id < (int)ctx->names.size(), "weight id out of range");
+    ctx->trainable[id] = on != 0;
+    return 0;
+}
+extern "C" int stair_ctx_get_trainable(const stair_ctx *ctx, int id, int32_t *on) {
+    STAIR_CHECK(ctx && on, "null argument");
+    STAIR_CHECK(id >= 0 && id < (int)ctx->names.size(), "weight id out of range");
+    *on = ctx->trainable[id];
     return 0;
 }
 
@@ -407,6 +422,10 @@ struct Bucket {
     // (mark_store_first); empty / -1 where the bucket has no such entry
     std::vector<int32_t> scol;
     int64_t soff = -1;
+    // gcol[0] with STAIR_TILE_NO_DX on every entry, for a chain bucket ALL of whose input tiles are clip tiles: what its tail gets
+    // instead while the video encoder's block is left out of the pass (nobody reads a clip tile's gradient then)
+    std::vector<int32_t> ncol;
+    int64_t noff = -1;
     // float offsets of this bucket's intermediates.  Inference: all buckets share one scratch set;
     // training: private regions, kept until stair_plan_backward has consumed them.
     int64_t svA = 0, svB = 0, svK = 0, svCat = 0, svHid = 0, svRs = 0, svSup = 0, svExtra = 0;
@@ -722,6 +741,7 @@ struct stair_plan {
     int64_t o_cv = 0, o_ct = 0, o_hprev = 0, o_gblock = 0, o_gatt = 0, o_gtok = 0, o_gqfeat = 0, o_gA = 0, o_gB = 0,
             o_gK = 0, o_gV0 = 0, o_gV1 = 0, o_gCat = 0, o_gS = 0, o_gRs = 0, o_gRs2 = 0, o_gExtra = 0, o_gStats = 0,
             o_wt = 0, o_dlogits = 0, o_loss = 0, o_zero_beg = 0, o_zero_end = 0, o_wfragT = 0;
+    int64_t o_discard = 0;          // where a reverse pass sends the gradient of a frozen weight (stair_ctx_set_trainable): never read
 };
 
 namespace {
@@ -791,6 +811,18 @@ void mark_store_first(stair_plan *pl, const std::vector<GEdge> &E) {
     pl->clear_tiles.clear();
     for (int t = 0; t < n_targets; ++t)
         if (!stored[t]) pl->clear_tiles.push_back(t);
+    // chains whose input gradient only the video encoder would read (Temporal's chain is not among them: its last product also
+    // feeds the gradient of the per-frame scale)
+    for (Bucket &b : pl->buckets) {
+        b.ncol.clear(); b.noff = -1;
+        if (b.cnt == 0 || !runs_chain(b) || b.op == STAIR_OP_TEMPORAL || b.gcol[0].size() != b.col[0].size() || b.col[0].empty()) continue;
+        bool clips = true;
+        for (int32_t slot : b.col[0]) clips = clips && slot >= 0 && slot < pl->n_vid;
+        for (int32_t target : b.gcol[0]) clips = clips && target >= 0 && target < STAIR_TILE_NO_DX;
+        if (!clips) continue;
+        b.ncol = b.gcol[0];
+        for (int32_t &target : b.ncol) target |= STAIR_TILE_NO_DX;
+    }
 }
 
 // vec_fix: where a vec-arena staging index was written with the provisional numbering n_vec + j; the layout pass moves the vec staging
@@ -1222,7 +1254,7 @@ int build_index_image(stair_plan *pl, const int32_t *q_off) {
     for (Bucket &b : pl->buckets)
         for (int c = 0; c < 8; ++c) idx_ints += align_up((int64_t)b.col[c].size(), 4) + align_up((int64_t)b.gcol[c].size(), 4);
     if (pl->train) {
-        for (const Bucket &b : pl->buckets) idx_ints += align_up((int64_t)b.scol.size(), 4);
+        for (const Bucket &b : pl->buckets) idx_ints += align_up((int64_t)b.scol.size(), 4) + align_up((int64_t)b.ncol.size(), 4);
         idx_ints += align_up((int64_t)pl->clear_tiles.size(), 4);
         // token row -> the spans that average over it (their gradient reaches the row by a gather in span order: no atomics)
         pl->tok_ptr.assign(pl->rows_q + 1, 0);
@@ -1284,6 +1316,8 @@ int build_index_image(stair_plan *pl, const int32_t *q_off) {
         pl->off_tok_ptr = push(pl->tok_ptr); pl->off_tok_span = push(pl->tok_span);
         for (Bucket &b : pl->buckets)
             if (!b.scol.empty()) b.soff = push(b.scol);
+        for (Bucket &b : pl->buckets)
+            if (!b.ncol.empty()) b.noff = push(b.ncol);
         pl->off_clear = push(pl->clear_tiles);
     }
     if (pl->train)
@@ -1452,6 +1486,11 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
         pl->o_gS = pl->take("gS", (int64_t)std::max(pl->maxSupRows, 1) * T, 64);
         pl->o_gRs = pl->take("gRs", I * T, 64);
         pl->o_gExtra = pl->take("gExtra", I, 64);
+        // the gradient of a frozen weight, where a launch produces it beside a trainable one (a Linear's dW with a live db, one of
+        // an encoder's eight tensors): the largest weight fits, nothing reads it, every frozen tensor shares it
+        int64_t most = 64;
+        for (int64_t ne : ctx->numel) most = std::max(most, ne);
+        pl->o_discard = pl->take("discard", most, 64);
     }
     pl->total = align_up(pl->total, 64);
     if (pl->train) {
@@ -1678,7 +1717,9 @@ extern "C" int stair_plan_nodes(const stair_plan *pl, int32_t *kind, int32_t *sl
 // =============================================================================================
 namespace {
 
-int resolve(const stair_ctx *ctx, Weights &W, bool grads) {
+// grads: the bound gradient buffer of every trainable weight; a frozen one (stair_ctx_set_trainable) gets `discard` instead --
+// whatever a launch still produces for it lands there, never in the bound buffer (which need not be bound at all)
+int resolve(const stair_ctx *ctx, Weights &W, bool grads, float *discard = nullptr) {
     const std::string p = "submodules.";
     auto get = [&](const std::string &name, const float *&dst, float **gdst) {
         dst = ctx->find(name);
@@ -1687,6 +1728,8 @@ int resolve(const stair_ctx *ctx, Weights &W, bool grads) {
             return 1;
         }
         if (grads) {
+            auto it = ctx->by_name.find(name);
+            if (it != ctx->by_name.end() && !ctx->trainable[it->second]) { *gdst = discard; return 0; }
             *gdst = ctx->findg(name);
             if (!*gdst) {
                 set_error("gradient buffer not set: " + name);
@@ -2466,7 +2509,7 @@ static int64_t det_layout(const stair_ctx *ctx) {
     int64_t o64 = 0;
     for (size_t i = 0; i < ctx->names.size(); ++i) {
         d.off[i] = o64; o64 += align_up(ctx->numel[i], 64);
-        if (ctx->gptr[i]) d.ranges.push_back({ctx->gptr[i], ctx->gptr[i] + ctx->numel[i], (int)i});
+        if (ctx->gptr[i] && ctx->trainable[i]) d.ranges.push_back({ctx->gptr[i], ctx->gptr[i] + ctx->numel[i], (int)i});     // (a frozen weight has no shadow: nothing adds to it)
     }
     std::sort(d.ranges.begin(), d.ranges.end(), [](const DetRange &a, const DetRange &b) { return a.beg < b.beg; });
     return o64;
@@ -2493,6 +2536,8 @@ struct BwdCtx {
     hipStream_t s;
     float *wt;                       // transposed weight images
     float *splitk = nullptr;         // split-K scratch (plan workspace): dX products that overwrite their target stage partials there
+    const float *discard = nullptr;  // the gradient pointer of every frozen weight (resolve): a product all of whose outputs go there is not launched
+    bool dead(const Lin &l) const { return l.dw == discard && l.db == discard; }
     std::vector<int64_t> wt_off;     // per weight id
     std::vector<char> deferred;      // per weight id: its weight-gradient product runs once, after all buckets (per-weight regions)
     // scratch ring of the slab-reduced weight-gradient products of the remaining map-level layers (csrc/gemm_tn_x3tr.hip): a product
@@ -2526,7 +2571,7 @@ int dense_bwd(const BwdCtx &B, const float *dZ, int groups, int R, int N, int K,
     t.row_scale = rs; t.rs_gstride = rs_gs; t.rs_gidx = rs_gidx;
     t.C = l.dw; t.ldc = K; t.M = M; t.rows_per_group = R; t.N = N; t.K = K;
     t.colsum = l.db;                 // db += colsum(dZ), summed while the TN kernel stages dZ
-    if (!(l.id >= 0 && l.id < (int)B.deferred.size() && B.deferred[l.id])) {
+    if (!(l.id >= 0 && l.id < (int)B.deferred.size() && B.deferred[l.id]) && !B.dead(l)) {
         const int64_t need = M >= policy_or(STAIR_OPT_TN_SLAB_MIN_ROWS, g_tn_slab_min_rows) && B.tn_ring && tn_x3tr_takes(t) ? align_up(tn_x3tr_scratch_floats(M, N, K), 64) : 0;
         if (need && need <= B.tn_ring_floats) {
             float *piece;
@@ -2577,6 +2622,14 @@ long long *stair::det_shadow(const float *g) {
 // The reverse pass behind both entry points.  Seed: the decoder CE against `answers` (stair_plan_backward), or the caller's logits
 // gradient when d_logits_in is set (stair_plan_backward_dlogits); d_video / d_question (optional) receive the encoders' input
 // gradients after BPTT.  With d_logits_in, d_video and d_question all NULL this is exactly the pass stair_plan_backward always ran.
+// Frozen weights (stair_ctx_set_trainable) -- the rule, stated once: their gradient pointers are the workspace's discard region
+// (resolve), so nothing reaches their bound buffers; a weight-gradient product all of whose outputs are frozen is not launched
+// (BwdCtx::dead); an encoder whose eight tensors are frozen and whose input gradient nobody asked for is left out whole; and when
+// no weight the plan uses outside the decoder is trainable, no input gradient is requested and the arenas hold no injected
+// gradient, the pass ends behind the decoder's own weight gradients.  While the video encoder's block is left out, a fused chain
+// whose input tiles are all clip tiles ends in front of its last product (STAIR_TILE_NO_DX, Bucket::ncol): nobody reads that dX.
+// With every weight trainable the pass is the one it always was.
+static void plan_uses(const stair_ctx *ctx, const stair_plan *pl, int32_t *used);
 static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, const float *question, void *workspace,
                          int64_t workspace_bytes, const int32_t *answers, float loss_scale, float *loss_out, const float *d_logits_in,
                          float *d_video, float *d_question, int32_t flags, stair_stream stream) {
@@ -2590,7 +2643,22 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     STAIR_CHECK(workspace_bytes >= pl->total * (int64_t)sizeof(float), "workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     Weights W;
-    if (resolve(ctx, W, true)) return 1;
+    float *const discard = static_cast<float *>(workspace) + pl->o_discard;
+    if (resolve(ctx, W, true, discard)) return 1;
+    // what the pass may leave out (see above)
+    bool enc_dw[2], enc_run[2];              // encoder e: any of its eight tensors trainable; its block runs at all
+    for (int e = 0; e < 2; ++e) {
+        enc_dw[e] = false;
+        for (int k = 0; k < 8; ++k) enc_dw[e] = enc_dw[e] || W.denc[e][k] != discard;
+        enc_run[e] = enc_dw[e] || (e == 0 ? d_video : d_question) != nullptr;
+    }
+    bool walk = (flags & STAIR_BWD_KEEP_ARENAS) || enc_run[0] || enc_run[1];
+    if (!walk) {
+        std::vector<int32_t> used(ctx->names.size());
+        plan_uses(ctx, pl, used.data());
+        for (size_t i = 0; i < used.size(); ++i)
+            walk = walk || (used[i] && ctx->trainable[i] && (int)i != W.dec0.id && (int)i != W.dec0.id + 1 && (int)i != W.dec3.id && (int)i != W.dec3.id + 1);
+    }
 
     const stair_config &g = ctx->cfg;
     const int H = g.hidden_size, Hh = H / 2, V = g.video_size, E = g.text_size, A = g.answer_vocab_length;
@@ -2616,7 +2684,9 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     // every tail adds, as it always did.
     const bool store_first = !(flags & STAIR_BWD_KEEP_ARENAS) && pl->store_first_ok && pl->o_wfragT > 0 && tile_mlp_usable(H, T) &&
                              (reinterpret_cast<uintptr_t>(ws) & 15) == 0;
-    if (store_first) {
+    if (!walk) {
+        // (nothing reads the gradient arenas: they are not cleared)
+    } else if (store_first) {
         const int64_t m0 = pl->o_gblock + (pl->o_map - pl->o_vec), m1 = m0 + (int64_t)(pl->n_map + pl->n_map_stage) * TH;
         RUN(launch_zero_segments(ws + pl->o_zero_beg, m0 - pl->o_zero_beg, g_map, didx + pl->off_clear, (int)pl->clear_tiles.size(), TH,
                                  ws + m1, pl->o_zero_end - m1, s));
@@ -2625,7 +2695,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
 
     // transposed images of every 2-D weight that needs a dX product
     BwdCtx B;
-    B.s = s; B.wt = ws + pl->o_wt; B.splitk = ws + pl->o_splitk;
+    B.s = s; B.wt = ws + pl->o_wt; B.splitk = ws + pl->o_splitk; B.discard = discard;
     B.tn_ring = pl->o_tnring ? ws + pl->o_tnring : nullptr; B.tn_ring_floats = pl->tnring_floats;
     B.wt_off.assign(ctx->names.size(), 0);
     // run-to-run reproducible weight gradients: kernels that add into a gradient tensor from several workgroups add into its
@@ -2676,7 +2746,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     // gradient row of the arena (relu' on load, kept as dZ), one for the second stage of the two-layer modules
     const bool grouped = fused && vec_group_usable(H) && vec_group_on();
     std::vector<VgProblem> bvg1, bvg2;
-    if (grouped) {      // planes of the transposed images (already there as fp32): block (j, s) of W^T = slot + j * nin + s
+    if (grouped && walk) {      // planes of the transposed images (already there as fp32): block (j, s) of W^T = slot + j * nin + s
         bool has[32] = {};                          // (W^T is [nseg * 512, nblk * 512]: the forward blocks with the two counts exchanged)
         for (const Bucket &b : pl->buckets) if (b.cnt > 0 && b.op >= 0 && b.op < 32) has[b.op] = true;
         const float *src[32];
@@ -2706,7 +2776,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         q.fa = vec; q.fb = vec; q.fia = fia; q.fib = fib; q.ldfa = H; q.ldfb = H; q.ga = g_vec; q.gb = g_vec; q.gia = gia; q.gib = gib;
         return q;
     };
-    if (fused) {
+    if (fused && walk) {
         bool need[WF_COUNT];
         // (FilterFrame variant 0 needs no transposed planes: its backward is not a chain)
         tile_weights_in_use(pl, need, [](const Bucket &b) { return b.op == STAIR_OP_FILTERFRAME && b.variant == 0; });
@@ -2723,25 +2793,41 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     else RUN(launch_ce_loss(logits, answers, loss_scale, loss, dlogits, n, A, s));
     {
         const float *cat = ws + pl->o_cat, *hid = ws + pl->o_hid;     // decoder buffers are never reused by buckets in training
+        // (a pass that ends here -- !walk -- needs d(hidden) only for the first layer's weight gradient, and no d(cat) at all)
+        const bool need_hid = walk || !B.dead(W.dec0);
         if (grouped) {
             // d(hidden) = (dlogits W3) * relu'(hidden) in one launch, d(cat[root, question]) = d(hidden) W0 with the adjoint of the
             // concatenation in the epilogue in a second one; the two weight gradients stay reductions over the batch (TN products)
             RUN(dense_bwd(B, dlogits, n, 1, A, 2 * H, hid, 2 * H, 2 * H, nullptr, W.dec3, nullptr, 2 * H, 2 * H, nullptr, 0));
+            if (need_hid) {
             VgProblem q3 = vg_fwd(n, dlogits, nullptr, A, nullptr, nullptr, 0, VG_IN_A, B.wt + B.wt_off[W.dec3.id], A, nullptr, 2 * H, 2, gV0, nullptr, 2 * H);
             q3.kred = A; q3.emask = hid; q3.ldm = 2 * H; q3.escale = inv_keep;
             RUN(launch_vec_group(&q3, 1, s));
             RUN(dense_bwd(B, gV0, n, 1, 2 * H, 2 * H, cat, 2 * H, 2 * H, nullptr, W.dec0, nullptr, 2 * H, 2 * H, nullptr, 0));
+            }
+            if (walk) {
             VgProblem q0 = {};
             q0.kind = VG_ADJ; q0.rows = n; q0.a = gV0; q0.lda = 2 * H; q0.b = gV0 + H; q0.ldb = 2 * H; q0.pack = VG_IN_CAT2; q0.in_scale = 1.0f; q0.kred = 512;
             q0.W = B.wt + B.wt_off[W.dec0.id]; q0.ldw = 2 * H; q0.N = 2 * H; q0.adj = VG_IN_CAT2; q0.wplanes = WFT(WV_DEC0);
             q0.fia = didx + pl->off_roots; q0.ldfa = H; q0.ldfb = H; q0.ga = g_vec; q0.gb = g_qfeat; q0.gia = didx + pl->off_groots;
             RUN(launch_vec_group(&q0, 1, s));
+            }
         } else {
-        RUN(dense_bwd(B, dlogits, n, 1, A, 2 * H, hid, 2 * H, 2 * H, nullptr, W.dec3, gV0, 2 * H, 2 * H, nullptr, 0));
+        RUN(dense_bwd(B, dlogits, n, 1, A, 2 * H, hid, 2 * H, 2 * H, nullptr, W.dec3, need_hid ? gV0 : nullptr, 2 * H, 2 * H, nullptr, 0));
+        if (need_hid) {
         RUN(launch_mask_relu(gV0, gV0, 2 * H, nullptr, hid, 2 * H, nullptr, n, 2 * H, s, inv_keep));
-        RUN(dense_bwd(B, gV0, n, 1, 2 * H, 2 * H, cat, 2 * H, 2 * H, nullptr, W.dec0, gCat, 2 * H, 2 * H, nullptr, 0));
-        RUN(launch_pack_bwd(PACK_CAT2, vec, didx + pl->off_roots, qfeat, nullptr, gCat, g_vec, g_qfeat, n, H, s));
+        RUN(dense_bwd(B, gV0, n, 1, 2 * H, 2 * H, cat, 2 * H, 2 * H, nullptr, W.dec0, walk ? gCat : nullptr, 2 * H, 2 * H, nullptr, 0));
         }
+        if (walk) RUN(launch_pack_bwd(PACK_CAT2, vec, didx + pl->off_roots, qfeat, nullptr, gCat, g_vec, g_qfeat, n, H, s));
+        }
+    }
+    if (!walk) {                // decoder only: the pass ends here (dW, db of the decoder went through the fixed-point shadows)
+        RUN(tn_x3tr_flush(s));
+        RUN(det_flush(ctx, s));
+        if (pl->bwd_event) STAIR_HIP(hipEventRecord(static_cast<hipEvent_t>(pl->bwd_event), s));
+        if (g_det.active) ctx->gshadow_dirty = false;
+        g_det.active = false;
+        return 0;
     }
 
     // ---- program levels in reverse ---------------------------------------------------------------
@@ -2763,6 +2849,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         a.W[l] = w; a.act[l] = 3; a.save[l] = save;
         if (!(a.act_bits[l] = BITS(bits))) a.act_mask[l] = mask;
     };
+    const bool nodx_on = !enc_run[0];          // nobody reads a clip tile's gradient: chains on clip tiles end before their last product
     auto bwd_bucket = [&](const Bucket &b, const int phase) -> int {
         if (b.cnt == 0) return 0;
         const int c = b.cnt;
@@ -2771,7 +2858,9 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         const int32_t *LEN = pl->ragged ? didx + b.off[6] : nullptr;
         // where the gradients of the operand columns go: the operand slots themselves, or staging slots (build_grad_fanin)
         const int32_t *G0 = didx + b.goff[0], *G1 = didx + b.goff[1], *G2 = didx + b.goff[2], *G4 = didx + b.goff[4];
-        const int32_t *G0c = store_first && b.soff >= 0 ? didx + b.soff : G0;      // the chain tails' copy of G0: first-touch marks
+        // the chain tails' copy of G0: first-touch marks -- or, for a bucket of clip tiles while the video encoder's block is left
+        // out, the marks that end the chain in front of its last product (csrc/tile_mlp.hip, STAIR_TILE_NO_DX)
+        const int32_t *G0c = nodx_on && b.noff >= 0 ? didx + b.noff : (store_first && b.soff >= 0 ? didx + b.soff : G0);
         const float *svA = ws + b.svA, *svB = ws + b.svB, *svK = ws + b.svK, *svCat = ws + b.svCat, *svHid = ws + b.svHid;
         const float *svRs = ws + b.svRs, *svSup = ws + b.svSup;
         // dZ of the bucket's first / second tile layer: its block of the weight's region (the product with X is deferred), else scratch
@@ -2815,6 +2904,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         };
         switch (b.op) {
             case OP_SPAN:
+                if (!enc_run[1]) break;         // (the token gradients feed the text encoder's BPTT alone)
                 RUN(launch_span_mean_bwd_rows(g_tok, H, pl->rows_q, didx + pl->off_tok_ptr, didx + pl->off_tok_span, I1, g_vec, I2, H, s));
                 break;
             case STAIR_OP_AND:
@@ -3003,7 +3093,18 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     auto fanin_level = [&](int L) -> int {
         if (L < 0 || L >= (int)pl->fanin_count.size() || fanin_done[L]) return 0;
         fanin_done[L] = 1;
-        return launch_grad_fanin(didx + pl->off_fanin + 5 * pl->fanin_first[L], pl->fanin_count[L], g_vec, g_map, g_att, H, T, s);
+        int first = pl->fanin_first[L], count = pl->fanin_count[L];
+        if (L == 0 && !enc_run[0]) {
+            // the clip tiles' entries (map slots 0 .. n_vid - 1: what BPTT of the video encoder reads, and nothing else) are left out;
+            // they follow each other -- a level's entries are vec rows, map tiles in slot order, att rows (build_grad_fanin)
+            int c0 = first, c1;
+            auto clip = [&](int i) { return pl->fanin[5 * i] == FAN_MAP && pl->fanin[5 * i + 1] < pl->n_vid; };
+            while (c0 < first + count && !clip(c0)) ++c0;
+            for (c1 = c0; c1 < first + count && clip(c1); ++c1) {}
+            if (int rc = launch_grad_fanin(didx + pl->off_fanin + 5 * first, c0 - first, g_vec, g_map, g_att, H, T, s)) return rc;
+            count -= c1 - first; first = c1;
+        }
+        return launch_grad_fanin(didx + pl->off_fanin + 5 * first, count, g_vec, g_map, g_att, H, T, s);
     };
     if (!fused) {
         for (auto it = pl->buckets.rbegin(); it != pl->buckets.rend(); ++it) {
@@ -3042,6 +3143,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     for (int w = 0; w < WF_COUNT; ++w) {
         if (w == WF_FFD || pl->wg_rows[w] == 0) continue;
         const Lin &l = WIX.wf[w]->lin(W);
+        if (B.dead(l)) continue;
         stair_gemm_tn_args t = {};
         t.A = ws + pl->wg_dz[w]; t.lda = H;
         t.C = l.dw; t.ldc = H; t.colsum = l.db;
@@ -3063,6 +3165,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     for (int w = 0; w < VD_COUNT; ++w) {
         if (pl->vd_rows[w] == 0) continue;
         const Lin &l = WIX.vd[w]->lin(W);
+        if (B.dead(l)) continue;
         const int Kw = vd_cols(w, H);
         stair_gemm_tn_args t = {};
         t.A = ws + pl->vd_dz[w]; t.lda = H;
@@ -3107,7 +3210,17 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
             }
         }
         // the two reverse-time recurrences in one launch while both fit on the chip, then each layer's weight gradients
+        // (a frozen encoder: without an input gradient to produce its block is left out and the other recurrence runs alone, in
+        // the single form of the same kernel; with one, BPTT runs and only the weight products are dropped -- what is left of
+        // them is clearing the gate gradients behind a short clip's end, which the input-gradient product reads)
+        auto enc_products = [&](const stair_lstm_bwd_args &a, int e) -> int {
+            return enc_dw[e] ? launch_lstm_bwd_weights(a, s) : launch_lstm_bwd_clear_tail(a, s);
+        };
         int rc_pair = -1;
+        if (!(enc_run[0] && enc_run[1])) {
+            for (int e = 1; e >= 0; --e)
+                if (enc_run[e]) { RUN(launch_lstm_bwd_recur(enc[e], s)); RUN(enc_products(enc[e], e)); }
+        } else {
         if (lstm_bwd_takes_coop(enc[0]) && lstm_bwd_takes_coop(enc[1])) rc_pair = launch_lstm_bwd_coop_pair(enc[1], enc[0], s);
         if (rc_pair > 0) return rc_pair;
         if (rc_pair < 0) {
@@ -3115,11 +3228,12 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
             // encoder's on a second stream was measured: nothing to gain at 512 or 2048 questions (6.13 vs 6.12 ms; 16.4-16.7 vs
             // 15.9-16.8) -- the one-workgroup reverse recurrence takes 256 registers x 512 threads, so from 1024 sequences on either
             // pass fills every CU by itself.
-            RUN(launch_lstm_bwd(enc[1], s));
-            RUN(launch_lstm_bwd(enc[0], s));
+            RUN(launch_lstm_bwd_recur(enc[1], s)); RUN(enc_products(enc[1], 1));
+            RUN(launch_lstm_bwd_recur(enc[0], s)); RUN(enc_products(enc[0], 0));
         } else {
-            RUN(launch_lstm_bwd_weights(enc[1], s));
-            RUN(launch_lstm_bwd_weights(enc[0], s));
+            RUN(enc_products(enc[1], 1));
+            RUN(enc_products(enc[0], 0));
+        }
         }
     }
     RUN(tn_x3tr_flush(s));                   // the encoders' slab-reduced weight gradients
@@ -3166,9 +3280,18 @@ extern "C" int stair_plan_backward_dlogits(stair_ctx *ctx, stair_plan *pl, const
 // Which weights receive a gradient from this plan (1) and which do not (0).  torch leaves .grad = None
 // for parameters of modules no program in the window used, and Adam then skips them entirely
 // (train_module.py:408-410); the optimizer kernel reproduces that with this mask.
+// A frozen weight (stair_ctx_set_trainable) receives none: it reports 0 whatever the programs use.
 extern "C" int stair_plan_touched(const stair_ctx *ctx, const stair_plan *pl, int32_t *touched, int32_t count) {
     STAIR_CHECK(ctx && pl && touched, "null argument");
     STAIR_CHECK(count == (int)ctx->names.size(), "count must equal stair_weight_count");
+    plan_uses(ctx, pl, touched);
+    for (int i = 0; i < count; ++i) touched[i] = touched[i] && ctx->trainable[i];
+    return 0;
+}
+
+// used[id] = 1 iff the plan's programs (or its encoders and decoder) send a gradient into weight `id`, frozen or not
+static void plan_uses(const stair_ctx *ctx, const stair_plan *pl, int32_t *touched) {
+    const int count = (int)ctx->names.size();
     for (int i = 0; i < count; ++i) touched[i] = 0;
     auto mark = [&](const std::string &name) {
         auto it = ctx->by_name.find("submodules." + name);
@@ -3197,7 +3320,6 @@ extern "C" int stair_plan_touched(const stair_ctx *ctx, const stair_plan *pl, in
             default: break;
         }
     }
-    return 0;
 }
 
 extern "C" int stair_adam_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq,

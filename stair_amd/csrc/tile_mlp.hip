@@ -207,7 +207,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
     // per-row tables of a packed tile.  pk_tf: bits 0..5 the frame to READ for the input row (0 where the row is zeroed), 16..21 the
     // row's frame, TM_PK_LIVE (not zeroed on input) / TM_PK_FIRST (STAIR_TILE_STORE_FIRST of its instance)
     constexpr int PKN = PACK ? TM_ROWS : 1;
-    __shared__ int pk_tf[PKN], pk_xi[PKN], pk_oi[PKN], pk_len[PKN], pk_mi[PKN], pk_fi[PKN], pk_ri[PKN], pk_pf[PKN], pk_pc[PKN], pk_allfirst;
+    __shared__ int pk_tf[PKN], pk_xi[PKN], pk_oi[PKN], pk_len[PKN], pk_mi[PKN], pk_fi[PKN], pk_ri[PKN], pk_pf[PKN], pk_pc[PKN], pk_allfirst, pk_allnodx;
     __shared__ float pk_sc[PKN], pk_ex[PKN];
 #define TM_PK_LIVE 0x200
 #define TM_PK_FIRST 0x400
@@ -304,7 +304,8 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 const bool live = ex && (!xbc || tt < ln);          // a broadcast row fills the clip's own frames only
                 int oraw = p.out_idx ? p.out_idx[i] : i;
                 const bool fst = KIND != KIND_FWD && (oraw & STAIR_TILE_STORE_FIRST) != 0;
-                if (KIND != KIND_FWD) oraw &= ~STAIR_TILE_STORE_FIRST;
+                const bool ndx = KIND == KIND_CHAIN && (oraw & STAIR_TILE_NO_DX) != 0;
+                if (KIND != KIND_FWD) oraw &= ~(STAIR_TILE_STORE_FIRST | STAIR_TILE_NO_DX);
                 pk_tf[R] = (live ? tt : 0) | (tt << 16) | (live ? TM_PK_LIVE : 0) | (fst ? TM_PK_FIRST : 0);
                 pk_xi[R] = p.x_idx ? p.x_idx[i] : i;
                 pk_oi[R] = oraw;
@@ -323,6 +324,9 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 if (KIND != KIND_FWD) {
                     const unsigned long long notfirst = __ballot(ex && !fst);
                     if (R == 0) pk_allfirst = notfirst == 0ull ? 1 : 0;
+                    // (a packed tile drops its last product only when EVERY instance it holds is marked STAIR_TILE_NO_DX)
+                    const unsigned long long wanted = __ballot(ex && !ndx);
+                    if (KIND == KIND_CHAIN && R == 0) pk_allnodx = wanted == 0ull ? 1 : 0;
                 }
             }
             TM_SYNC();
@@ -491,7 +495,17 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
         TM_SYNC();
 
         f32x16 acc[2][2];
+        bool nodx = false;
         for (int ph = 0; ph < p.n_layers; ++ph) {
+            // STAIR_TILE_NO_DX: nobody reads this tile's input gradient -- the chain ends in front of its last product (dX = dZ W of
+            // the first forward layer) and its tail; every dZ save before it has been written.  Uniform over the workgroup; looked up
+            // here, once per tile, so that nothing more is live across the k loops
+            if (KIND == KIND_CHAIN && ph + 1 == p.n_layers &&
+                (PACK ? __builtin_amdgcn_readfirstlane(pk_allnodx) != 0
+                      : (p.out_idx != nullptr && (__builtin_amdgcn_readfirstlane(p.out_idx[ii]) & STAIR_TILE_NO_DX) != 0))) {
+                nodx = true;
+                break;
+            }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -680,6 +694,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             }
         }
 
+        if (KIND == KIND_CHAIN && nodx) continue;      // (the stage before ended with a barrier; the next tile begins with one)
         // ---- tails, from the staged rows ---------------------------------------------------------------------------------
         float *svl = p.save[p.n_layers - 1];
         if (svl)                                      // the last layer's rows for the backward pass (coalesced 2 KB rows)
@@ -1194,8 +1209,9 @@ __global__ __launch_bounds__(512) void tile_split_pad_kernel(TmParams pp) {
         if (KIND == KIND_FWD && p.save_bits[l]) p.save_bits[l][(int64_t)tile * TM_H + tid] = 0ull;
     }
     const int oraw = p.out_idx ? p.out_idx[ii] : ii;
-    const int64_t oslot = KIND != KIND_FWD ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
+    const int64_t oslot = KIND != KIND_FWD ? (oraw & ~(STAIR_TILE_STORE_FIRST | STAIR_TILE_NO_DX)) : oraw;
     if (KIND != KIND_FWD) {
+        if (KIND == KIND_CHAIN && (oraw & STAIR_TILE_NO_DX)) return;        // (no input gradient wanted: no tail, nothing to write)
         const bool stores = (KIND == KIND_TEMPORAL_BWD || p.tail == STAIR_TILE_ACCUMULATE) ? (oraw & STAIR_TILE_STORE_FIRST) != 0 : p.tail == STAIR_TILE_STORE;
         if (stores) zero_rows(p.out + oslot * p.out_gstride + (int64_t)sfr0 * TM_H);
         return;

@@ -94,8 +94,9 @@ def _filterframe_launch(model, res, items, scale, grads):
     if index is None:
         raise RuntimeError('FilterFrame loss needs model.object_index = losses.object_index(json.load(open(word2id_filename)))')
     head = model.submodules['FilterFrame'].pretrain_head
-    if grads and head.weight.grad is None:
+    if grads and any(t.requires_grad and t.grad is None for t in (head.weight, head.bias)):
         raise RuntimeError('pretrain head of FilterFrame has no .grad buffer (use stair_amd.train.Trainer)')
+    hgrad = lambda t: t.grad if grads and t.requires_grad else None       # a frozen head: no dW / db, d_map is still injected
     frames = [int(a[2]) if len(a) > 2 else T for a in items]
 
     def target(gold_dict, L):            # the criterion sees pred.size(0) = the clip's own frames (train_module.py:146)
@@ -115,7 +116,7 @@ def _filterframe_launch(model, res, items, scale, grads):
         order_d, goff_d = torch.from_numpy(order).to(dev), torch.from_numpy(goff).to(dev)
         check(lib.stair_loss_groups(p(order_d), p(goff_d), len(goff) - 1))
     check(lib.stair_loss_filterframe_len(p(mp), p(gmap), p(slot), p(gold), p(head.weight), p(head.bias),
-                                         p(head.weight.grad) if grads else None, p(head.bias.grad) if grads else None, p(len_d),
+                                         p(hgrad(head.weight)), p(hgrad(head.bias)), p(len_d),
                                          len(items), T, H, O, C.c_float(scale), p(out),
                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
@@ -423,7 +424,7 @@ def prepare_module_losses(model, res, questions, pretrain_modules=CRITERION_MODU
             continue
         if not model.config['have_pretrain_head']:
             raise RuntimeError('%s loss needs have_pretrain_head (modules.py)' % module)
-        if model.submodules[module].pretrain_head.weight.grad is None:
+        if any(t.requires_grad and t.grad is None for t in model.submodules[module].pretrain_head.parameters()):
             raise RuntimeError('pretrain head of %s has no .grad buffer (use stair_amd.train.Trainer)' % module)
         hq, hpos, hlab = gb.head[module]
         tok = hpos + base[hq]
@@ -502,6 +503,8 @@ def launch_module_losses(model, res, prep, scale):
     vec, gvec = res._arena(res.info.vec_off, res.info.n_vec, H), res.grad_arena('vec')
     att, gatt = res._arena(res.info.att_off, res.info.n_att, T), res.grad_arena('att')
     P = lambda t: C.c_void_p(t.data_ptr())
+    PG = lambda t: C.c_void_p(t.grad.data_ptr()) if t.requires_grad else None      # a frozen head weight: no gradient (d_vec is still injected)
+    live = lambda prefix, head: {'%s.%s' % (prefix, k) for k, t in (('weight', head.weight), ('bias', head.bias)) if t.requires_grad}
     # reproducible sums (like the decoder-only step): head-weight gradients through the context's fixed-point shadows, which the
     # backward pass that follows adds to the gradients; arena gradients group by group (stair_loss_groups)
     model._bind_grads()                 # the shadows are found through the bound gradient buffers
@@ -520,13 +523,13 @@ def launch_module_losses(model, res, prep, scale):
         out = torch.empty(n_items, device=dev)
         groups(order_d, goff_d)
         check(lib.stair_loss_head(head.weight.shape[0], P(vec), P(gvec), P(slot_d), P(lab_d), P(head.weight), P(head.bias),
-                                  P(head.weight.grad), P(head.bias.grad), n_items, H, C.c_float(scale), P(out), stream))
+                                  PG(head.weight), PG(head.bias), n_items, H, C.c_float(scale), P(out), stream))
         losses[module] = out
-        touched.update({'submodules.%s.pretrain_head.weight' % module, 'submodules.%s.pretrain_head.bias' % module})
+        touched.update(live('submodules.%s.pretrain_head' % module, head))
     # ---- FilterFrame (off by default, args.py:62) ----
     if prep['ff_items']:
         losses['FilterFrame'] = _filterframe_launch(model, res, prep['ff_items'], scale, True)
-        touched.update({'submodules.FilterFrame.pretrain_head.weight', 'submodules.FilterFrame.pretrain_head.bias'})
+        touched.update(live('submodules.FilterFrame.pretrain_head', model.submodules['FilterFrame'].pretrain_head))
     if prep['n_cont'] and 'cont_table' in prep:
         slot_d, cls_d, win_d, pres_d, reps, n_cls = prep['cont_table']
         out = torch.empty(prep['n_cont'], device=dev)

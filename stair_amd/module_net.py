@@ -349,6 +349,7 @@ class VideoNMN(nn.Module):
         self._weight_names = [lib.stair_weight_name(self._ctx, i).decode() for i in range(lib.stair_weight_count(self._ctx))]
         self._bound = {}
         self._gbound = {}
+        self._trainable = [True] * len(self._weight_names)      # what the context holds (stair_ctx_set_trainable; its default is 1)
         self._ws = None
         self._proj = None
         # run_programs: enqueue the encoders' input projections before the plan is built (False: inside the plan's pass)
@@ -392,9 +393,24 @@ class VideoNMN(nn.Module):
                 check(lib.stair_ctx_set_weight(self._ctx, i, C.c_void_p(p.data_ptr()), p.numel()))
                 self._bound[name] = p.data_ptr()
 
-    def _bind_grads(self):
+    def _sync_trainable(self):
+        """requires_grad of every canonical weight -> the context, before every training pass: a frozen weight gets no gradient
+        and no update, and the reverse pass launches nothing that only it needed (stair_ctx_set_trainable).  Only the bits that
+        changed since the last pass cross the boundary.  Returns the flags in weight-table order."""
         sd = dict(self.named_parameters())
         for i, name in enumerate(self._weight_names):
+            on = bool(sd[name].requires_grad)
+            if self._trainable[i] != on:
+                check(lib.stair_ctx_set_trainable(self._ctx, i, 1 if on else 0))
+                self._trainable[i] = on
+        return self._trainable
+
+    def _bind_grads(self):
+        sd = dict(self.named_parameters())
+        trainable = self._sync_trainable()
+        for i, name in enumerate(self._weight_names):
+            if not trainable[i]:                 # frozen: the pass writes nothing for it, it needs no buffer
+                continue
             g = sd[name].grad
             if g is None or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
                 raise RuntimeError('parameter %s has no contiguous float32 GPU .grad buffer; use stair_amd.train.Trainer '
@@ -496,6 +512,8 @@ class VideoNMN(nn.Module):
             raise ValueError('bf16 clip features need video_size % 32 == 0')
         T = video.shape[1]
         self._bind_weights()
+        if train:
+            self._sync_trainable()              # (BatchResult.touched() and the reverse pass go by the context's flags)
         # The encoders' input projections need the inputs only: enqueue them BEFORE packing the programs and building the plan (3-4 ms
         # of host work at 2048 questions), so the device is busy meanwhile (stair_encoders_project; results bit-identical)
         proj = None

@@ -126,9 +126,18 @@ class Trainer:
                  scheduler_start_factor=1.0, scheduler_end_factor=0.1, scheduler_total_iters=200000, world=1,
                  skip_untouched='ever', train_module_before_iters=1e10, train_decoder_after_iters=0, rank=0,
                  dropout=None, dropout_seed=0, native_allreduce=False, class_table=None, global_batch=None, overlap_allreduce=None,
-                 max_grad_norm=None):
-        """skip_untouched: 'ever'   -- a parameter is skipped by Adam until the first window that sends it a gradient
-                                      (torch 1.13, which the reference pins: zero_grad() keeps zero tensors afterwards);
+                 max_grad_norm=None, freeze=()):
+        """freeze: name prefixes of parameters to freeze, in state_dict terms without the leading 'submodules.' -- a module or
+                encoder ('video_encoder', 'Filter': not FilterFrame), a layer ('Filter.param.representation.0') or one tensor
+                ('decoder.3.weight').  A convenience for p.requires_grad_(False): the flags themselves are read again at every
+                step, so a schedule may thaw (or freeze) parameters between steps.  A frozen parameter gets no gradient (its
+                p.grad segment stays zero), no update (weight, both moments and step count keep their bits), counts for nothing
+                in grad_norm / the clip coefficient / seg_grad_norm (what clip_grad_norm_ does over parameters without a
+                gradient), and the reverse pass launches nothing that only it needed (include/stair_hip.h,
+                stair_ctx_set_trainable).  At world > 1 the frozen set must be the same on every rank; this is not checked.
+        skip_untouched: 'ever'   -- a parameter is skipped by Adam until the first window that sends it a gradient
+                                      (torch 1.13, which the reference pins: zero_grad() keeps zero tensors afterwards); a
+                                      frozen parameter counts from the first step in which it is trainable AND used;
                            'window' -- skipped in every window that does not touch it (torch >= 2.0, set_to_none=True).
         max_grad_norm: None (default) -- the step is the reference's, which has no clipping: nothing extra is launched;
                        a positive float -- torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) between the gradient
@@ -179,6 +188,14 @@ class Trainer:
         self.iters = 0                                      # optimizer steps taken (LambdaLR counter)
         params = dict(model.named_parameters())
         names = model._weight_names
+        freeze = (freeze,) if isinstance(freeze, str) else tuple(freeze)
+        for pre in freeze:
+            pre = pre[len('submodules.'):] if pre.startswith('submodules.') else pre
+            hit = [nme for nme in names if nme[len('submodules.'):] == pre or nme[len('submodules.'):].startswith(pre + '.')]
+            if not hit:
+                raise ValueError('freeze: no parameter is named %r or lies under it' % pre)
+            for nme in hit:
+                params[nme].requires_grad_(False)
         dev = next(model.parameters()).device
         assert dev.type == 'cuda', 'Trainer needs the model on the GPU'
         # flat order: everything but the encoders first (their gradients are final before BPTT starts), the encoders last
@@ -211,7 +228,9 @@ class Trainer:
         self._params = [params[nme] for nme in names]
         self.steps = torch.zeros(len(names), device=dev)     # per-tensor Adam step counts
         self.touched = torch.zeros(len(names), dtype=torch.int32, device=dev)
+        self._ever = [False] * len(names)                    # host view of 'ever': touched in some step so far (on this rank)
         self._mask_ring = _PinnedRing(len(names))
+        self._train_ring = _PinnedRing(len(names))           # the trainable flags of a step, uploaded only while something is frozen
         self._status = []                                    # (step, pinned int32 copy of the step's REDUCED status word, event) per step in flight
         self.guard = torch.zeros(1, dtype=torch.int32, device=dev)      # status of the current step, summed over ranks: Adam's guard
         self._side = self._ev_ready = None
@@ -282,13 +301,17 @@ class Trainer:
         res = self.model.run_programs(programs, spans, video, question, q_lens, train=True, video_index=video_index, dropout=drop,
                                       video_len=video_len, before_run=prepare if supervised else None)
         extra = set()
+        trainable = list(self.model._trainable)               # requires_grad of this step (run_programs has synced it into the context)
         tl = res.touched()                                    # known from the plan: uploaded BEFORE the backward pass is enqueued
+                                                              # (0 for a frozen weight, whatever the programs use)
         if supervised:
             res.zero_grad_arenas()
             self.module_losses, extra = L.launch_module_losses(self.model, res, prep['p'], self.module_loss_weight / G)
             if extra:
                 tl = [t_ or (nme in extra) for t_, nme in zip(tl, self.model._weight_names)]
         t = self._mask_ring.upload(tl, self.touched.device)
+        frozen = not all(trainable)
+        tmask = self._train_ring.upload(trainable, self.touched.device) if frozen else None
         overlap = self._side is not None
         loss = res.backward(answers, self.decoder_loss_weight / G, keep_arenas=supervised,
                             ready_event=self._ev_ready if overlap else None)
@@ -328,11 +351,14 @@ class Trainer:
             self.touched = torch.maximum(self.touched, t * ok)
         else:
             self.touched.copy_(t)
-        self.steps += (self.touched * ok).to(torch.float32)
+        # Adam's mask: under 'ever' a parameter that was touched once and is frozen NOW is skipped too (its moments must not decay
+        # into the weight); nothing is frozen -> the mask is self.touched itself, as it always was
+        mask = self.touched * tmask if frozen else self.touched
+        self.steps += (mask * ok).to(torch.float32)
         lr = self.lr * self.lr_factor()
         adam_args = (C.c_void_p(self.flat_p.data_ptr()), C.c_void_p(self.flat_g.data_ptr()),
                      C.c_void_p(self.exp_avg.data_ptr()), C.c_void_p(self.exp_avg_sq.data_ptr()),
-                     C.c_void_p(self.seg_of_block.data_ptr()), C.c_void_p(self.touched.data_ptr()),
+                     C.c_void_p(self.seg_of_block.data_ptr()), C.c_void_p(mask.data_ptr()),
                      C.c_void_p(self.steps.data_ptr()), C.c_float(lr), C.c_float(self.betas[0]),
                      C.c_float(self.betas[1]), C.c_float(self.eps), C.c_float(self.wd), self.n,
                      C.c_void_p(self.guard.data_ptr()))           # guard: no update when ANY rank's pass failed
@@ -342,7 +368,13 @@ class Trainer:
             check(lib.stair_adam_step(*adam_args, stream))
         # the kernel wrote the parameters through their storage: tell torch, as an in-place torch update would (version counters --
         # what autograd's saved tensors and a ClipCache's staleness check go by)
-        torch.autograd.graph.increment_version(self._params)
+        # -- for the parameters the kernel may have written only: a frozen encoder keeps its version, and a ClipCache made before the
+        # run is still fresh after it.  (At world > 1 another rank's shard may have touched what this one's did not.)
+        self._ever = [a or b for a, b in zip(self._ever, tl)]
+        hit = trainable if self.world > 1 else [a and b for a, b in zip(trainable, self._ever if self.skip_untouched == 'ever' else tl)]
+        written = [p for p, w in zip(self._params, hit) if w]
+        if written:
+            torch.autograd.graph.increment_version(written)
         if len(self._status) < 16:
             host = torch.empty(1, dtype=torch.int32).pin_memory()
         else:                                                 # the oldest entry's buffer is reused: look at it first
