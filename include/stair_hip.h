@@ -593,8 +593,16 @@ int stair_cosine_topk(const float *queries, int64_t ldq, const int32_t *q_idx, c
                                (gather_encoded_video_kernel) copies clip v's video_len[v] rows into map slot v and writes exact zeros
                                behind them; the text encoder runs alone.  With STAIR_PLAN_EXT_PROJECTION the caller's buffer holds the text
                                projection only: stair_projection_floats / stair_encoders_project with n_videos = 0 (video may be NULL).
-                               Inference only: combined with STAIR_PLAN_TRAIN every stair_plan_build* fails (a plan of encoded clips has no
-                               encoder to send gradients to). */
+                               Combined with STAIR_PLAN_TRAIN the plan builds only while all eight submodules.video_encoder.* tensors are
+                               frozen (stair_ctx_set_trainable(ctx, id, 0)); with one of them trainable every stair_plan_build* fails: a plan
+                               of encoded clips has no encoder to send gradients to, and a cache of a trainable encoder would be stale after
+                               the first step.  Such a training plan has the node table, slots, levels, buckets and gradient arenas of the
+                               STAIR_PLAN_TRAIN plan of the same batch and none of the video encoder's training saves (cell states, the video
+                               half of h(t-1), its weight-gradient scratch); stair_plan_set_dropout works as on any training plan.
+                               stair_plan_backward[_dlogits] takes video == NULL, refuses d_video and refuses -- before anything is
+                               enqueued -- when a tensor of the encoder was thawed since the build; the pass is that of a frozen video
+                               encoder (no BPTT, chains on clip tiles end early), plus the gradient of the encodings on request
+                               (stair_plan_set_encoded_video_grad).  stair_plan_touched reports 0 for the encoder. */
 int stair_plan_build(stair_ctx *ctx, int32_t n, const int32_t *prog_off, const int32_t *tokens,
                      const int32_t *span_lo, const int32_t *span_hi, const int32_t *q_off, int32_t T,
                      int32_t flags, stair_plan **out);
@@ -753,11 +761,24 @@ int stair_plan_set_projection(const stair_ctx *ctx, stair_plan *plan, float *buf
  *                        stair_plan_run_flags refuses to run such a plan before this call.  Lifetime: the cache memory must stay alive
  *                        and UNMODIFIED until the stream has passed every pass (and every replay of a captured pass) of the plan; the
  *                        library keeps the pointer, not a copy.  The encodings are those of the weights and the matmul mode they were
- *                        made with: after either changes, encode again. */
+ *                        made with: after either changes, encode again.
+ *   stair_plan_set_encoded_video_grad   (additive to ABI 7) a STAIR_PLAN_TRAIN | STAIR_PLAN_VIDEO_ENCODED plan, after
+ *                        stair_plan_set_encoded_video: every LATER reverse pass also produces the gradient of the encodings -- for a
+ *                        caller whose own clip encoder sits in front of the executor.  Behind the last gradient fan-in ONE launch
+ *                        (scatter_encoded_video_grad_kernel, the gather's adjoint: no atomics, no LDS) STORES plan clip v's video_len[v]
+ *                        gradient rows at d_enc + rows[v] * clip_stride_floats (rows: those of stair_plan_set_encoded_video) and exact
+ *                        zeros behind them up to rows_cap - 1; the gradient of a clip is the sum over the questions that share it.  Rows
+ *                        of d_enc that no plan clip names are not written.  d_enc: device fp32, 16-byte aligned, alive until the stream has
+ *                        passed the reverse pass; strides checked as for the encodings.  Refused: a plan without both flags, a call
+ *                        before stair_plan_set_encoded_video, a video_len[v] > rows_cap, and rows that are not pairwise distinct (two
+ *                        plan clips would store to one gradient row).  d_enc == NULL withdraws the request, and so does a new
+ *                        stair_plan_set_encoded_video.  Host-only.  With the request the pass walks every level, ends no chain early
+ *                        (STAIR_TILE_NO_DX is off) and sums the clip tiles' fan-in; every parameter gradient keeps its bits. */
 int64_t stair_encode_clips_ws_bytes(const stair_ctx *ctx, int32_t n, int32_t T, int32_t out_rows_cap);
 int stair_encode_clips(stair_ctx *ctx, const void *video, int32_t video_is_bf16, int32_t n, int32_t T, const int32_t *video_len,
                        float *out, int32_t out_rows_cap, void *workspace, int64_t workspace_bytes, stair_stream stream);
 int stair_plan_set_encoded_video(stair_plan *plan, const float *enc, int64_t clip_stride_floats, int32_t rows_cap, const int32_t *rows);
+int stair_plan_set_encoded_video_grad(stair_plan *plan, float *d_enc, int64_t clip_stride_floats, int32_t rows_cap);
 int stair_plan_run_flags(stair_ctx *ctx, stair_plan *plan, const float *video, const float *question,
                          void *workspace, int64_t workspace_bytes, float *logits, int32_t *argmax, int32_t flags,
                          stair_stream stream);

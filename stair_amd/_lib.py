@@ -248,6 +248,7 @@ SIGNATURES = [
     ('stair_encode_clips', C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_int64, C.c_void_p]),
     ('stair_plan_set_encoded_video', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, c_int32_p]),
+    ('stair_plan_set_encoded_video_grad', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     ('stair_plan_run_flags', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p]),
 ]

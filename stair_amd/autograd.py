@@ -13,6 +13,9 @@ Semantics:
   with ``requires_grad = False``: the forward call hands the flags to the context (``VideoNMN._sync_trainable``), and the reverse
   pass then launches nothing that only they needed -- a frozen encoder costs no BPTT unless ``video`` / ``question`` asks for its
   input gradient;
+* on encoded clips (a ``ClipCache``, or the caller's own encodings) the video encoder must be frozen; the encodings' gradient is the
+  adjoint of the plan's gather (``stair_plan_set_encoded_video_grad``): summed over the questions that share a clip, zero behind a
+  clip's frames and for clips that no question reads;
 * every differentiable call owns its workspace and projection buffer until its backward has run (the model's shared buffers are
   rewritten by the next batch), so several outstanding forwards may go backward together; the buffers are released afterwards;
 * a batch goes backward ONCE: BPTT overwrites the saved gates with their gradients.  A second backward through the same logits
@@ -33,20 +36,27 @@ _SEG = 64          # gradient buffers start on 256-byte boundaries inside one fl
 
 class PlanLogits(torch.autograd.Function):
     """apply(model, call, video, question, *params) -> logits [n, A]; `call` = (programs, spans, q_lens, video_index, video_len,
-    dropout, cse) as for ``VideoNMN.run_programs``; `params` in the order of ``model._weight_names``."""
+    dropout, cse, clips, plan_clips) as for ``VideoNMN.run_programs``; `params` in the order of ``model._weight_names``.  On encoded
+    clips (``VideoNMN.logits(clips=...)`` / ``(encoded=...)``) plan_clips is what ``VideoNMN._clips_of_rows`` returned and `video`
+    is None (a ClipCache: no gradient goes to it) or the encodings [n_clips, T, H], whose gradient comes back in their shape."""
 
     @staticmethod
     def forward(ctx, model, call, video, question, *params):
-        programs, spans, q_lens, video_index, video_len, dropout, cse = call
+        programs, spans, q_lens, video_index, video_len, dropout, cse, clips, plan_clips = call
         shared = model._ws, model._proj
         model._ws = model._proj = None           # run_programs allocates buffers for THIS batch; the shared ones are put back
         try:
-            res = model.run_programs(programs, spans, video.detach(), question.detach(), q_lens, train=True, video_index=video_index,
-                                     dropout=dropout, video_len=video_len, cse=cse)
+            if plan_clips is not None:           # encoded clips: a ClipCache (video is None), or the encodings themselves as `video`
+                res = model._run_cached(programs, spans, question.detach(), q_lens, None, cse, clips, *plan_clips, train=True,
+                                        dropout=dropout, enc=None if video is None else video.detach())
+            else:
+                res = model.run_programs(programs, spans, video.detach(), question.detach(), q_lens, train=True, video_index=video_index,
+                                         dropout=dropout, video_len=video_len, cse=cse)
         finally:
             model._ws, model._proj = shared
         ctx.model, ctx.res = model, res
-        ctx.video_dtype = video.dtype
+        ctx.video_dtype = video.dtype if video is not None else None
+        ctx.encoded = plan_clips is not None
         return res.logits
 
     @staticmethod
@@ -70,17 +80,22 @@ class PlanLogits(torch.autograd.Function):
         dev = res.logits.device
         flat = torch.zeros(total, dtype=torch.float32, device=dev)
         grads = [flat[o: o + params[name].numel()].view_as(params[name]) for o, name in zip(offs, names)]
-        d_video = torch.empty(res._video.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        # (encoded clips: the pass stores the rows of the plan's clips only -- clips that no question reads keep these zeros)
+        d_encoded = torch.zeros(res._enc.shape, dtype=torch.float32, device=dev) if ctx.encoded and ctx.needs_input_grad[2] else None
+        d_video = torch.empty(res._video.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] and not ctx.encoded else None
         d_question = torch.empty(res._question.shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
         try:
             for i, g in enumerate(grads):
                 check(lib.stair_ctx_set_grad(model._ctx, i, C.c_void_p(g.data_ptr()), g.numel()))
-            res.backward_dlogits(d_logits.detach().to(torch.float32).contiguous(), d_video, d_question, bind_grads=False)
+            res.backward_dlogits(d_logits.detach().to(torch.float32).contiguous(), d_video, d_question, bind_grads=False,
+                                 d_encoded=d_encoded)
             touched = res.touched()
         finally:
             model._gbound = {}                   # a Trainer (or BatchResult.backward) used later binds its own buffers again
             del res                              # the plan, its workspace and projection buffer go (stream-ordered reuse)
         if d_video is not None and ctx.video_dtype != torch.float32:
             d_video = d_video.to(ctx.video_dtype)
+        if ctx.encoded:
+            d_video = d_encoded
         out = [g if (t and need) else None for g, t, need in zip(grads, touched, need_p)]
         return (None, None, d_video, d_question, *out)

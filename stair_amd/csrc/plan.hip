@@ -226,6 +226,12 @@ extern "C" int stair_ctx_get_trainable(const stair_ctx *ctx, int id, int32_t *on
     *on = ctx->trainable[id];
     return 0;
 }
+// all eight tensors of the video encoder are frozen: the condition under which a training plan of encoded clips exists
+static bool video_encoder_frozen(const stair_ctx *ctx) {
+    for (size_t i = 0; i < ctx->names.size(); ++i)
+        if (ctx->names[i].compare(0, 25, "submodules.video_encoder.") == 0 && ctx->trainable[i]) return false;
+    return true;
+}
 
 // =============================================================================================
 // plan
@@ -294,6 +300,35 @@ static int launch_gather_encoded_video(const float *src, int64_t src_stride, con
     STAIR_ACCT("gather_encoded_video", 2ll * n * T_dst * H * 4);
     hipLaunchKernelGGL(gather_encoded_video_kernel, dim3(n, (th4 + 2047) / 2048), dim3(256), 0, s, src, src_stride, rows, len, dst, dst_stride,
                        th4, H / 4, src_rows);
+    STAIR_LAUNCH_CHECK();
+    return 0;
+}
+
+// The gather's adjoint (training plans of encoded clips, stair_plan_set_encoded_video_grad): gradient tile v = src + v * src_stride
+// ([T_src, H], the clip's tile of the map gradient arena, complete behind the last fan-in) into the caller's rows
+// dst + rows[v] * dst_stride, which hold dst_rows rows: the first min(len[v], dst_rows, T_src) rows of the tile, exact zeros behind
+// them up to dst_rows - 1 (nothing behind a clip's end is read from the tile: the frames there carry no gradient of the encodings).
+// It STORES: the caller has checked that rows are pairwise distinct, so no two blocks share a destination; rows of dst that no plan
+// clip names are not written.  dh4 = dst_rows * H / 4; 16-byte loads and stores as in the gather.  Grid (clips, chunks).
+__global__ void __launch_bounds__(256) scatter_encoded_video_grad_kernel(const float *__restrict__ src, int64_t src_stride, const int32_t *__restrict__ rows,
+                                                                           const int32_t *__restrict__ len, float *__restrict__ dst, int64_t dst_stride,
+                                                                           int dh4, int h4, int src_rows) {
+    const int v = blockIdx.x;
+    const int live4 = min(min(len[v], src_rows) * h4, dh4);
+    const float4 *s = reinterpret_cast<const float4 *>(src + (int64_t)v * src_stride);
+    float4 *d = reinterpret_cast<float4 *>(dst + (int64_t)rows[v] * dst_stride);
+    for (int e = blockIdx.y * blockDim.x + threadIdx.x; e < dh4; e += gridDim.y * blockDim.x)
+        d[e] = e < live4 ? s[e] : float4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+
+// the caller has checked: rows[v] pairwise distinct and inside the destination, H % 4 == 0, strides % 4 == 0, 16-byte aligned bases
+static int launch_scatter_encoded_video_grad(const float *src, int64_t src_stride, const int32_t *rows, const int32_t *len, float *dst,
+                                             int64_t dst_stride, int n, int T_src, int H, int dst_rows, hipStream_t s) {
+    if (n <= 0) return 0;
+    const int dh4 = dst_rows * H / 4;
+    STAIR_ACCT("scatter_encoded_video_grad", 2ll * n * T_src * H * 4);
+    hipLaunchKernelGGL(scatter_encoded_video_grad_kernel, dim3(n, (dh4 + 2047) / 2048), dim3(256), 0, s, src, src_stride, rows, len, dst,
+                       dst_stride, dh4, H / 4, T_src);
     STAIR_LAUNCH_CHECK();
     return 0;
 }
@@ -720,7 +755,13 @@ struct stair_plan {
     const float *enc = nullptr;
     int64_t enc_stride = 0, off_encrows = 0;
     int32_t enc_rows_cap = 0;
-    int proj_vid() const { return enc_video ? 0 : n_vid; }      // the clips whose input projection the plan lays out and runs
+    // ... and, for a training plan of encoded clips, where a reverse pass puts the gradient of the encodings (stair_plan_set_encoded_video_grad;
+    // NULL: nobody asked): clip v's gradient rows at d_enc + idx[off_encrows + v] * d_enc_stride
+    float *d_enc = nullptr;
+    int64_t d_enc_stride = 0;
+    int32_t d_enc_rows_cap = 0;
+    int proj_vid() const { return enc_video ? 0 : n_vid; }      // the clips whose input projection the plan lays out and runs (and whose
+                                                                // training saves it keeps: cv, the video half of hprev, tnenc0)
     std::vector<Region> regions;   // every region of the workspace, recorded as the builder assigns it (stair_plan_regions)
     // the next `nfloats` floats of the workspace, aligned to `align` floats; recorded under `name` unless that is null
     int64_t take(const char *name, int64_t nfloats, int64_t align, int32_t index = -1) {
@@ -1411,12 +1452,13 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
             const int64_t most_rows = std::max<int64_t>((int64_t)std::max(pl->maxI, 1) * T, 64);
             pl->tnring_floats = 2 * align_up(tn_x3tr_scratch_floats(most_rows & ~31ll, H, 3 * H), 64);
             pl->o_tnring = pl->take("tnring", pl->tnring_floats, 64);
-            const int64_t rv = ((int64_t)pl->n_vid * T) & ~31ll, rq = (int64_t)pl->rows_q & ~31ll;
+            const int64_t rv = ((int64_t)pl->proj_vid() * T) & ~31ll, rq = (int64_t)pl->rows_q & ~31ll;
             const int E4 = ctx->cfg.text_size, V4 = ctx->cfg.video_size;
             pl->tnenc_floats[0] = 2 * (align_up(tn_x3tr_scratch_floats(std::max<int64_t>(rv, 64), 2 * H, H / 2), 64) +
                                        align_up(tn_x3tr_scratch_floats(std::max<int64_t>(rv, 64), 2 * H, V4), 64));
             pl->tnenc_floats[1] = 2 * (align_up(tn_x3tr_scratch_floats(std::max<int64_t>(rq, 64), 2 * H, H / 2), 64) +
                                        align_up(tn_x3tr_scratch_floats(std::max<int64_t>(rq, 64), 2 * H, E4), 64));
+            if (pl->enc_video) pl->tnenc_floats[0] = 0;      // (a plan of encoded clips has no video encoder: no weight-gradient products)
             pl->o_tnenc[0] = pl->take("tnenc", pl->tnenc_floats[0], 64, 0);
             pl->o_tnenc[1] = pl->take("tnenc", pl->tnenc_floats[1], 64, 1);
         }
@@ -1457,9 +1499,9 @@ int layout_workspace(stair_plan *pl, const stair_ctx *ctx) {
             if (w3 >= 0) { b.dzB = pl->wg_dz[w3] + at[w3] * T * H; b.svA = piece(".svA", bi, pl->wg_sx[w3] + at[w3] * T * H, (int64_t)b.cnt * T * H); at[w3] += b.cnt; }
         }
         const int64_t I = std::max(pl->maxI, 1), Vv = pl->maxV;
-        pl->o_cv = pl->take("cv", (int64_t)pl->n_vid * T * H, 64);
+        pl->o_cv = pl->take("cv", (int64_t)pl->proj_vid() * T * H, 64);
         pl->o_ct = pl->take("ct", (int64_t)pl->rows_q * H, 64);
-        pl->o_hprev = pl->take("hprev", ((int64_t)pl->n_vid * T + pl->rows_q) * H, 64);        // video rows, then text rows: the two backward passes may run side by side
+        pl->o_hprev = pl->take("hprev", ((int64_t)pl->proj_vid() * T + pl->rows_q) * H, 64);   // video rows, then text rows: the two backward passes may run side by side
         pl->o_wt = pl->take("wt", ctx_weight_floats(ctx), 64);
         pl->o_gA = pl->take("gA", I * T * H, 64);
         pl->o_gB = pl->take("gB", I * T * H, 64);
@@ -1577,8 +1619,12 @@ extern "C" int stair_plan_build_ragged(stair_ctx *ctx, int32_t n, const int32_t 
     pl->train = (flags & STAIR_PLAN_TRAIN) != 0;
     pl->ext_proj = (flags & STAIR_PLAN_EXT_PROJECTION) != 0;
     pl->enc_video = (flags & STAIR_PLAN_VIDEO_ENCODED) != 0;
-    STAIR_CHECK(!(pl->enc_video && pl->train), "STAIR_PLAN_VIDEO_ENCODED cannot be combined with STAIR_PLAN_TRAIN: a plan of encoded clips has no "
-                                               "video encoder to send gradients to (training on cached encodings is not supported)");
+    // A training plan of encoded clips exists only while all eight tensors of the video encoder are frozen: a cache of a trainable
+    // encoder would be stale after the first step (the reverse pass checks the flags again: they may change between steps)
+    STAIR_CHECK(!(pl->enc_video && pl->train) || video_encoder_frozen(ctx),
+                "STAIR_PLAN_VIDEO_ENCODED can be combined with STAIR_PLAN_TRAIN only while the video encoder is frozen: a plan of encoded "
+                "clips has no video encoder to send gradients to, and a cache of a trainable one would be stale after the first step "
+                "(training on cached encodings needs stair_ctx_set_trainable(ctx, id, 0) for all eight submodules.video_encoder.* tensors)");
     const int ntok = prog_off[n];
     pl->nodes.assign(ntok, Node());
     pl->roots.assign(n, -1);
@@ -1930,6 +1976,30 @@ extern "C" int stair_plan_set_encoded_video(stair_plan *pl, const float *enc, in
         if (pl->pin.p) pl->pin.p[pl->off_encrows + v] = rows[v];
     }
     pl->enc = enc; pl->enc_stride = clip_stride_floats; pl->enc_rows_cap = rows_cap;
+    pl->d_enc = nullptr;            // (a request for the encodings' gradient named the old rows: it is made again)
+    return 0;
+}
+
+// Request (d_enc != NULL) or withdraw (NULL) the gradient of a training plan's encodings.  Host-only; read by every later reverse pass:
+// behind the last fan-in ONE launch (scatter_encoded_video_grad_kernel, the gather's adjoint) stores plan clip v's gradient rows at
+// d_enc + rows[v] * clip_stride_floats -- rows as handed to stair_plan_set_encoded_video -- and exact zeros behind the clip's frames.
+extern "C" int stair_plan_set_encoded_video_grad(stair_plan *pl, float *d_enc, int64_t clip_stride_floats, int32_t rows_cap) {
+    STAIR_CHECK(pl, "null plan");
+    STAIR_CHECK(pl->enc_video && pl->train, "the gradient of the encodings belongs to a plan built with STAIR_PLAN_TRAIN | STAIR_PLAN_VIDEO_ENCODED");
+    if (!d_enc) { pl->d_enc = nullptr; return 0; }
+    STAIR_CHECK(pl->enc, "call stair_plan_set_encoded_video first: the gradient rows are the rows of the encodings");
+    const int64_t H = pl->cfg.hidden_size;
+    STAIR_CHECK((reinterpret_cast<uintptr_t>(d_enc) & 15) == 0 && clip_stride_floats % 4 == 0, "gradient of the encodings must be 16-byte aligned, clip stride a multiple of 4 floats");
+    STAIR_CHECK(rows_cap >= 1 && clip_stride_floats >= (int64_t)rows_cap * H, "clip stride smaller than rows_cap * hidden_size");
+    std::vector<int32_t> rows(pl->idx.begin() + pl->off_encrows, pl->idx.begin() + pl->off_encrows + pl->n_vid);
+    for (int v = 0; v < pl->n_vid; ++v)
+        STAIR_CHECK(pl->vlen[v] <= rows_cap, "video_len[" + std::to_string(v) + "] = " + std::to_string(pl->vlen[v]) +
+                                             " frames exceed the gradient's rows_cap = " + std::to_string(rows_cap));
+    std::sort(rows.begin(), rows.end());
+    for (int v = 1; v < pl->n_vid; ++v)
+        STAIR_CHECK(rows[v] != rows[v - 1], "rows are not pairwise distinct (row " + std::to_string(rows[v]) + " is named by two plan clips, which "
+                                            "would store to one gradient row): hand every distinct clip to the plan once");
+    pl->d_enc = d_enc; pl->d_enc_stride = clip_stride_floats; pl->d_enc_rows_cap = rows_cap;
     return 0;
 }
 
@@ -2629,11 +2699,20 @@ long long *stair::det_shadow(const float *g) {
 // gradient, the pass ends behind the decoder's own weight gradients.  While the video encoder's block is left out, a fused chain
 // whose input tiles are all clip tiles ends in front of its last product (STAIR_TILE_NO_DX, Bucket::ncol): nobody reads that dX.
 // With every weight trainable the pass is the one it always was.
+// A training plan of encoded clips (STAIR_PLAN_VIDEO_ENCODED) has no video encoder: `video` may be NULL, the pass is the one of a
+// frozen video encoder, and the clip tiles' gradients are produced exactly when stair_plan_set_encoded_video_grad asked for them.
 static void plan_uses(const stair_ctx *ctx, const stair_plan *pl, int32_t *used);
 static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, const float *question, void *workspace,
                          int64_t workspace_bytes, const int32_t *answers, float loss_scale, float *loss_out, const float *d_logits_in,
                          float *d_video, float *d_question, int32_t flags, stair_stream stream) {
-    STAIR_CHECK(ctx && pl && video && question && workspace && (answers || d_logits_in), "null argument");
+    STAIR_CHECK(ctx && pl && question && workspace && (answers || d_logits_in), "null argument");
+    STAIR_CHECK(video || pl->enc_video, "null argument");          // (a plan of encoded clips reads no clip features: video may be NULL)
+    // a training plan of encoded clips: the flags may have changed since the build -- refused before anything is enqueued
+    STAIR_CHECK(!pl->enc_video || video_encoder_frozen(ctx),
+                "a STAIR_PLAN_TRAIN | STAIR_PLAN_VIDEO_ENCODED plan goes backward only while the video encoder is frozen: one of its eight "
+                "tensors was made trainable after the plan was built (training on cached encodings needs a frozen video encoder)");
+    STAIR_CHECK(!(pl->enc_video && d_video), "a plan of encoded clips has no clip features to send a gradient to: d_video must be NULL "
+                                             "(stair_plan_set_encoded_video_grad requests the gradient of the encodings)");
     PolicyScope policy_scope(&ctx->policy);
     TileSwitchForce tile_scope(pl->tile_sw);               // the packing and segments of the forward pass that wrote the saves and bits
     STAIR_CHECK(pl->train, "plan was not built with STAIR_PLAN_TRAIN");
@@ -2652,7 +2731,12 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         for (int k = 0; k < 8; ++k) enc_dw[e] = enc_dw[e] || W.denc[e][k] != discard;
         enc_run[e] = enc_dw[e] || (e == 0 ? d_video : d_question) != nullptr;
     }
-    bool walk = (flags & STAIR_BWD_KEEP_ARENAS) || enc_run[0] || enc_run[1];
+    // The video encoder's two questions, stated next to each other.  Does its BPTT run: never for a plan of encoded clips (checked
+    // above: all eight tensors frozen, no d_video).  Does anyone read a clip tile's gradient: BPTT, or -- a plan of encoded clips --
+    // the gather's adjoint, exactly when the gradient of the encodings was requested (stair_plan_set_encoded_video_grad).
+    if (pl->enc_video) enc_run[0] = false;
+    const bool clip_grads = pl->enc_video ? pl->d_enc != nullptr : enc_run[0];
+    bool walk = (flags & STAIR_BWD_KEEP_ARENAS) || clip_grads || enc_run[1];
     if (!walk) {
         std::vector<int32_t> used(ctx->names.size());
         plan_uses(ctx, pl, used.data());
@@ -2849,7 +2933,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         a.W[l] = w; a.act[l] = 3; a.save[l] = save;
         if (!(a.act_bits[l] = BITS(bits))) a.act_mask[l] = mask;
     };
-    const bool nodx_on = !enc_run[0];          // nobody reads a clip tile's gradient: chains on clip tiles end before their last product
+    const bool nodx_on = !clip_grads;          // nobody reads a clip tile's gradient: chains on clip tiles end before their last product
     auto bwd_bucket = [&](const Bucket &b, const int phase) -> int {
         if (b.cnt == 0) return 0;
         const int c = b.cnt;
@@ -3094,8 +3178,8 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         if (L < 0 || L >= (int)pl->fanin_count.size() || fanin_done[L]) return 0;
         fanin_done[L] = 1;
         int first = pl->fanin_first[L], count = pl->fanin_count[L];
-        if (L == 0 && !enc_run[0]) {
-            // the clip tiles' entries (map slots 0 .. n_vid - 1: what BPTT of the video encoder reads, and nothing else) are left out;
+        if (L == 0 && !clip_grads) {
+            // the clip tiles' entries (map slots 0 .. n_vid - 1: what BPTT of the video encoder or the gather's adjoint reads, and nothing else) are left out;
             // they follow each other -- a level's entries are vec rows, map tiles in slot order, att rows (build_grad_fanin)
             int c0 = first, c1;
             auto clip = [&](int i) { return pl->fanin[5 * i] == FAN_MAP && pl->fanin[5 * i + 1] < pl->n_vid; };
@@ -3134,6 +3218,10 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     }
 
     for (int L = pl->n_levels; L >= 0; --L) RUN(fanin_level(L));        // levels without a bucket of their own (clip tiles: before BPTT)
+    // the gradient of the encodings (a plan of encoded clips, on request): the clip tiles of the map gradient arena are final here
+    if (pl->enc_video && pl->d_enc)
+        RUN(launch_scatter_encoded_video_grad(g_map, TH, didx + pl->off_encrows, didx + pl->off_lenv, pl->d_enc, pl->d_enc_stride, pl->n_vid, T, H,
+                                              pl->d_enc_rows_cap, s));
 
     // ---- the deferred weight-gradient products: one long reduction per weight -------------------------------
     // They are leaves (nothing downstream reads dW before the optimizer), and what follows on `s` -- BPTT through both encoders,
@@ -3196,13 +3284,14 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         stair_lstm_bwd_args enc[2] = {};
         for (int e = 0; e < 2; ++e) {
             stair_lstm_bwd_args &a = enc[e];
+            if (e == 0 && pl->enc_video) continue;       // (no video encoder: its block never runs, none of its regions exists)
             if (e == 0) enc_input(a, g, 0, video, (flags & STAIR_RUN_VIDEO_BF16) != 0, pl->n_vid * T, pl->n_vid, T);
             else enc_input(a, g, 1, question, false, pl->rows_q, n, pl->max_q);
             enc_recurrence(a, pl, W, e, ws, didx);
             a.gates = pl->proj_base(ws) + (e == 0 ? pl->pj.xpv : pl->pj.xpt);
             a.cbuf = ws + (e == 0 ? pl->o_cv : pl->o_ct); a.out = e == 0 ? map : ws + pl->o_tok;
             a.d_out = e == 0 ? g_map : g_tok; a.d_hn = e == 0 ? nullptr : g_qfeat; a.ldd = H;
-            a.hprev_ws = ws + pl->o_hprev + (e == 0 ? 0 : (int64_t)pl->n_vid * T * H);
+            a.hprev_ws = ws + pl->o_hprev + (e == 0 ? 0 : (int64_t)pl->proj_vid() * T * H);
             if (pl->o_tnenc[e]) { a.tn_ws = ws + pl->o_tnenc[e]; a.tn_ws_floats = pl->tnenc_floats[e]; }
             for (int d = 0; d < 2; ++d) {
                 a.dw_ih[d] = W.denc[e][4 * d]; a.dw_hh[d] = W.denc[e][4 * d + 1];
@@ -3257,7 +3346,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
 extern "C" int stair_plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, const float *question,
                                    void *workspace, int64_t workspace_bytes, const int32_t *answers, float loss_scale,
                                    float *loss_out, int32_t flags, stair_stream stream) {
-    STAIR_CHECK(ctx && pl && video && question && workspace && answers, "null argument");
+    STAIR_CHECK(ctx && pl && question && workspace && answers, "null argument");
     return plan_backward(ctx, pl, video, question, workspace, workspace_bytes, answers, loss_scale, loss_out, nullptr, nullptr, nullptr,
                          flags, stream);
 }
@@ -3266,7 +3355,8 @@ extern "C" int stair_plan_backward_dlogits(stair_ctx *ctx, stair_plan *pl, const
                                            void *workspace, int64_t workspace_bytes, const float *d_logits, float *d_video,
                                            float *d_question, int32_t flags, stair_stream stream) {
     // every argument error is reported here, before anything is enqueued
-    STAIR_CHECK(ctx && pl && video && question && workspace && d_logits, "null argument");
+    STAIR_CHECK(ctx && pl && question && workspace && d_logits, "null argument");
+    STAIR_CHECK(video || pl->enc_video, "null argument");
     STAIR_CHECK(pl->train, "plan was not built with STAIR_PLAN_TRAIN");
     STAIR_CHECK(workspace_bytes >= pl->total * (int64_t)sizeof(float), "workspace too small");
     STAIR_CHECK(((reinterpret_cast<uintptr_t>(d_logits) | reinterpret_cast<uintptr_t>(d_video) | reinterpret_cast<uintptr_t>(d_question)) & 15) == 0,
@@ -3299,6 +3389,7 @@ static void plan_uses(const stair_ctx *ctx, const stair_plan *pl, int32_t *touch
     };
     auto lin = [&](const std::string &prefix) { mark(prefix + ".weight"); mark(prefix + ".bias"); };
     for (const char *enc : {"video_encoder", "text_encoder"})
+        if (!(pl->enc_video && std::string(enc) == "video_encoder"))          // (a plan of encoded clips has no video encoder)
         for (const char *sfx : {"", "_reverse"})
             for (const char *w : {"weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"}) mark(std::string(enc) + "." + w + sfx);
     lin("decoder.0"); lin("decoder.3");

@@ -135,22 +135,35 @@ class BatchResult:
         ops._req(answers, 'answers', torch.int32)
         loss = torch.empty(self.info.n_questions, dtype=torch.float32, device=answers.device)
         self._model._bind_grads()
-        flags = (1 if keep_arenas else 0) | (RUN_VIDEO_BF16 if self._video.dtype == torch.bfloat16 else 0)
+        video = self._video             # None: a training plan of cached encodings (no clip features, no video encoder)
+        flags = (1 if keep_arenas else 0) | (RUN_VIDEO_BF16 if video is not None and video.dtype == torch.bfloat16 else 0)
         check(lib.stair_plan_set_backward_event(self._plan, C.c_void_p(ready_event.cuda_event if ready_event is not None else None)))
-        check(lib.stair_plan_backward(self._model._ctx, self._plan, C.c_void_p(self._video.data_ptr()),
+        check(lib.stair_plan_backward(self._model._ctx, self._plan, C.c_void_p(video.data_ptr() if video is not None else None),
                                       C.c_void_p(self._question.data_ptr()), C.c_void_p(self._ws.data_ptr()),
                                       self._ws.numel() * 4, C.c_void_p(answers.data_ptr()), C.c_float(loss_scale),
                                       C.c_void_p(loss.data_ptr()), flags,
                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return loss
 
-    def backward_dlogits(self, d_logits, d_video=None, d_question=None, keep_arenas=False, bind_grads=True):
+    def backward_dlogits(self, d_logits, d_video=None, d_question=None, keep_arenas=False, bind_grads=True, d_encoded=None):
         """Reverse pass of a train=True run seeded by an arbitrary logits gradient (stair_plan_backward_dlogits): d_logits
         float32 [n, A] on the GPU, already scaled.  Parameter gradients are accumulated into the model's gradient buffers
         (bind_grads=False: into the buffers the caller bound with stair_ctx_set_grad).  d_video (float32, the shape of the
         run's video) and d_question (float32 [q_rows, E]) are optional and OVERWRITTEN with the input gradients.  The pass
-        overwrites the plan's saved gates: a batch goes backward once."""
+        overwrites the plan's saved gates: a batch goes backward once.
+        A pass on encoded clips (run_programs(clips=...) / the `encoded=` form of VideoNMN.logits) has no video: d_video must be
+        None.  d_encoded (optional, float32, the shape of the encodings the plan reads) receives the gradient of the encodings
+        (stair_plan_set_encoded_video_grad): the rows of the plan's clips (clip_rows) are OVERWRITTEN -- a clip's gradient summed
+        over the questions that share it, zeros behind its frames -- and every other row is left as it is."""
         n, A = self.info.n_questions, self._model.config['answer_vocab_length']
+        if self._video is None and d_video is not None:
+            raise ValueError('a pass on encoded clips has no video to send a gradient to (d_encoded is the gradient of the encodings)')
+        if d_encoded is not None:
+            if self._enc is None:
+                raise ValueError('d_encoded belongs to a pass on encoded clips')
+            ops._req(d_encoded, 'd_encoded')
+            if tuple(d_encoded.shape) != tuple(self._enc.shape):
+                raise ValueError('d_encoded must have the shape of the encodings %s' % (tuple(self._enc.shape),))
         ops._req(d_logits, 'd_logits')
         if tuple(d_logits.shape) != (n, A):
             raise ValueError('d_logits must be [%d, %d]' % (n, A))
@@ -164,11 +177,18 @@ class BatchResult:
                 raise ValueError('d_question must have the shape of the question rows %s' % (tuple(self._question.shape),))
         if bind_grads:
             self._model._bind_grads()
-        flags = (1 if keep_arenas else 0) | (RUN_VIDEO_BF16 if self._video.dtype == torch.bfloat16 else 0)
+        flags = (1 if keep_arenas else 0) | (RUN_VIDEO_BF16 if self._video is not None and self._video.dtype == torch.bfloat16 else 0)
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
-        check(lib.stair_plan_backward_dlogits(self._model._ctx, self._plan, ptr(self._video), ptr(self._question), ptr(self._ws),
-                                              self._ws.numel() * 4, ptr(d_logits), ptr(d_video), ptr(d_question), flags,
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        if d_encoded is not None:       # the request: the plan keeps the pointer for this pass only
+            cap, H = self._enc.shape[1], self._enc.shape[2]
+            check(lib.stair_plan_set_encoded_video_grad(self._plan, ptr(d_encoded), cap * H, cap))
+        try:
+            check(lib.stair_plan_backward_dlogits(self._model._ctx, self._plan, ptr(self._video), ptr(self._question), ptr(self._ws),
+                                                  self._ws.numel() * 4, ptr(d_logits), ptr(d_video), ptr(d_question), flags,
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        finally:
+            if d_encoded is not None:
+                check(lib.stair_plan_set_encoded_video_grad(self._plan, None, 0, 0))
 
     def capture_graph(self):
         """Record this batch's forward pass (encoders, every program level, decoder, argmax) into a hipGraph and
@@ -432,22 +452,37 @@ class VideoNMN(nn.Module):
         return self._ws
 
     # ---------------------------------------------------------------------------------------
+    def _video_encoder_frozen(self):
+        """The rule of training on encoded clips: all eight tensors of the video encoder have requires_grad = False."""
+        sd = dict(self.named_parameters())
+        return not any(sd[k].requires_grad for k in self._weight_names if '.video_encoder.' in k)
+
+    def _check_encoded_training(self, train, dropout):
+        if train and not self._video_encoder_frozen():
+            raise ValueError('training on cached encodings needs a frozen video encoder: set requires_grad = False on all eight '
+                             'submodules.video_encoder.* tensors (Trainer(freeze=(\'video_encoder\',))) -- the plan has no video encoder '
+                             'to send gradients to, and a cache of a trainable one would be stale after the first step')
+        if not train and dropout is not None and dropout[0] > 0:
+            raise ValueError('dropout is a training-mode operation (train=True); this pass on cached clips is inference')
+
     def _run_cached_args(self, clips, video, video_index, video_len, n, train, dropout):
         """run_programs(clips=cache): checks, then (cache rows of the plan's clips, clip of every question, the clips' frames, T)."""
         if video is not None or video_len is not None:
-            raise ValueError('a pass on cached clips takes video=None and no video_len: the cache holds the encodings and their lengths')
-        if train:
-            raise ValueError('training on cached encodings is not supported (the plan has no video encoder to send gradients to)')
-        if dropout is not None and dropout[0] > 0:
-            raise ValueError('dropout is a training-mode operation; a pass on cached clips is inference')
+            raise ValueError('video given together with clips: a pass on cached clips takes video=None and no video_len (the cache '
+                             'holds the encodings and their lengths)')
+        self._check_encoded_training(train, dropout)
         if video_index is None:
             raise ValueError('video_index is required with clips=: the cache row of every question\'s clip')
         clips.check()
-        rows = np.ascontiguousarray(np.asarray(video_index, dtype=np.int32))
-        if rows.shape != (n,) or n == 0 or rows.min() < 0 or rows.max() >= len(clips):
-            raise ValueError('video_index must hold one row of the cache (0 .. %d) per question' % (len(clips) - 1))
         if clips.hidden_size != self.config['hidden_size'] or clips.device != next(self.parameters()).device:
             raise ValueError('the clip cache belongs to another configuration or device')
+        return self._clips_of_rows(video_index, clips.lengths, n, 'the cache')
+
+    def _clips_of_rows(self, video_index, lengths, n, what):
+        """(rows of the plan's clips, clip of every question, the clips' frames, T) for questions that name rows of `what`."""
+        rows = np.ascontiguousarray(np.asarray(video_index, dtype=np.int32))
+        if rows.shape != (n,) or n == 0 or rows.min() < 0 or rows.max() >= len(lengths):
+            raise ValueError('video_index must hold one row of %s (0 .. %d) per question' % (what, len(lengths) - 1))
         # every distinct row is ONE clip of the plan (order of first use), so that questions about one clip share its nodes
         uniq, first, index = np.unique(rows, return_index=True, return_inverse=True)
         order = np.argsort(first, kind='stable')
@@ -455,7 +490,7 @@ class VideoNMN(nn.Module):
         rank[order] = np.arange(len(order))
         used = np.ascontiguousarray(uniq[order].astype(np.int32))
         index = np.ascontiguousarray(rank[index].astype(np.int32))
-        lens = np.ascontiguousarray(clips.lengths[used])
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32)[used])
         T = int(lens.max())
         if self.config['max_video_length'] <= 32:       # Linear(T,T) Temporal nets fix T (modules.py:266-277): the reference crashes on any other clip
             T = self.config['max_video_length']
@@ -490,12 +525,16 @@ class VideoNMN(nn.Module):
         names the CACHE ROW of every question's clip, in any order and with repeats; every distinct row becomes one clip of the
         plan (BatchResult.clip_rows), which runs no video encoder: one launch copies the cached rows into the map arena
         (STAIR_PLAN_VIDEO_ENCODED).  The plan's T is the longest clip used (max_video_length for the Linear-Temporal
-        configurations, which admit no other length).  Inference only: train=True and dropout raise ValueError, and so does a
-        cache whose encoder weights or matmul mode are no longer the model's (ClipCache.check)."""
+        configurations, which admit no other length).  train=True (with dropout=, before_run= as on clips) is admitted while
+        all eight tensors of the video encoder are frozen (requires_grad = False) and raises ValueError otherwise: the training
+        plan keeps none of the encoder's saves, the reverse pass is the frozen-encoder pass, the encoder's tensors report
+        untouched and the cache stays fresh.  dropout with train=False raises ValueError, and so does a cache whose encoder
+        weights or matmul mode are no longer the model's (ClipCache.check)."""
         n = len(programs)
         if clips is not None:
             return self._run_cached(programs, spans, question, q_lens, before_run, cse, clips,
-                                    *self._run_cached_args(clips, video, video_index, video_len, n, train, dropout))
+                                    *self._run_cached_args(clips, video, video_index, video_len, n, train, dropout),
+                                    train=train, dropout=dropout)
         if video_index is not None:
             video_index = np.ascontiguousarray(np.asarray(video_index, dtype=np.int32))
             if video_index.shape != (n,):
@@ -576,11 +615,16 @@ class VideoNMN(nn.Module):
             res.logits = ws[info.logits_off: info.logits_off + n * A].view(n, A).clone()    # (n x A floats) that survives the next step
         return res
 
-    def _run_cached(self, programs, spans, question, q_lens, before_run, cse, clips, used, index, lens, T):
-        """The pass of run_programs on a ClipCache: `used` = cache rows of the plan's clips, `index` = clip of every question."""
+    def _run_cached(self, programs, spans, question, q_lens, before_run, cse, clips, used, index, lens, T, train=False, dropout=None,
+                    enc=None):
+        """The pass of run_programs on a ClipCache: `used` = cache rows of the plan's clips, `index` = clip of every question.
+        enc (in place of clips): the encodings themselves, [n_clips, rows_cap, H] float32 on the device (VideoNMN.logits(encoded=))."""
         n, dev = len(programs), question.device
         ops._req(question, 'question')
         self._bind_weights()
+        if train:
+            self._sync_trainable()              # (the builder, BatchResult.touched() and the reverse pass go by the context's flags)
+        drop_on = dropout is not None and dropout[0] > 0
         stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
         proj = None
         if self.early_projection and question.shape[0] > 0:       # the text projection alone, ahead of the plan (n_videos = 0)
@@ -597,12 +641,16 @@ class VideoNMN(nn.Module):
         plan = C.c_void_p()
         check(lib.stair_plan_build_ragged(self._ctx, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), len(used), ip(index),
                                           ip(lens) if ragged else None, T,
-                                          PLAN_VIDEO_ENCODED | (0 if cse else 2) | (PLAN_EXT_PROJECTION if proj is not None else 0), C.byref(plan)))
+                                          PLAN_VIDEO_ENCODED | (1 if train else 0) | (0 if cse and not drop_on else 2) |
+                                          (PLAN_EXT_PROJECTION if proj is not None else 0), C.byref(plan)))
         try:
             info = PlanInfo()
             check(lib.stair_plan_get_info(plan, C.byref(info)))
-            enc = clips.enc
-            check(lib.stair_plan_set_encoded_video(plan, C.c_void_p(enc.data_ptr()), clips.rows_cap * clips.hidden_size, clips.rows_cap, ip(used)))
+            if drop_on:
+                check(lib.stair_plan_set_dropout(plan, C.c_float(float(dropout[0])), C.c_uint64(int(dropout[1]) & (2 ** 64 - 1))))
+            if enc is None:
+                enc = clips.enc
+            check(lib.stair_plan_set_encoded_video(plan, C.c_void_p(enc.data_ptr()), enc.shape[1] * enc.shape[2], enc.shape[1], ip(used)))
             ws = self._workspace(info.workspace_bytes, dev)
             if proj is not None:
                 check(lib.stair_plan_set_projection(self._ctx, plan, C.c_void_p(proj.data_ptr()), proj.numel()))
@@ -620,6 +668,9 @@ class VideoNMN(nn.Module):
         check(lib.stair_plan_run_flags(self._ctx, plan, None, C.c_void_p(question.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel() * 4,
                                        C.c_void_p(logits.data_ptr()), C.c_void_p(pred.data_ptr()), RUN_PROJECTED if proj is not None else 0,
                                        stream()))
+        if train:       # as in run_programs: the plan's logits stay in the workspace for the backward pass, the caller gets a copy
+            A = self.config['answer_vocab_length']
+            res.logits = ws[info.logits_off: info.logits_off + n * A].view(n, A).clone()
         return res
 
     def _matmul_mode_now(self):
@@ -671,19 +722,65 @@ class VideoNMN(nn.Module):
         cache.add(clips, ids=ids, video_len=video_len, batch_size=batch_size)
         return cache
 
-    def logits(self, programs, spans, video, question, q_lens, video_index=None, video_len=None, dropout=None, cse=True):
+    def _encoded_args(self, encoded, video_index, video_len, n):
+        """logits(encoded=enc): checks, then (rows of the plan's clips, clip of every question, the clips' frames, T)."""
+        dev, H = next(self.parameters()).device, self.config['hidden_size']
+        if not isinstance(encoded, torch.Tensor) or encoded.dim() != 3 or encoded.shape[2] != H or encoded.shape[0] == 0 or encoded.shape[1] == 0:
+            raise ValueError('encoded must be a float32 [n_clips, T, %d] tensor of clip encodings, got shape %s'
+                             % (H, tuple(getattr(encoded, 'shape', ()))))
+        if encoded.device != dev or encoded.dtype != torch.float32 or not encoded.is_contiguous():
+            raise ValueError('encoded must be a contiguous float32 tensor on the model\'s device %s' % (dev,))
+        if encoded.shape[1] > self.config['max_video_length']:
+            raise ValueError('encoded holds %d frames per clip, max_video_length is %d' % (encoded.shape[1], self.config['max_video_length']))
+        n_clips, cap = encoded.shape[0], encoded.shape[1]
+        if video_index is None:
+            if n_clips != n:
+                raise ValueError('video_index is required when encoded holds another number of clips than there are questions')
+            video_index = np.arange(n, dtype=np.int32)
+        lengths = np.full(n_clips, cap, np.int32) if video_len is None else np.ascontiguousarray(np.asarray(video_len, dtype=np.int32))
+        if lengths.shape != (n_clips,) or lengths.min() < 1 or lengths.max() > cap:
+            raise ValueError('video_len must hold the frames (1 .. %d) of each of the %d encoded clips' % (cap, n_clips))
+        return self._clips_of_rows(video_index, lengths, n, 'encoded')
+
+    def logits(self, programs, spans, video, question, q_lens, video_index=None, video_len=None, dropout=None, cse=True, clips=None,
+               encoded=None):
         """[n, A] logits of a batch (arguments as for run_programs) with a torch autograd graph: when grad mode is on and any
         parameter, `video` or `question` requires grad, the result has a grad_fn whose backward runs the native reverse pass
         seeded by the logits gradient (stair_amd.autograd.PlanLogits) -- parameter gradients, and input gradients for `video`
         (fp32 or bf16) / `question` when they require grad.  A batch goes backward once; double backward is not supported.
-        Otherwise an inference plan runs (dropout does not apply there) and the logits are those of run_programs."""
+        Otherwise an inference plan runs (dropout does not apply there) and the logits are those of run_programs.
+
+        On encoded clips (video=None; the differentiable forms need the video encoder frozen, ValueError otherwise):
+        clips=cache, video_index = the cache row of every question's clip -- autograd over a ClipCache; no gradient goes to the cache.
+        encoded=enc, a float32 [n_clips, T, H] tensor on the GPU (the output of a clip encoder of the caller's own, in torch),
+        video_index [n] (optional when n_clips == n) = the clip of every question, video_len [n_clips] (optional) = the clips'
+        frames.  When enc requires grad it receives a gradient of its own shape: a clip's gradient is summed over the questions
+        that share it, zero behind its video_len and zero for clips that no question reads."""
         params = [dict(self.named_parameters())[n] for n in self._weight_names]
+        if clips is not None or encoded is not None:
+            if video is not None or (clips is not None and encoded is not None):
+                raise ValueError('video given together with clips= / encoded=: a pass on encoded clips takes video=None and one of the two')
+            src = encoded
+            grad = torch.is_grad_enabled() and (question.requires_grad or any(p.requires_grad for p in params) or
+                                                (isinstance(src, torch.Tensor) and src.requires_grad))
+            if clips is not None:
+                plan_clips = self._run_cached_args(clips, None, video_index, video_len, len(programs), grad, dropout if grad else None)
+            else:
+                self._check_encoded_training(grad, dropout if grad else None)
+                plan_clips = self._encoded_args(encoded, video_index, video_len, len(programs))
+            if not grad:
+                with torch.no_grad():
+                    return self._run_cached(programs, spans, question, q_lens, None, cse, clips, *plan_clips,
+                                            enc=None if src is None else src.detach()).logits
+            from .autograd import PlanLogits
+            call = (programs, spans, q_lens, video_index, video_len, dropout, cse, clips, plan_clips)
+            return PlanLogits.apply(self, call, src, question, *params)
         if not (torch.is_grad_enabled() and (video.requires_grad or question.requires_grad or any(p.requires_grad for p in params))):
             with torch.no_grad():
                 return self.run_programs(programs, spans, video, question, q_lens, video_index=video_index, video_len=video_len,
                                          cse=cse).logits
         from .autograd import PlanLogits
-        call = (programs, spans, q_lens, video_index, video_len, dropout, cse)
+        call = (programs, spans, q_lens, video_index, video_len, dropout, cse, None, None)
         return PlanLogits.apply(self, call, video, question, *params)
 
     def forward_batch(self, batch, train=False, share_videos=True, dropout=None, cse=True, clip_cache=None):
@@ -697,7 +794,8 @@ class VideoNMN(nn.Module):
         `video_features` occupy (or by a `video_id` entry, when every dict carries one).
 
         clip_cache (a ClipCache of encode_clips): the clips are looked up by d['video_id'] and not encoded again (their
-        'video_features' are not read); an id the cache does not hold raises KeyError naming it."""
+        'video_features' are not read); an id the cache does not hold raises KeyError naming it.  With train=True the video
+        encoder must be frozen (see run_programs, `clips`)."""
         dev = next(self.parameters()).device
         if clip_cache is not None:
             rows = clip_cache.rows([d['video_id'] for d in batch])

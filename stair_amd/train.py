@@ -262,14 +262,21 @@ class Trainer:
         return end if self.iters > total else start + (end - start) / total * self.iters
 
     def step(self, programs, spans, video, question, q_lens, answers, global_batch=None, questions=None, video_index=None,
-             video_len=None):
+             video_len=None, clips=None):
         """One optimizer step over this rank's shard of a window.  `questions` -- the dicts, with 'sg_res_by_step', or their
         losses.GoldBatch (losses.collate_gold: the data loader's collate step; the per-question bookkeeping then costs the stepping
         process nothing) -- switches the per-module intermediate losses on (train_module.py:351-373, 388-406).
         video_index: questions that share a clip (see VideoNMN.run_programs).
+        clips (a ClipCache of VideoNMN.encode_clips, with video=None and video_index = the cache row of every question's clip): the
+        step runs on the cached encodings -- no video projection, no video recurrence, none of the encoder's training saves.  The
+        video encoder must be frozen (Trainer(freeze=('video_encoder',)) / requires_grad = False on its eight tensors), else
+        ValueError before anything is enqueued; its tensors report untouched and keep weights, moments, step counts and torch
+        version, so the cache is still fresh after the step.
         Returns (per-question decoder CE of the local shard, BatchResult)."""
         from . import losses as L
         n = len(programs)
+        if clips is not None:                                 # refused here: nothing of the step has been enqueued or counted yet
+            self.model._run_cached_args(clips, video, video_index, video_len, n, True, None)
         if global_batch is None:
             global_batch = self.global_batch
         if global_batch is None and self.world > 1:           # ragged shards: the window is the SUM of the shard sizes
@@ -299,7 +306,7 @@ class Trainer:
                                                 window=self.contrastive_window, world=self.world, rank=self.rank,
                                                 class_table=self.class_table, global_batch=G)
         res = self.model.run_programs(programs, spans, video, question, q_lens, train=True, video_index=video_index, dropout=drop,
-                                      video_len=video_len, before_run=prepare if supervised else None)
+                                      video_len=video_len, before_run=prepare if supervised else None, clips=clips)
         extra = set()
         trainable = list(self.model._trainable)               # requires_grad of this step (run_programs has synced it into the context)
         tl = res.touched()                                    # known from the plan: uploaded BEFORE the backward pass is enqueued
