@@ -35,28 +35,26 @@ _SEG = 64          # gradient buffers start on 256-byte boundaries inside one fl
 
 
 class PlanLogits(torch.autograd.Function):
-    """apply(model, call, video, question, *params) -> logits [n, A]; `call` = (programs, spans, q_lens, video_index, video_len,
-    dropout, cse, clips, plan_clips) as for ``VideoNMN.run_programs``; `params` in the order of ``model._weight_names``.  On encoded
-    clips (``VideoNMN.logits(clips=...)`` / ``(encoded=...)``) plan_clips is what ``VideoNMN._clips_of_rows`` returned and `video`
-    is None (a ClipCache: no gradient goes to it) or the encodings [n_clips, T, H], whose gradient comes back in their shape."""
+    """apply(model, call, video, question, *params) -> logits [n, A]; `call` = (programs, spans, q_lens, dropout, cse, src) as for
+    ``VideoNMN.run_programs``, src the pass's ``ClipSource``; `params` in the order of ``model._weight_names``.  `video` is the
+    tensor of the source that autograd sees: the clip features, or on encoded clips (``VideoNMN.logits(clips=...)`` /
+    ``(encoded=...)``) None (a ClipCache: no gradient goes to it) or the encodings [n_clips, T, H], whose gradient comes back in
+    their shape."""
 
     @staticmethod
     def forward(ctx, model, call, video, question, *params):
-        programs, spans, q_lens, video_index, video_len, dropout, cse, clips, plan_clips = call
+        programs, spans, q_lens, dropout, cse, src = call
+        if video is not None:
+            src = src.with_tensor(video.detach())
         shared = model._ws, model._proj
-        model._ws = model._proj = None           # run_programs allocates buffers for THIS batch; the shared ones are put back
+        model._ws = model._proj = None           # the pass allocates buffers for THIS batch; the shared ones are put back
         try:
-            if plan_clips is not None:           # encoded clips: a ClipCache (video is None), or the encodings themselves as `video`
-                res = model._run_cached(programs, spans, question.detach(), q_lens, None, cse, clips, *plan_clips, train=True,
-                                        dropout=dropout, enc=None if video is None else video.detach())
-            else:
-                res = model.run_programs(programs, spans, video.detach(), question.detach(), q_lens, train=True, video_index=video_index,
-                                         dropout=dropout, video_len=video_len, cse=cse)
+            res = model._run(src, programs, spans, question.detach(), q_lens, True, dropout, None, cse)
         finally:
             model._ws, model._proj = shared
         ctx.model, ctx.res = model, res
         ctx.video_dtype = video.dtype if video is not None else None
-        ctx.encoded = plan_clips is not None
+        ctx.encoded = src.video is None
         return res.logits
 
     @staticmethod

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from typing import Any, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -29,6 +30,35 @@ from ._lib import PlanInfo, StairConfig, StairError, check, lib
 VAL_STR, VAL_VEC, VAL_MAP, VAL_ATT, VAL_FRAME, VAL_PAIR = range(6)
 RUN_INDEX_RESIDENT, RUN_VIDEO_BF16, RUN_PROJECTED = 1, 2, 4          # stair_plan_run_flags / stair_plan_backward flags (include/stair_hip.h)
 PLAN_EXT_PROJECTION, PLAN_VIDEO_ENCODED = 4, 8                       # stair_plan_build* flags
+
+
+class ClipSource(NamedTuple):
+    """Where a plan's clip tiles come from: clip features that the plan's own video encoder reads (`video`), or encodings made
+    before -- a ClipCache's or the caller's own (`enc`) -- of which the plan gathers the rows `rows` and runs no video encoder.
+    Made by VideoNMN._clip_source, which carries the checks of each form; the pass (VideoNMN._run) only reads it."""
+    video: Optional[torch.Tensor]       # [n_videos, T, V] clip features, fp32 or bf16; None on encoded clips
+    enc: Optional[torch.Tensor]         # [n_clips, rows_cap, H] encodings the plan gathers from; None on clip features
+    cache: Any                          # the ClipCache that owns enc, kept alive for the plan (it holds enc's address); else None
+    rows: Optional[np.ndarray]          # int32 [n_videos]: the row of enc of every plan clip (map slot v = row rows[v]); else None
+    n_videos: int                       # clips of the plan
+    index: Optional[np.ndarray]         # int32 [n]: the plan clip of every question; None: question q asks about clip q
+    lens: Optional[np.ndarray]          # int32 [n_videos]: frames of every plan clip; None: all of them have T
+    T: int
+
+    def video_arg(self):
+        """(the clip features' address or NULL, RUN_VIDEO_BF16 or 0): the video arguments of every run and reverse-pass call."""
+        v = self.video
+        return C.c_void_p(v.data_ptr() if v is not None else None), RUN_VIDEO_BF16 if v is not None and v.dtype == torch.bfloat16 else 0
+
+    def with_tensor(self, t):
+        """The same source reading its tensor -- the clip features, else the encodings -- from `t` (autograd hands in a detached one)."""
+        return self._replace(video=t) if self.video is not None else self._replace(enc=t)
+
+    def question_frames(self):
+        """[n] frames of every question's clip when the clips differ in length, else None (all T)."""
+        if self.lens is None:
+            return None
+        return self.lens[self.index] if self.index is not None else self.lens
 
 
 class L2Normalize(nn.Module):
@@ -92,15 +122,16 @@ class BatchResult:
     question_feature, grad_arena() -- is a VIEW into the model's shared workspace and is overwritten by the next
     run_programs / forward_batch / Trainer.step on the same model: clone what must outlive it (VideoNMN.forward does)."""
 
-    def __init__(self, model, plan, info, ws, logits, pred, prog_off, programs, video=None, question=None):
+    def __init__(self, model, plan, info, ws, logits, pred, prog_off, programs, src, question, proj):
         self._model, self._plan, self.info, self._ws = model, plan, info, ws
         self.logits, self.pred = logits, pred
         self._prog_off, self._programs = prog_off, programs
-        self._video, self._question = video, question
-        self.question_frames = None          # [n] frames per question when the batch mixes clip lengths, else None (all info.T)
-        # a pass on cached encodings (run_programs(clips=...)): the cache and its tensor, kept alive for the plan (it holds their
-        # address), and the cache row of every plan clip (map slot v = cache row clip_rows[v]); video is None then
-        self._clips = self._enc = self.clip_rows = None
+        self._src, self._question, self._proj = src, question, proj
+        self._video = src.video
+        self.question_frames = src.question_frames()    # the loss driver masks its criteria with them
+        # a pass on encoded clips (run_programs(clips=...), logits(encoded=...)): the cache and the encodings, kept alive for the plan
+        # (it holds their address), and the row of every plan clip (map slot v = row clip_rows[v]); video is None then
+        self._clips, self._enc, self.clip_rows = src.cache, src.enc, src.rows
 
     def status_word(self):
         """The plan's status word (int32 view of one workspace element): 0 = every pass on this workspace since run_programs
@@ -135,13 +166,12 @@ class BatchResult:
         ops._req(answers, 'answers', torch.int32)
         loss = torch.empty(self.info.n_questions, dtype=torch.float32, device=answers.device)
         self._model._bind_grads()
-        video = self._video             # None: a training plan of cached encodings (no clip features, no video encoder)
-        flags = (1 if keep_arenas else 0) | (RUN_VIDEO_BF16 if video is not None and video.dtype == torch.bfloat16 else 0)
+        video, bf16 = self._src.video_arg()     # NULL: a training plan of encoded clips (no clip features, no video encoder)
         check(lib.stair_plan_set_backward_event(self._plan, C.c_void_p(ready_event.cuda_event if ready_event is not None else None)))
-        check(lib.stair_plan_backward(self._model._ctx, self._plan, C.c_void_p(video.data_ptr() if video is not None else None),
+        check(lib.stair_plan_backward(self._model._ctx, self._plan, video,
                                       C.c_void_p(self._question.data_ptr()), C.c_void_p(self._ws.data_ptr()),
                                       self._ws.numel() * 4, C.c_void_p(answers.data_ptr()), C.c_float(loss_scale),
-                                      C.c_void_p(loss.data_ptr()), flags,
+                                      C.c_void_p(loss.data_ptr()), (1 if keep_arenas else 0) | bf16,
                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return loss
 
@@ -177,14 +207,15 @@ class BatchResult:
                 raise ValueError('d_question must have the shape of the question rows %s' % (tuple(self._question.shape),))
         if bind_grads:
             self._model._bind_grads()
-        flags = (1 if keep_arenas else 0) | (RUN_VIDEO_BF16 if self._video is not None and self._video.dtype == torch.bfloat16 else 0)
+        video, bf16 = self._src.video_arg()
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
         if d_encoded is not None:       # the request: the plan keeps the pointer for this pass only
             cap, H = self._enc.shape[1], self._enc.shape[2]
             check(lib.stair_plan_set_encoded_video_grad(self._plan, ptr(d_encoded), cap * H, cap))
         try:
-            check(lib.stair_plan_backward_dlogits(self._model._ctx, self._plan, ptr(self._video), ptr(self._question), ptr(self._ws),
-                                                  self._ws.numel() * 4, ptr(d_logits), ptr(d_video), ptr(d_question), flags,
+            check(lib.stair_plan_backward_dlogits(self._model._ctx, self._plan, video, ptr(self._question), ptr(self._ws),
+                                                  self._ws.numel() * 4, ptr(d_logits), ptr(d_video), ptr(d_question),
+                                                  (1 if keep_arenas else 0) | bf16,
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         finally:
             if d_encoded is not None:
@@ -294,7 +325,7 @@ class CapturedPlan:
         dev = res._question.device
         self._ws = torch.empty((info.workspace_bytes + 3) // 4, dtype=torch.float32, device=dev)
         self._proj = None
-        if getattr(res, '_proj', None) is not None:       # the plan keeps its projections outside the workspace: a private buffer too
+        if res._proj is not None:       # the plan keeps its projections outside the workspace: a private buffer too
             self._proj = torch.empty(res._proj.numel(), dtype=torch.float32, device=dev)     # (the replay recomputes them: no RUN_PROJECTED)
             check(lib.stair_plan_set_projection(model._ctx, res._plan, C.c_void_p(self._proj.data_ptr()), self._proj.numel()))
         self.logits, self.pred = res.logits, res.pred
@@ -312,12 +343,11 @@ class CapturedPlan:
 
     def _enqueue(self, stream):
         res = self.result
-        video = res._video              # None: a plan of cached encodings (the index image uploaded above names their rows)
-        check(lib.stair_plan_run_flags(res._model._ctx, res._plan, C.c_void_p(video.data_ptr() if video is not None else None),
+        video, bf16 = res._src.video_arg()      # NULL: a plan of cached encodings (the index image uploaded above names their rows)
+        check(lib.stair_plan_run_flags(res._model._ctx, res._plan, video,
                                        C.c_void_p(res._question.data_ptr()), C.c_void_p(self._ws.data_ptr()),
                                        self._ws.numel() * 4, C.c_void_p(self.logits.data_ptr()),
-                                       C.c_void_p(self.pred.data_ptr()),
-                                       RUN_INDEX_RESIDENT | (RUN_VIDEO_BF16 if video is not None and video.dtype == torch.bfloat16 else 0),
+                                       C.c_void_p(self.pred.data_ptr()), RUN_INDEX_RESIDENT | bf16,
                                        C.c_void_p(stream.cuda_stream)))
 
     def replay(self):
@@ -457,26 +487,85 @@ class VideoNMN(nn.Module):
         sd = dict(self.named_parameters())
         return not any(sd[k].requires_grad for k in self._weight_names if '.video_encoder.' in k)
 
-    def _check_encoded_training(self, train, dropout):
-        if train and not self._video_encoder_frozen():
+    def _check_mode(self, encoded, train, dropout):
+        """The mode rules of a pass, applied before anything is built: training on encoded clips needs the video encoder frozen,
+        dropout needs train=True."""
+        if encoded and train and not self._video_encoder_frozen():
             raise ValueError('training on cached encodings needs a frozen video encoder: set requires_grad = False on all eight '
                              'submodules.video_encoder.* tensors (Trainer(freeze=(\'video_encoder\',))) -- the plan has no video encoder '
                              'to send gradients to, and a cache of a trainable one would be stale after the first step')
         if not train and dropout is not None and dropout[0] > 0:
-            raise ValueError('dropout is a training-mode operation (train=True); this pass on cached clips is inference')
+            raise ValueError('dropout is a training-mode operation (train=True)' +
+                             ('; this pass on cached clips is inference' if encoded else ''))
 
-    def _run_cached_args(self, clips, video, video_index, video_len, n, train, dropout):
-        """run_programs(clips=cache): checks, then (cache rows of the plan's clips, clip of every question, the clips' frames, T)."""
+    def _clip_source(self, n, video, video_index, video_len, clips=None, encoded=None, train=False, dropout=None):
+        """The ClipSource of a pass over n questions, one public form each: clips= (a ClipCache), encoded= (caller-made encodings),
+        else video.  Checks everything that can be refused before a plan exists; enqueues nothing."""
+        if clips is not None:
+            return self._source_of_cache(n, clips, video, video_index, video_len, train, dropout)
+        if encoded is not None:
+            return self._source_of_encodings(n, encoded, video_index, video_len, train, dropout)
+        return self._source_of_video(n, video, video_index, video_len, train, dropout)
+
+    def _source_of_video(self, n, video, video_index, video_len, train, dropout):
+        if video_index is not None:
+            video_index = np.ascontiguousarray(np.asarray(video_index, dtype=np.int32))
+            if video_index.shape != (n,):
+                raise ValueError('video_index must have one entry per question')
+            if video.dim() != 3 or n == 0 or video_index.min() < 0 or video_index.max() >= video.shape[0]:
+                raise ValueError('video must be [n_videos, T, V] and video_index must point into it')
+        elif video.dim() != 3 or video.shape[0] != n:
+            raise ValueError('video must be [n, T, V]')
+        # clip features: fp32, or the stored bf16 format of BASELINE.json configs[1] (video.dtype == torch.bfloat16): the
+        # input projection of the video encoder then runs on the bf16 rows directly (two MFMA products per operand pair)
+        ops._req(video, 'video', torch.bfloat16 if video.dtype == torch.bfloat16 else torch.float32)
+        if video.dtype == torch.bfloat16 and self.config['video_size'] % 32:
+            raise ValueError('bf16 clip features need video_size % 32 == 0')
+        T = video.shape[1]
+        if video_len is not None:
+            video_len = np.ascontiguousarray(np.asarray(video_len, dtype=np.int32))
+            if video_len.shape != (video.shape[0],):
+                raise ValueError('video_len must have one entry per clip')
+            if bool((video_len == T).all()):
+                video_len = None
+        self._check_mode(False, train, dropout)
+        return ClipSource(video, None, None, None, video.shape[0], video_index, video_len, T)
+
+    def _source_of_cache(self, n, clips, video, video_index, video_len, train, dropout):
         if video is not None or video_len is not None:
             raise ValueError('video given together with clips: a pass on cached clips takes video=None and no video_len (the cache '
                              'holds the encodings and their lengths)')
-        self._check_encoded_training(train, dropout)
+        self._check_mode(True, train, dropout)
         if video_index is None:
             raise ValueError('video_index is required with clips=: the cache row of every question\'s clip')
         clips.check()
         if clips.hidden_size != self.config['hidden_size'] or clips.device != next(self.parameters()).device:
             raise ValueError('the clip cache belongs to another configuration or device')
-        return self._clips_of_rows(video_index, clips.lengths, n, 'the cache')
+        return self._source_of_rows(clips.enc, clips, video_index, clips.lengths, n, 'the cache')
+
+    def _source_of_encodings(self, n, encoded, video_index, video_len, train, dropout):
+        self._check_mode(True, train, dropout)
+        dev, H = next(self.parameters()).device, self.config['hidden_size']
+        if not isinstance(encoded, torch.Tensor) or encoded.dim() != 3 or encoded.shape[2] != H or encoded.shape[0] == 0 or encoded.shape[1] == 0:
+            raise ValueError('encoded must be a float32 [n_clips, T, %d] tensor of clip encodings, got shape %s'
+                             % (H, tuple(getattr(encoded, 'shape', ()))))
+        if encoded.device != dev or encoded.dtype != torch.float32 or not encoded.is_contiguous():
+            raise ValueError('encoded must be a contiguous float32 tensor on the model\'s device %s' % (dev,))
+        if encoded.shape[1] > self.config['max_video_length']:
+            raise ValueError('encoded holds %d frames per clip, max_video_length is %d' % (encoded.shape[1], self.config['max_video_length']))
+        n_clips, cap = encoded.shape[0], encoded.shape[1]
+        if video_index is None:
+            if n_clips != n:
+                raise ValueError('video_index is required when encoded holds another number of clips than there are questions')
+            video_index = np.arange(n, dtype=np.int32)
+        lengths = np.full(n_clips, cap, np.int32) if video_len is None else np.ascontiguousarray(np.asarray(video_len, dtype=np.int32))
+        if lengths.shape != (n_clips,) or lengths.min() < 1 or lengths.max() > cap:
+            raise ValueError('video_len must hold the frames (1 .. %d) of each of the %d encoded clips' % (cap, n_clips))
+        return self._source_of_rows(encoded, None, video_index, lengths, n, 'encoded')
+
+    def _source_of_rows(self, enc, cache, video_index, lengths, n, what):
+        used, index, lens, T = self._clips_of_rows(video_index, lengths, n, what)
+        return ClipSource(None, enc, cache, used, len(used), index, lens if bool((lens != T).any()) else None, T)
 
     def _clips_of_rows(self, video_index, lengths, n, what):
         """(rows of the plan's clips, clip of every question, the clips' frames, T) for questions that name rows of `what`."""
@@ -530,147 +619,65 @@ class VideoNMN(nn.Module):
         plan keeps none of the encoder's saves, the reverse pass is the frozen-encoder pass, the encoder's tensors report
         untouched and the cache stays fresh.  dropout with train=False raises ValueError, and so does a cache whose encoder
         weights or matmul mode are no longer the model's (ClipCache.check)."""
-        n = len(programs)
-        if clips is not None:
-            return self._run_cached(programs, spans, question, q_lens, before_run, cse, clips,
-                                    *self._run_cached_args(clips, video, video_index, video_len, n, train, dropout),
-                                    train=train, dropout=dropout)
-        if video_index is not None:
-            video_index = np.ascontiguousarray(np.asarray(video_index, dtype=np.int32))
-            if video_index.shape != (n,):
-                raise ValueError('video_index must have one entry per question')
-            if video.dim() != 3 or n == 0 or video_index.min() < 0 or video_index.max() >= video.shape[0]:
-                raise ValueError('video must be [n_videos, T, V] and video_index must point into it')
-        elif video.dim() != 3 or video.shape[0] != n:
-            raise ValueError('video must be [n, T, V]')
-        # clip features: fp32, or the stored bf16 format of BASELINE.json configs[1] (video.dtype == torch.bfloat16): the
-        # input projection of the video encoder then runs on the bf16 rows directly (two MFMA products per operand pair)
-        ops._req(video, 'video', torch.bfloat16 if video.dtype == torch.bfloat16 else torch.float32)
-        ops._req(question, 'question')
-        if video.dtype == torch.bfloat16 and self.config['video_size'] % 32:
-            raise ValueError('bf16 clip features need video_size % 32 == 0')
-        T = video.shape[1]
-        self._bind_weights()
-        if train:
-            self._sync_trainable()              # (BatchResult.touched() and the reverse pass go by the context's flags)
-        # The encoders' input projections need the inputs only: enqueue them BEFORE packing the programs and building the plan (3-4 ms
-        # of host work at 2048 questions), so the device is busy meanwhile (stair_encoders_project; results bit-identical)
-        proj = None
-        if self.early_projection and n > 0 and video.shape[0] > 0 and question.shape[0] > 0:
-            nf = int(lib.stair_projection_floats(self._ctx, video.shape[0], T, question.shape[0]))
-            proj = self._projection(nf, video.device)
-            check(lib.stair_encoders_project(self._ctx, C.c_void_p(video.data_ptr()), 1 if video.dtype == torch.bfloat16 else 0,
-                                             video.shape[0], T, C.c_void_p(question.data_ptr()), question.shape[0],
-                                             C.c_void_p(proj.data_ptr()), proj.numel(), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        cache = self._programs
-        compiled = [cache.get(p, sp) for p, sp in zip(programs, spans)]       # packed once per distinct (program, spans)
-        prog_off, tokens, lo, hi, q_off = frontend.pack_batch(compiled, q_lens)
-        if question.shape[0] != int(q_off[-1]):
-            raise ValueError('question rows (%d) != sum(q_lens) (%d)' % (question.shape[0], int(q_off[-1])))
+        src = self._clip_source(len(programs), video, video_index, video_len, clips, None, train, dropout)
+        return self._run(src, programs, spans, question, q_lens, train, dropout, before_run, cse)
 
-        def ip(a):
-            return a.ctypes.data_as(C.POINTER(C.c_int32))
-        plan = C.c_void_p()
-        # under dropout every occurrence of a node draws its own mask (module_net.py:100-106 in model.train()): nothing is shared
-        drop_on = dropout is not None and dropout[0] > 0
-        if video_len is not None:
-            video_len = np.ascontiguousarray(np.asarray(video_len, dtype=np.int32))
-            if video_len.shape != (video.shape[0],):
-                raise ValueError('video_len must have one entry per clip')
-            if bool((video_len == T).all()):
-                video_len = None
-        check(lib.stair_plan_build_ragged(self._ctx, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), video.shape[0],
-                                          ip(video_index) if video_index is not None else None,
-                                          ip(video_len) if video_len is not None else None, T,
-                                          (1 if train else 0) | (0 if cse and not drop_on else 2) | (PLAN_EXT_PROJECTION if proj is not None else 0),
-                                          C.byref(plan)))
-        try:
-            info = PlanInfo()
-            check(lib.stair_plan_get_info(plan, C.byref(info)))
-            if dropout is not None and dropout[0] > 0:
-                if not train:
-                    raise ValueError('dropout is a training-mode operation (train=True)')
-                check(lib.stair_plan_set_dropout(plan, C.c_float(float(dropout[0])), C.c_uint64(int(dropout[1]) & (2 ** 64 - 1))))
-            ws = self._workspace(info.workspace_bytes, video.device)
-            if proj is not None:
-                check(lib.stair_plan_set_projection(self._ctx, plan, C.c_void_p(proj.data_ptr()), proj.numel()))
-            A = self.config['answer_vocab_length']
-            logits = torch.empty(n, A, dtype=torch.float32, device=video.device)
-            pred = torch.empty(n, dtype=torch.int32, device=video.device)
-        except Exception:
-            lib.stair_plan_destroy(plan)
-            raise
-        res = BatchResult(self, plan, info, ws, logits, pred, prog_off, programs, video, question)     # owns the plan from here on
-        res._proj = proj
-        if video_len is not None:       # frames of every question's clip (the loss driver masks its criteria with them)
-            res.question_frames = video_len[video_index] if video_index is not None else video_len
-        if before_run is not None:
-            before_run(res)
-        check(lib.stair_plan_run_flags(self._ctx, plan, C.c_void_p(video.data_ptr()), C.c_void_p(question.data_ptr()),
-                                       C.c_void_p(ws.data_ptr()), ws.numel() * 4, C.c_void_p(logits.data_ptr()),
-                                       C.c_void_p(pred.data_ptr()),
-                                       (RUN_VIDEO_BF16 if video.dtype == torch.bfloat16 else 0) | (RUN_PROJECTED if proj is not None else 0),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        if train:       # a training plan keeps its logits inside the workspace for the backward pass; hand the caller a copy
-            res.logits = ws[info.logits_off: info.logits_off + n * A].view(n, A).clone()    # (n x A floats) that survives the next step
-        return res
-
-    def _run_cached(self, programs, spans, question, q_lens, before_run, cse, clips, used, index, lens, T, train=False, dropout=None,
-                    enc=None):
-        """The pass of run_programs on a ClipCache: `used` = cache rows of the plan's clips, `index` = clip of every question.
-        enc (in place of clips): the encodings themselves, [n_clips, rows_cap, H] float32 on the device (VideoNMN.logits(encoded=))."""
-        n, dev = len(programs), question.device
+    def _run(self, src, programs, spans, question, q_lens, train, dropout, before_run, cse):
+        """The batched pass, once for every ClipSource (arguments as for run_programs).  What the forms differ in is read off `src`:
+        the video arguments of the early projection, the clips of the build, the gather's operands, the video argument of the run."""
+        n, dev, A = len(programs), question.device, self.config['answer_vocab_length']
         ops._req(question, 'question')
         self._bind_weights()
         if train:
             self._sync_trainable()              # (the builder, BatchResult.touched() and the reverse pass go by the context's flags)
+        # under dropout every occurrence of a node draws its own mask (module_net.py:100-106 in model.train()): nothing is shared
         drop_on = dropout is not None and dropout[0] > 0
         stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        video, bf16 = src.video_arg()
+        # The encoders' input projections need the inputs only: enqueue them BEFORE packing the programs and building the plan (3-4 ms
+        # of host work at 2048 questions), so the device is busy meanwhile (stair_encoders_project; results bit-identical).
+        # Encoded clips: the text projection alone (n_videos = 0)
         proj = None
-        if self.early_projection and question.shape[0] > 0:       # the text projection alone, ahead of the plan (n_videos = 0)
-            nf = int(lib.stair_projection_floats(self._ctx, 0, T, question.shape[0]))
+        if self.early_projection and n > 0 and question.shape[0] > 0:
+            nv = src.n_videos if src.video is not None else 0
+            nf = int(lib.stair_projection_floats(self._ctx, nv, src.T, question.shape[0]))
             proj = self._projection(nf, dev)
-            check(lib.stair_encoders_project(self._ctx, None, 0, 0, T, C.c_void_p(question.data_ptr()), question.shape[0],
-                                             C.c_void_p(proj.data_ptr()), proj.numel(), stream()))
-        compiled = [self._programs.get(p, sp) for p, sp in zip(programs, spans)]
+            check(lib.stair_encoders_project(self._ctx, video, 1 if bf16 else 0, nv, src.T, C.c_void_p(question.data_ptr()),
+                                             question.shape[0], C.c_void_p(proj.data_ptr()), proj.numel(), stream()))
+        compiled = [self._programs.get(p, sp) for p, sp in zip(programs, spans)]       # packed once per distinct (program, spans)
         prog_off, tokens, lo, hi, q_off = frontend.pack_batch(compiled, q_lens)
         if question.shape[0] != int(q_off[-1]):
             raise ValueError('question rows (%d) != sum(q_lens) (%d)' % (question.shape[0], int(q_off[-1])))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        ragged = not bool((lens == T).all())
         plan = C.c_void_p()
-        check(lib.stair_plan_build_ragged(self._ctx, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), len(used), ip(index),
-                                          ip(lens) if ragged else None, T,
-                                          PLAN_VIDEO_ENCODED | (1 if train else 0) | (0 if cse and not drop_on else 2) |
-                                          (PLAN_EXT_PROJECTION if proj is not None else 0), C.byref(plan)))
+        check(lib.stair_plan_build_ragged(self._ctx, n, ip(prog_off), ip(tokens), ip(lo), ip(hi), ip(q_off), src.n_videos, ip(src.index),
+                                          ip(src.lens), src.T,
+                                          (PLAN_VIDEO_ENCODED if src.enc is not None else 0) | (1 if train else 0) |
+                                          (0 if cse and not drop_on else 2) | (PLAN_EXT_PROJECTION if proj is not None else 0), C.byref(plan)))
         try:
             info = PlanInfo()
             check(lib.stair_plan_get_info(plan, C.byref(info)))
             if drop_on:
                 check(lib.stair_plan_set_dropout(plan, C.c_float(float(dropout[0])), C.c_uint64(int(dropout[1]) & (2 ** 64 - 1))))
-            if enc is None:
-                enc = clips.enc
-            check(lib.stair_plan_set_encoded_video(plan, C.c_void_p(enc.data_ptr()), enc.shape[1] * enc.shape[2], enc.shape[1], ip(used)))
+            if src.enc is not None:
+                enc = src.enc
+                check(lib.stair_plan_set_encoded_video(plan, C.c_void_p(enc.data_ptr()), enc.shape[1] * enc.shape[2], enc.shape[1], ip(src.rows)))
             ws = self._workspace(info.workspace_bytes, dev)
             if proj is not None:
                 check(lib.stair_plan_set_projection(self._ctx, plan, C.c_void_p(proj.data_ptr()), proj.numel()))
-            logits = torch.empty(n, self.config['answer_vocab_length'], dtype=torch.float32, device=dev)
+            logits = torch.empty(n, A, dtype=torch.float32, device=dev)
             pred = torch.empty(n, dtype=torch.int32, device=dev)
         except Exception:
             lib.stair_plan_destroy(plan)
             raise
-        res = BatchResult(self, plan, info, ws, logits, pred, prog_off, programs, None, question)      # owns the plan from here on
-        res._proj, res._clips, res._enc, res.clip_rows = proj, clips, enc, used
-        if ragged:
-            res.question_frames = lens[index]
+        res = BatchResult(self, plan, info, ws, logits, pred, prog_off, programs, src, question, proj)     # owns the plan from here on
         if before_run is not None:
             before_run(res)
-        check(lib.stair_plan_run_flags(self._ctx, plan, None, C.c_void_p(question.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel() * 4,
-                                       C.c_void_p(logits.data_ptr()), C.c_void_p(pred.data_ptr()), RUN_PROJECTED if proj is not None else 0,
-                                       stream()))
-        if train:       # as in run_programs: the plan's logits stay in the workspace for the backward pass, the caller gets a copy
-            A = self.config['answer_vocab_length']
-            res.logits = ws[info.logits_off: info.logits_off + n * A].view(n, A).clone()
+        check(lib.stair_plan_run_flags(self._ctx, plan, video, C.c_void_p(question.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel() * 4,
+                                       C.c_void_p(logits.data_ptr()), C.c_void_p(pred.data_ptr()),
+                                       bf16 | (RUN_PROJECTED if proj is not None else 0), stream()))
+        if train:       # a training plan keeps its logits inside the workspace for the backward pass; hand the caller a copy
+            res.logits = ws[info.logits_off: info.logits_off + n * A].view(n, A).clone()    # (n x A floats) that survives the next step
         return res
 
     def _matmul_mode_now(self):
@@ -722,26 +729,6 @@ class VideoNMN(nn.Module):
         cache.add(clips, ids=ids, video_len=video_len, batch_size=batch_size)
         return cache
 
-    def _encoded_args(self, encoded, video_index, video_len, n):
-        """logits(encoded=enc): checks, then (rows of the plan's clips, clip of every question, the clips' frames, T)."""
-        dev, H = next(self.parameters()).device, self.config['hidden_size']
-        if not isinstance(encoded, torch.Tensor) or encoded.dim() != 3 or encoded.shape[2] != H or encoded.shape[0] == 0 or encoded.shape[1] == 0:
-            raise ValueError('encoded must be a float32 [n_clips, T, %d] tensor of clip encodings, got shape %s'
-                             % (H, tuple(getattr(encoded, 'shape', ()))))
-        if encoded.device != dev or encoded.dtype != torch.float32 or not encoded.is_contiguous():
-            raise ValueError('encoded must be a contiguous float32 tensor on the model\'s device %s' % (dev,))
-        if encoded.shape[1] > self.config['max_video_length']:
-            raise ValueError('encoded holds %d frames per clip, max_video_length is %d' % (encoded.shape[1], self.config['max_video_length']))
-        n_clips, cap = encoded.shape[0], encoded.shape[1]
-        if video_index is None:
-            if n_clips != n:
-                raise ValueError('video_index is required when encoded holds another number of clips than there are questions')
-            video_index = np.arange(n, dtype=np.int32)
-        lengths = np.full(n_clips, cap, np.int32) if video_len is None else np.ascontiguousarray(np.asarray(video_len, dtype=np.int32))
-        if lengths.shape != (n_clips,) or lengths.min() < 1 or lengths.max() > cap:
-            raise ValueError('video_len must hold the frames (1 .. %d) of each of the %d encoded clips' % (cap, n_clips))
-        return self._clips_of_rows(video_index, lengths, n, 'encoded')
-
     def logits(self, programs, spans, video, question, q_lens, video_index=None, video_len=None, dropout=None, cse=True, clips=None,
                encoded=None):
         """[n, A] logits of a batch (arguments as for run_programs) with a torch autograd graph: when grad mode is on and any
@@ -757,31 +744,18 @@ class VideoNMN(nn.Module):
         frames.  When enc requires grad it receives a gradient of its own shape: a clip's gradient is summed over the questions
         that share it, zero behind its video_len and zero for clips that no question reads."""
         params = [dict(self.named_parameters())[n] for n in self._weight_names]
-        if clips is not None or encoded is not None:
-            if video is not None or (clips is not None and encoded is not None):
-                raise ValueError('video given together with clips= / encoded=: a pass on encoded clips takes video=None and one of the two')
-            src = encoded
-            grad = torch.is_grad_enabled() and (question.requires_grad or any(p.requires_grad for p in params) or
-                                                (isinstance(src, torch.Tensor) and src.requires_grad))
-            if clips is not None:
-                plan_clips = self._run_cached_args(clips, None, video_index, video_len, len(programs), grad, dropout if grad else None)
-            else:
-                self._check_encoded_training(grad, dropout if grad else None)
-                plan_clips = self._encoded_args(encoded, video_index, video_len, len(programs))
-            if not grad:
-                with torch.no_grad():
-                    return self._run_cached(programs, spans, question, q_lens, None, cse, clips, *plan_clips,
-                                            enc=None if src is None else src.detach()).logits
-            from .autograd import PlanLogits
-            call = (programs, spans, q_lens, video_index, video_len, dropout, cse, clips, plan_clips)
-            return PlanLogits.apply(self, call, src, question, *params)
-        if not (torch.is_grad_enabled() and (video.requires_grad or question.requires_grad or any(p.requires_grad for p in params))):
+        if (clips is not None or encoded is not None) and (video is not None or (clips is not None and encoded is not None)):
+            raise ValueError('video given together with clips= / encoded=: a pass on encoded clips takes video=None and one of the two')
+        tensor = video if video is not None else encoded        # what of the source autograd may differentiate (a ClipCache: nothing)
+        grad = torch.is_grad_enabled() and (question.requires_grad or any(p.requires_grad for p in params) or
+                                            (isinstance(tensor, torch.Tensor) and tensor.requires_grad))
+        src = self._clip_source(len(programs), video, video_index, video_len, clips, encoded, grad, dropout if grad else None)
+        if not grad:
             with torch.no_grad():
-                return self.run_programs(programs, spans, video, question, q_lens, video_index=video_index, video_len=video_len,
-                                         cse=cse).logits
+                return self._run(src if tensor is None else src.with_tensor(tensor.detach()), programs, spans, question, q_lens,
+                                 False, None, None, cse).logits
         from .autograd import PlanLogits
-        call = (programs, spans, q_lens, video_index, video_len, dropout, cse, None, None)
-        return PlanLogits.apply(self, call, video, question, *params)
+        return PlanLogits.apply(self, (programs, spans, q_lens, dropout, cse, src), tensor, question, *params)
 
     def forward_batch(self, batch, train=False, share_videos=True, dropout=None, cse=True, clip_cache=None):
         """batch: list of question dicts in the reference layout (dataset.py:191-233).  Clips may differ in their
@@ -797,13 +771,20 @@ class VideoNMN(nn.Module):
         'video_features' are not read); an id the cache does not hold raises KeyError naming it.  With train=True the video
         encoder must be frozen (see run_programs, `clips`)."""
         dev = next(self.parameters()).device
+        video = video_len = None
         if clip_cache is not None:
-            rows = clip_cache.rows([d['video_id'] for d in batch])
-            qs = [torch.as_tensor(d['question']) for d in batch]
-            question = torch.cat(qs).to(dev, torch.float32).contiguous()
-            return self.run_programs([d['nmn_program_list'] for d in batch], [d['prog_str_to_question_tokens'] for d in batch], None,
-                                     question, [q.shape[0] for q in qs], train=train, video_index=rows, dropout=dropout, cse=cse,
-                                     clips=clip_cache)
+            index = clip_cache.rows([d['video_id'] for d in batch])
+        else:
+            video, index, video_len = self._pack_clips(batch, share_videos, dev)
+        qs = [torch.as_tensor(d['question']) for d in batch]
+        question = torch.cat(qs).to(dev, torch.float32).contiguous()
+        return self.run_programs([d['nmn_program_list'] for d in batch], [d['prog_str_to_question_tokens'] for d in batch], video, question,
+                                 [q.shape[0] for q in qs], train=train, video_index=index, dropout=dropout, video_len=video_len, cse=cse,
+                                 clips=clip_cache)
+
+    @staticmethod
+    def _pack_clips(batch, share_videos, dev):
+        """(video [n_videos, T, V] on the device, clip of every question or None, frames of every clip or None) of a batch of dicts."""
         clips, index = [], None
         if share_videos and len(batch) > 1:
             by_id = all('video_id' in d for d in batch)
@@ -826,12 +807,7 @@ class VideoNMN(nn.Module):
         if len(set(frames)) > 1:                   # mixed clip lengths: pad to the longest, keep every clip's own length
             video_len, Tm = frames, max(frames)
             clips = [torch.nn.functional.pad(c.to(vdtype), (0, 0, 0, Tm - c.shape[0])) for c in clips]
-        video = torch.stack(clips).to(dev, vdtype).contiguous()
-        qs = [torch.as_tensor(d['question']) for d in batch]
-        question = torch.cat(qs).to(dev, torch.float32).contiguous()
-        return self.run_programs([d['nmn_program_list'] for d in batch],
-                                 [d['prog_str_to_question_tokens'] for d in batch], video, question,
-                                 [q.shape[0] for q in qs], train=train, video_index=index, dropout=dropout, video_len=video_len, cse=cse)
+        return torch.stack(clips).to(dev, vdtype).contiguous(), index, video_len
 
     # ---------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -275,8 +275,8 @@ class Trainer:
         Returns (per-question decoder CE of the local shard, BatchResult)."""
         from . import losses as L
         n = len(programs)
-        if clips is not None:                                 # refused here: nothing of the step has been enqueued or counted yet
-            self.model._run_cached_args(clips, video, video_index, video_len, n, True, None)
+        # the checks of the clips, once per step; what they refuse is refused here: nothing of the step has been enqueued or counted yet
+        src = self.model._clip_source(n, video, video_index, video_len, clips, train=True)
         if global_batch is None:
             global_batch = self.global_batch
         if global_batch is None and self.world > 1:           # ragged shards: the window is the SUM of the shard sizes
@@ -305,10 +305,9 @@ class Trainer:
             prep['p'] = L.prepare_module_losses(self.model, res_, questions, no_intermediate=self.no_intermediate,
                                                 window=self.contrastive_window, world=self.world, rank=self.rank,
                                                 class_table=self.class_table, global_batch=G)
-        res = self.model.run_programs(programs, spans, video, question, q_lens, train=True, video_index=video_index, dropout=drop,
-                                      video_len=video_len, before_run=prepare if supervised else None, clips=clips)
+        res = self.model._run(src, programs, spans, question, q_lens, True, drop, prepare if supervised else None, True)
         extra = set()
-        trainable = list(self.model._trainable)               # requires_grad of this step (run_programs has synced it into the context)
+        trainable = list(self.model._trainable)               # requires_grad of this step (the pass has synced it into the context)
         tl = res.touched()                                    # known from the plan: uploaded BEFORE the backward pass is enqueued
                                                               # (0 for a frozen weight, whatever the programs use)
         if supervised:
