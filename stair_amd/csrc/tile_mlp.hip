@@ -184,6 +184,8 @@ __device__ __forceinline__ int tm_fresh_v(int v) {
 // the tails that reduce over frames see where one instance ends.  What they need per ROW is looked up once per tile by wave 0
 // (lane R = row R) into small LDS tables (pk_*); a row's entry is wave-uniform (row = wave + 8 j), so it is read back into SGPRs.
 // Rows of instances >= cnt and rows >= P T do not exist: their entries point at row 0 of the tile (read, zeroed, never written).
+// The tails are ONE implementation for all forms: a row finds its target through the TM_ROW_* accessors in front of them, which
+// read the row's pk_* entries in a packed tile and the tile's own (uniform) slot, first row and row number in the other forms.
 // The relu' bit masks stay indexed by TILE number: a packed chain reads what the packed forward launch of the same bucket wrote.
 //
 // SPLIT: an instance of T > 64 frames runs as S = ceil(T / 64) SEGMENTS, segment g = frames 64 g .. min(64 g + 64, T) - 1,
@@ -721,329 +723,133 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
         const bool ofirst = KIND != KIND_FWD && (oraw & STAIR_TILE_STORE_FIRST) != 0;
         const int64_t oslot = KIND != KIND_FWD ? (oraw & ~STAIR_TILE_STORE_FIRST) : oraw;
         const int64_t orow0 = SPLIT ? (int64_t)sfr0 * TM_H : 0;       // the segment's first row in the instance's [T, H] target
-        if (PACK) {
-            // ---- the tails of a packed tile: the same arithmetic per row, every row at its own instance's targets ----------------
-            // (a copy of the unpacked tails below with per-row addresses, so that the unpacked instantiations compile as they did:
-            //  a change to a tail's arithmetic is made in BOTH -- tests/test_gpu_tile_pack.py compares the two bit for bit)
-            const int Tc = p.T;
-            // (row R's frame, and its tile in `out`: the entry of out_idx without the STORE_FIRST bit)
-#define TM_PK_T(row_) ((TM_PK_S(pk_tf, row_) >> 16) & 63)
-#define TM_PK_OUT(row_) (p.out + (int64_t)TM_PK_S(pk_oi, row_) * p.out_gstride)
-            if (KIND == KIND_TEMPORAL_BWD) {
-                // ROWSCALE_ADJ (see the unpacked form below): d feat_t += r_t G_t, d r_t += G_t . feat_t, per row
-                __builtin_amdgcn_sched_barrier(0);
-                v4f f0[8], f1[8];
-                float rr[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {           // every global load of the tail first
-                    const int R = wave + 8 * j, ts = TM_PK_S(pk_tf, R) & 63;
-                    const float *feat = p.adj_feat + (int64_t)TM_PK_S(pk_fi, R) * p.adj_feat_gstride + (int64_t)ts * TM_H;
-                    f0[j] = tm_ld(feat + 4 * lane);
-                    f1[j] = tm_ld(feat + 256 + 4 * lane);
-                    rr[j] = p.adj_rs[(int64_t)TM_PK_S(pk_ri, R) * Tc + ts];
-                }
-                const bool allfirst = TM_PK_S(&pk_allfirst, 0) != 0;
-                if (allfirst) {                         // every instance of the tile stores the first contribution to its target
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int R = wave + 8 * j;
-                        if (R < T) {
-                            const int t = TM_PK_T(R);
-                            float *dst = TM_PK_OUT(R) + (int64_t)t * TM_H;
-                            float *drs = p.adj_drs + (int64_t)TM_PK_S(pk_ri, R) * Tc + t;
-                            const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
-                            float d = 0.f;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
-                            d = wave_sum(d);
-                            if (lane == 0) unsafeAtomicAdd(drs, d);
-                            *reinterpret_cast<v4f *>(dst + 4 * lane) = rr[j] * g0;
-                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = rr[j] * g1;
-                        }
-                    }
-                } else if (p.acc_exclusive) {           // read - add - write; a row whose instance stores first discards what it read
-                    v4f o0[8], o1[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int R = wave + 8 * j;
-                        const float *src = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
-                        o0[j] = *reinterpret_cast<const v4f *>(src + 4 * lane);
-                        o1[j] = *reinterpret_cast<const v4f *>(src + 256 + 4 * lane);
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int R = wave + 8 * j;
-                        if (R < T) {
-                            const int tf = TM_PK_S(pk_tf, R), t = (tf >> 16) & 63;
-                            float *dst = TM_PK_OUT(R) + (int64_t)t * TM_H;
-                            float *drs = p.adj_drs + (int64_t)TM_PK_S(pk_ri, R) * Tc + t;
-                            const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
-                            float d = 0.f;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
-                            d = wave_sum(d);
-                            if (lane == 0) unsafeAtomicAdd(drs, d);
-                            const bool fst = (tf & TM_PK_FIRST) != 0;
-                            *reinterpret_cast<v4f *>(dst + 4 * lane) = fst ? rr[j] * g0 : o0[j] + rr[j] * g0;
-                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = fst ? rr[j] * g1 : o1[j] + rr[j] * g1;
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int R = wave + 8 * j;
-                        if (R < T) {
-                            const int tf = TM_PK_S(pk_tf, R), t = (tf >> 16) & 63;
-                            float *dst = TM_PK_OUT(R) + (int64_t)t * TM_H;
-                            float *drs = p.adj_drs + (int64_t)TM_PK_S(pk_ri, R) * Tc + t;
-                            const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
-                            float d = 0.f;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
-                            d = wave_sum(d);
-                            if (lane == 0) unsafeAtomicAdd(drs, d);
-                            if (tf & TM_PK_FIRST) {
-                                *reinterpret_cast<v4f *>(dst + 4 * lane) = rr[j] * g0;
-                                *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = rr[j] * g1;
-                            } else {
-#pragma unroll
-                                for (int c = 0; c < TM_H / 64; ++c) unsafeAtomicAdd(dst + 64 * c + lane, rr[j] * F[R * TM_FLD + 64 * c + lane]);
-                            }
-                        }
-                    }
-                }
-            } else
-            switch (KIND == KIND_CHAIN && p.tail != STAIR_TILE_ACCUMULATE ? (p.tail == STAIR_TILE_STORE ? STAIR_TILE_STORE : STAIR_TILE_NONE)
-                                                                 : (KIND != KIND_CHAIN && p.tail == STAIR_TILE_ACCUMULATE ? STAIR_TILE_NONE : p.tail)) {
-                case STAIR_TILE_STORE:
-                    for (int R = wave; R < T; R += 8) {
-                        float *dst = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
-                        tm_st(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane));
-                        tm_st(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane));
-                    }
-                    break;
-                case STAIR_TILE_ACCUMULATE:
-                    if (KIND != KIND_CHAIN) break;
-                    if (TM_PK_S(&pk_allfirst, 0) != 0) {        // every instance of the tile stores: no target is read
-                        for (int R = wave; R < T; R += 8) {
-                            float *dst = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
-                            *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane);
-                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
-                        }
-                        break;
-                    }
-                    if (p.acc_exclusive) {              // whole rows read, added and written back; a storing instance's rows discard the read
-                        __builtin_amdgcn_sched_barrier(0);
-                        v4f o0[8], o1[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const int R = wave + 8 * j;
-                            const float *src = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
-                            o0[j] = *reinterpret_cast<const v4f *>(src + 4 * lane);
-                            o1[j] = *reinterpret_cast<const v4f *>(src + 256 + 4 * lane);
-                        }
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const int R = wave + 8 * j;
-                            if (R < T) {
-                                const int tf = TM_PK_S(pk_tf, R);
-                                float *dst = TM_PK_OUT(R) + (int64_t)((tf >> 16) & 63) * TM_H;
-                                const bool fst = (tf & TM_PK_FIRST) != 0;
-                                const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
-                                *reinterpret_cast<v4f *>(dst + 4 * lane) = fst ? g0 : o0[j] + g0;
-                                *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = fst ? g1 : o1[j] + g1;
-                            }
-                        }
-                        break;
-                    }
-                    for (int R = wave; R < T; R += 8) {
-                        const int tf = TM_PK_S(pk_tf, R);
-                        float *dst = TM_PK_OUT(R) + (int64_t)((tf >> 16) & 63) * TM_H;
-                        if (tf & TM_PK_FIRST) {
-                            *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane);
-                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
-                        } else {
-#pragma unroll
-                            for (int c = 0; c < TM_H / 64; ++c) unsafeAtomicAdd(dst + 64 * c + lane, F[R * TM_FLD + 64 * c + lane]);
-                        }
-                    }
-                    break;
-                case STAIR_TILE_SUM_ROWS: {               // one sum per instance, over its own frames, in frame order
-                    if (KIND == KIND_CHAIN) break;
-                    const int col = tm_fresh_v(TM_TID());
-                    for (int sg = 0; sg < pkN; ++sg) {
-                        const int R0 = sg * Tc;
-                        const int L = TM_PK_S(pk_len, R0);
-                        float s = 0.f;
-                        for (int t = 0; t < L; ++t) s += F[(R0 + t) * TM_FLD + col];
-                        TM_PK_OUT(R0)[col] = s;
-                    }
-                    break;
-                }
-                case STAIR_TILE_COSINE: {                 // every instance against its own keyword rows
-                    if (KIND == KIND_CHAIN) break;
-                    for (int sg = 0; sg < pkN; ++sg) {
-                        const int R0 = sg * Tc;
-                        const int first = TM_PK_S(pk_pf, R0), cn = TM_PK_S(pk_pc, R0);
-                        for (int j = 0; j < cn; ++j) {
-                            const float *k = p.kb + (int64_t)(first + j) * TM_H;
-                            const v4f k0 = *reinterpret_cast<const v4f *>(k + 4 * lane), k1 = *reinterpret_cast<const v4f *>(k + 256 + 4 * lane);
-                            float *arow = p.att + (int64_t)p.att_idx[first + j] * Tc;
-                            float nk = 0.f;
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) nk += k0[i] * k0[i] + k1[i] * k1[i];
-                            nk = wave_sum(nk);
-                            for (int t = wave; t < Tc; t += 8) {
-                                const float *fr = F + (R0 + t) * TM_FLD;
-                                const v4f f0 = *reinterpret_cast<const v4f *>(fr + 4 * lane), f1 = *reinterpret_cast<const v4f *>(fr + 256 + 4 * lane);
-                                float nf = 0.f, d = 0.f;
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) { nf += f0[i] * f0[i] + f1[i] * f1[i]; d += f0[i] * k0[i] + f1[i] * k1[i]; }
-                                nf = wave_sum(nf); d = wave_sum(d);
-                                if (lane == 0) {
-                                    const float eps = 1e-8f;
-                                    const float c = d / (fmaxf(sqrtf(nf), eps) * fmaxf(sqrtf(nk), eps));
-                                    arow[t] = (c + 1.0f) * 0.49f;
-                                }
-                            }
-                        }
-                    }
-                    break;
-                }
-                case STAIR_TILE_ROWDOT_SIGMOID: {
-                    if (KIND == KIND_CHAIN) break;
-                    const v4f w0 = *reinterpret_cast<const v4f *>(p.vw + 4 * lane), w1 = *reinterpret_cast<const v4f *>(p.vw + 256 + 4 * lane);
-                    const float vb0 = p.vb[0];
-                    for (int R = wave; R < T; R += 8) {
-                        const float off = vb0 + pk_ex[R];
-                        const v4f f0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
-                        float d = 0.f;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) d += f0[i] * w0[i] + f1[i] * w1[i];
-                        d = wave_sum(d);
-                        if (lane == 0) TM_PK_OUT(R)[TM_PK_T(R)] = sigmoid_acc(d + off);
-                    }
-                    break;
-                }
-                case STAIR_TILE_LAYERNORM: {
-                    if (KIND == KIND_CHAIN) break;
-                    const v4f g0 = *reinterpret_cast<const v4f *>(p.gamma + 4 * lane), g1 = *reinterpret_cast<const v4f *>(p.gamma + 256 + 4 * lane);
-                    const v4f b0 = *reinterpret_cast<const v4f *>(p.beta + 4 * lane), b1 = *reinterpret_cast<const v4f *>(p.beta + 256 + 4 * lane);
-                    for (int R = wave; R < T; R += 8) {
-                        v4f f0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
-                        float sum = 0.f;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) sum += f0[i] + f1[i];
-                        const float mean = wave_sum(sum) / (float)TM_H;
-                        float sq = 0.f;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) { const float a = f0[i] - mean, b = f1[i] - mean; sq += a * a + b * b; }
-                        const float rstd = rsqrtf(wave_sum(sq) / (float)TM_H + p.ln_eps);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) { f0[i] = (f0[i] - mean) * rstd * g0[i] + b0[i]; f1[i] = (f1[i] - mean) * rstd * g1[i] + b1[i]; }
-                        float *dst = TM_PK_OUT(R) + (int64_t)TM_PK_T(R) * TM_H;
-                        *reinterpret_cast<v4f *>(dst + 4 * lane) = f0;
-                        *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = f1;
-                    }
-                    break;
-                }
-                default: break;
-            }
-#undef TM_PK_OUT
-#undef TM_PK_T
-        } else
+        // ---- where staged row R goes: ONE implementation of every tail, each row's targets looked up through these ------------
+        // A plain or split tile belongs to one instance: its targets are the tile's (oslot, orow0, sfr0, ofirst, the row number),
+        // uniform by construction.  A packed tile's row has its instance's: the pk_* entries of row R, read back into SGPRs
+        // (R = wave + 8 j is wave-uniform).  PACK is a template argument, so every form compiles its own spelling only.
+        const int Tc = p.T;                                           // frames of an instance (SPLIT: of all its segments)
+        // the tile's first row in `out`; row R's frame, its instance's slot in `out`, its target row (tile_: the tile's first row or a
+        // tm_fresh copy of it -- a packed tile has none, and computes none) and its scalar target
+#define TM_TILE_OUT (p.out + oslot * p.out_gstride + orow0)
+#define TM_ROW_T(row_) (PACK ? (TM_PK_S(pk_tf, row_) >> 16) & 63 : (row_))
+#define TM_ROW_SLOT(row_) (PACK ? (int64_t)TM_PK_S(pk_oi, row_) : oslot)
+#define TM_ROW_OUT(tile_, row_) (PACK ? p.out + TM_ROW_SLOT(row_) * p.out_gstride + (int64_t)TM_ROW_T(row_) * TM_H : (tile_) + (int64_t)(row_) * TM_H)
+#define TM_ROW_VAL(row_) p.out[TM_ROW_SLOT(row_) * p.out_gstride + sfr0 + TM_ROW_T(row_)]
+        // a row to LOAD through: row 0 for the rows behind the tile's last (a packed tile's tables point those at row 0 themselves)
+#define TM_ROW_OR0(row_) (PACK ? (row_) : ((row_) < T ? (row_) : 0))
+        // does R's instance store first (tile-uniform in the plain forms: the branches on it fold), does every instance of the tile
+#define TM_ROW_FIRST(row_) (PACK ? (TM_PK_S(pk_tf, row_) & TM_PK_FIRST) != 0 : ofirst)
+#define TM_ALL_FIRST() (PACK ? TM_PK_S(&pk_allfirst, 0) != 0 : ofirst)
         if (KIND == KIND_TEMPORAL_BWD) {
             // tail ROWSCALE_ADJ: the staged rows are G = dZ W, the gradient of the SCALED input r_t feat_t of the dense layer:
             // d feat_t += r_t G_t (one dword per lane, 256 contiguous bytes per wave-instruction), d r_t += G_t . feat_t
-            const float *feat = tm_fresh(p.adj_feat + (int64_t)(p.adj_feat_idx ? __builtin_amdgcn_readfirstlane(p.adj_feat_idx[ii]) : ii) * p.adj_feat_gstride + (SPLIT ? (int64_t)sfr0 * TM_H : 0));
-            const int64_t rslot = p.adj_rs_idx ? __builtin_amdgcn_readfirstlane(p.adj_rs_idx[ii]) : ii;
-            const float *rs = p.adj_rs + rslot * (SPLIT ? p.T : T) + sfr0;
-            float *drs = p.adj_drs + rslot * (SPLIT ? p.T : T) + sfr0;
-            float *dst = tm_fresh(p.out + oslot * p.out_gstride + (SPLIT ? (int64_t)sfr0 * TM_H : 0));
+            // (the plain forms' tile-level pointers; computed in a packed tile, where nothing reads them, they cost its form three VGPRs)
+            const float *feat = PACK ? nullptr : tm_fresh(p.adj_feat + (int64_t)(p.adj_feat_idx ? __builtin_amdgcn_readfirstlane(p.adj_feat_idx[ii]) : ii) * p.adj_feat_gstride + (SPLIT ? (int64_t)sfr0 * TM_H : 0));
+            const int64_t rslot = PACK ? 0 : (p.adj_rs_idx ? __builtin_amdgcn_readfirstlane(p.adj_rs_idx[ii]) : ii);
+            const float *rs = PACK ? nullptr : p.adj_rs + rslot * (SPLIT ? p.T : T) + sfr0;
+            float *drs = PACK ? nullptr : p.adj_drs + rslot * (SPLIT ? p.T : T) + sfr0;
+            float *tile = PACK ? nullptr : tm_fresh(TM_TILE_OUT);
+            // frame 0 of R's instance in adj_feat, adj_rs and adj_drs (SPLIT: the segment's first frame)
+#define TM_ROW_FEAT(row_) (PACK ? p.adj_feat + (int64_t)TM_PK_S(pk_fi, row_) * p.adj_feat_gstride : feat)
+#define TM_ROW_RS(row_) (PACK ? p.adj_rs + (int64_t)TM_PK_S(pk_ri, row_) * Tc : rs)
+#define TM_ROW_DRS(row_) (PACK ? p.adj_drs + (int64_t)TM_PK_S(pk_ri, row_) * Tc : drs)
             __builtin_amdgcn_sched_barrier(0);      // the loads stay below the epilogue (hoisted, they cost registers there)
             v4f f0[8], f1[8];
             float rr[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {           // every global load of the tail first
-                const int t = wave + 8 * j, ts = t < T ? t : 0;
-                f0[j] = tm_ld(feat + (int64_t)ts * TM_H + 4 * lane);
-                f1[j] = tm_ld(feat + (int64_t)ts * TM_H + 256 + 4 * lane);
-                rr[j] = rs[ts];
+                const int R = wave + 8 * j, ts = PACK ? TM_PK_S(pk_tf, R) & 63 : TM_ROW_OR0(R);     // the frame to READ, as in the input stage
+                f0[j] = tm_ld(TM_ROW_FEAT(R) + (int64_t)ts * TM_H + 4 * lane);
+                f1[j] = tm_ld(TM_ROW_FEAT(R) + (int64_t)ts * TM_H + 256 + 4 * lane);
+                rr[j] = TM_ROW_RS(R)[ts];
             }
-            if (ofirst) {                           // first contribution to a tile the pass has not cleared: rows stored, the target not read
+            if (TM_ALL_FIRST()) {                   // first contribution to targets the pass has not cleared: rows stored, the target not read
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const int t = wave + 8 * j;
-                    if (t < T) {
-                        const v4f g0 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                    const int R = wave + 8 * j;
+                    if (R < T) {
+                        float *dst = TM_ROW_OUT(tile, R), *drs_ = TM_ROW_DRS(R) + TM_ROW_T(R);
+                        const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
                         float d = 0.f;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
                         d = wave_sum(d);
-                        if (lane == 0) unsafeAtomicAdd(drs + t, d);
-                        *reinterpret_cast<v4f *>(dst + (int64_t)t * TM_H + 4 * lane) = rr[j] * g0;
-                        *reinterpret_cast<v4f *>(dst + (int64_t)t * TM_H + 256 + 4 * lane) = rr[j] * g1;
+                        if (lane == 0) unsafeAtomicAdd(drs_, d);
+                        *reinterpret_cast<v4f *>(dst + 4 * lane) = rr[j] * g0;
+                        *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = rr[j] * g1;
                     }
                 }
             } else if (p.acc_exclusive) {           // read - add - write instead of atomics (see ACCUMULATE); a branch of its own:
                 v4f o0[8], o1[8];                   // a condition inside the unrolled loops made every load wait and spill
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const int t = wave + 8 * j, ts = t < T ? t : 0;
-                    o0[j] = *reinterpret_cast<const v4f *>(dst + (int64_t)ts * TM_H + 4 * lane);
-                    o1[j] = *reinterpret_cast<const v4f *>(dst + (int64_t)ts * TM_H + 256 + 4 * lane);
+                    const int R = wave + 8 * j;
+                    const float *src = TM_ROW_OUT(tile, TM_ROW_OR0(R));
+                    o0[j] = *reinterpret_cast<const v4f *>(src + 4 * lane);
+                    o1[j] = *reinterpret_cast<const v4f *>(src + 256 + 4 * lane);
                 }
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const int t = wave + 8 * j;
-                    if (t < T) {
-                        const v4f g0 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                    const int R = wave + 8 * j;
+                    if (R < T) {
+                        float *dst = TM_ROW_OUT(tile, R), *drs_ = TM_ROW_DRS(R) + TM_ROW_T(R);
+                        const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
                         float d = 0.f;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
                         d = wave_sum(d);
-                        if (lane == 0) unsafeAtomicAdd(drs + t, d);
-                        *reinterpret_cast<v4f *>(dst + (int64_t)t * TM_H + 4 * lane) = o0[j] + rr[j] * g0;
-                        *reinterpret_cast<v4f *>(dst + (int64_t)t * TM_H + 256 + 4 * lane) = o1[j] + rr[j] * g1;
+                        if (lane == 0) unsafeAtomicAdd(drs_, d);
+                        const bool fst = TM_ROW_FIRST(R);       // a row whose instance stores first discards what it read
+                        *reinterpret_cast<v4f *>(dst + 4 * lane) = fst ? rr[j] * g0 : o0[j] + rr[j] * g0;
+                        *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = fst ? rr[j] * g1 : o1[j] + rr[j] * g1;
                     }
                 }
             } else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const int t = wave + 8 * j;
-                    if (t < T) {
-                        const v4f g0 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                    const int R = wave + 8 * j;
+                    if (R < T) {
+                        float *dst = TM_ROW_OUT(tile, R), *drs_ = TM_ROW_DRS(R) + TM_ROW_T(R);
+                        const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
                         float d = 0.f;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) d += g0[i] * f0[j][i] + g1[i] * f1[j][i];
                         d = wave_sum(d);
-                        if (lane == 0) unsafeAtomicAdd(drs + t, d);
+                        if (lane == 0) unsafeAtomicAdd(drs_, d);
+                        if (TM_ROW_FIRST(R)) {
+                            *reinterpret_cast<v4f *>(dst + 4 * lane) = rr[j] * g0;
+                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = rr[j] * g1;
+                        } else {
 #pragma unroll
-                        for (int c = 0; c < TM_H / 64; ++c) unsafeAtomicAdd(dst + (int64_t)t * TM_H + 64 * c + lane, rr[j] * F[t * TM_FLD + 64 * c + lane]);
+                            for (int c = 0; c < TM_H / 64; ++c) unsafeAtomicAdd(dst + 64 * c + lane, rr[j] * F[R * TM_FLD + 64 * c + lane]);
+                        }
                     }
                 }
             }
+#undef TM_ROW_DRS
+#undef TM_ROW_RS
+#undef TM_ROW_FEAT
         } else
         switch (KIND == KIND_CHAIN && p.tail != STAIR_TILE_ACCUMULATE ? (p.tail == STAIR_TILE_STORE ? STAIR_TILE_STORE : STAIR_TILE_NONE)
                                                              : (KIND != KIND_CHAIN && p.tail == STAIR_TILE_ACCUMULATE ? STAIR_TILE_NONE : p.tail)) {
             case STAIR_TILE_STORE:
-                for (int t = wave; t < T; t += 8) {
-                    float *dst = p.out + oslot * p.out_gstride + orow0 + (int64_t)t * TM_H;
-                    tm_st(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane));
-                    tm_st(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane));
+                for (int R = wave; R < T; R += 8) {
+                    float *dst = TM_ROW_OUT(TM_TILE_OUT, R);
+                    tm_st(dst + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane));
+                    tm_st(dst + 256 + 4 * lane, *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane));
                 }
                 break;
             case STAIR_TILE_ACCUMULATE:               // backward chains: dX added into a gradient tile several instances may share
                 if (KIND != KIND_CHAIN) break;
                 // one dword per lane, 256 contiguous bytes per wave-instruction: the shape float atomics run at full rate in
                 // (MI355X_MICROARCH.md "Global float atomics"; 16-byte-strided lanes spread an instruction over 1 KB)
-                if (ofirst) {
-                    // the first contribution of the pass to a tile that was not cleared (stair_plan_backward marks it): what the
+                if (TM_ALL_FIRST()) {
+                    // the first contribution of the pass to targets that were not cleared (stair_plan_backward marks them): what the
                     // read - add - write below leaves in a zeroed tile, without the 128 KB read (a branch of its own, like that one)
-                    for (int t = wave; t < T; t += 8) {
-                        float *dst = p.out + oslot * p.out_gstride + orow0 + (int64_t)t * TM_H;
-                        *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane);
-                        *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                    for (int R = wave; R < T; R += 8) {
+                        float *dst = TM_ROW_OUT(TM_TILE_OUT, R);
+                        *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane);
+                        *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
                     }
                     break;
                 }
@@ -1052,82 +858,105 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     // gives every same-level reader of a slot a target of its own): whole rows read, added and written back, every
                     // load of the tile's rows in flight at once -- float atomics retire 256 B per ~50 ns and CU (1.3 TB/s chip-wide,
                     // MI355X_MICROARCH.md "Global float atomics"): 25 us per tile, as long as two layers of the chain
-                    float *dst = tm_fresh(p.out + oslot * p.out_gstride + orow0);
+                    float *tile = PACK ? nullptr : tm_fresh(TM_TILE_OUT);
                     __builtin_amdgcn_sched_barrier(0);          // the loads stay below the epilogue (hoisted, they cost registers there)
                     v4f o0[8], o1[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        const int t = wave + 8 * j, ts = t < T ? t : 0;
-                        o0[j] = *reinterpret_cast<const v4f *>(dst + (int64_t)ts * TM_H + 4 * lane);
-                        o1[j] = *reinterpret_cast<const v4f *>(dst + (int64_t)ts * TM_H + 256 + 4 * lane);
+                        const int R = wave + 8 * j;
+                        const float *src = TM_ROW_OUT(tile, TM_ROW_OR0(R));
+                        o0[j] = *reinterpret_cast<const v4f *>(src + 4 * lane);
+                        o1[j] = *reinterpret_cast<const v4f *>(src + 256 + 4 * lane);
                     }
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        const int t = wave + 8 * j;
-                        if (t < T) {
-                            *reinterpret_cast<v4f *>(dst + (int64_t)t * TM_H + 4 * lane) = o0[j] + *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane);
-                            *reinterpret_cast<v4f *>(dst + (int64_t)t * TM_H + 256 + 4 * lane) = o1[j] + *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                        const int R = wave + 8 * j;
+                        if (R < T) {
+                            const v4f g0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), g1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                            float *dst = TM_ROW_OUT(tile, R);
+                            const bool fst = TM_ROW_FIRST(R);   // a row whose instance stores first discards what it read
+                            *reinterpret_cast<v4f *>(dst + 4 * lane) = fst ? g0 : o0[j] + g0;
+                            *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = fst ? g1 : o1[j] + g1;
                         }
                     }
                     break;
                 }
-                for (int t = wave; t < T; t += 8) {
-                    float *dst = p.out + oslot * p.out_gstride + orow0 + (int64_t)t * TM_H;
+                for (int R = wave; R < T; R += 8) {
+                    float *dst = TM_ROW_OUT(TM_TILE_OUT, R);
+                    if (TM_ROW_FIRST(R)) {
+                        *reinterpret_cast<v4f *>(dst + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane);
+                        *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
+                    } else {
 #pragma unroll
-                    for (int c = 0; c < TM_H / 64; ++c) unsafeAtomicAdd(dst + 64 * c + lane, F[t * TM_FLD + 64 * c + lane]);
+                        for (int c = 0; c < TM_H / 64; ++c) unsafeAtomicAdd(dst + 64 * c + lane, F[R * TM_FLD + 64 * c + lane]);
+                    }
                 }
                 break;
             case STAIR_TILE_SUM_ROWS: {               // Filter: sum over the clip's own frames (modules.py:374,376)
                 if (KIND == KIND_CHAIN) break;
-                const int L = SPLIT ? seg_len : (p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T);
-                const int col = tm_fresh_v(TM_TID());       // (not hoisted out of the tile loop: three values kept that way went to scratch)
-                float s = SPLIT && sgn > 0 ? walk_sum : 0.f;    // (SPLIT: the instance's frames in order, segment after segment)
-                for (int t = 0; t < L; ++t) s += F[t * TM_FLD + col];
-                // (the walk ends with the clip's last live segment: the ones behind it are skipped above)
-                const int nlive = SPLIT ? (p.len ? max(1, (min(__builtin_amdgcn_readfirstlane(p.len[ii]), p.T) + TM_ROWS - 1) / TM_ROWS) : nsg) : 1;
-                if (SPLIT && sgn + 1 < nlive) { walk_sum = s; walk_next = sgn + 1; break; }
-                if (SPLIT) walk_next = 0;
-                p.out[oslot * p.out_gstride + col] = s;
+                // one sum per instance of the tile (pkN: 1 in the plain and split forms), over its own frames, in frame order
+                // (do-while, here and in COSINE: with PACK false there is no loop for the compiler to fold, and the code is what it was)
+                int sg = 0;
+                do {
+                    const int R0 = PACK ? sg * Tc : 0;
+                    const int L = PACK ? TM_PK_S(pk_len, R0) : (SPLIT ? seg_len : (p.len ? __builtin_amdgcn_readfirstlane(p.len[inst]) : T));
+                    const int col = tm_fresh_v(TM_TID());       // (not hoisted out of the tile loop: three values kept that way went to scratch)
+                    float s = SPLIT && sgn > 0 ? walk_sum : 0.f;    // (SPLIT: the instance's frames in order, segment after segment)
+                    for (int t = 0; t < L; ++t) s += F[(R0 + t) * TM_FLD + col];
+                    // (the walk ends with the clip's last live segment: the ones behind it are skipped above)
+                    const int nlive = SPLIT ? (p.len ? max(1, (min(__builtin_amdgcn_readfirstlane(p.len[ii]), p.T) + TM_ROWS - 1) / TM_ROWS) : nsg) : 1;
+                    if (SPLIT && sgn + 1 < nlive) { walk_sum = s; walk_next = sgn + 1; break; }
+                    if (SPLIT) walk_next = 0;
+                    p.out[TM_ROW_SLOT(R0) * p.out_gstride + col] = s;
+                } while (PACK && ++sg < pkN);
                 break;
             }
             case STAIR_TILE_COSINE: {                 // Localize: (cos(f_t, k_j) + 1) * 0.49, nn.CosineSimilarity eps 1e-8
                 if (KIND == KIND_CHAIN) break;
-                const int first = __builtin_amdgcn_readfirstlane(p.pair_first[ii]), cn = __builtin_amdgcn_readfirstlane(p.pair_cnt[ii]);
-                // pair-major: a keyword row (and its norm, and its attention slot) is fetched once, not once per frame
-                for (int j = 0; j < cn; ++j) {
-                    const float *k = p.kb + (int64_t)(first + j) * TM_H;
-                    const v4f k0 = *reinterpret_cast<const v4f *>(k + 4 * lane), k1 = *reinterpret_cast<const v4f *>(k + 256 + 4 * lane);
-                    float *arow = p.att + (int64_t)p.att_idx[first + j] * (SPLIT ? p.T : T) + sfr0;
-                    float nk = 0.f;
+                // every instance of the tile (pkN: 1 in the plain and split forms) against its own keyword rows
+                int sg = 0;
+                do {
+                    const int R0 = PACK ? sg * Tc : 0, rows = PACK ? Tc : T;
+                    const int first = PACK ? TM_PK_S(pk_pf, R0) : __builtin_amdgcn_readfirstlane(p.pair_first[ii]);
+                    const int cn = PACK ? TM_PK_S(pk_pc, R0) : __builtin_amdgcn_readfirstlane(p.pair_cnt[ii]);
+                    // pair-major: a keyword row (and its norm, and its attention slot) is fetched once, not once per frame
+                    for (int j = 0; j < cn; ++j) {
+                        const float *k = p.kb + (int64_t)(first + j) * TM_H;
+                        const v4f k0 = *reinterpret_cast<const v4f *>(k + 4 * lane), k1 = *reinterpret_cast<const v4f *>(k + 256 + 4 * lane);
+                        float *arow = p.att + (int64_t)p.att_idx[first + j] * (SPLIT ? p.T : rows) + sfr0;
+                        float nk = 0.f;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) nk += k0[i] * k0[i] + k1[i] * k1[i];
-                    nk = wave_sum(nk);
-                    for (int t = wave; t < T; t += 8) {
-                        const v4f f0 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
-                        float nf = 0.f, d = 0.f;
+                        for (int i = 0; i < 4; ++i) nk += k0[i] * k0[i] + k1[i] * k1[i];
+                        nk = wave_sum(nk);
+                        for (int t = wave; t < rows; t += 8) {
+                            const float *fr = F + (R0 + t) * TM_FLD;
+                            const v4f f0 = *reinterpret_cast<const v4f *>(fr + 4 * lane), f1 = *reinterpret_cast<const v4f *>(fr + 256 + 4 * lane);
+                            float nf = 0.f, d = 0.f;
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) { nf += f0[i] * f0[i] + f1[i] * f1[i]; d += f0[i] * k0[i] + f1[i] * k1[i]; }
-                        nf = wave_sum(nf); d = wave_sum(d);
-                        if (lane == 0) {
-                            const float eps = 1e-8f;
-                            const float c = d / (fmaxf(sqrtf(nf), eps) * fmaxf(sqrtf(nk), eps));
-                            arow[t] = (c + 1.0f) * 0.49f;
+                            for (int i = 0; i < 4; ++i) { nf += f0[i] * f0[i] + f1[i] * f1[i]; d += f0[i] * k0[i] + f1[i] * k1[i]; }
+                            nf = wave_sum(nf); d = wave_sum(d);
+                            if (lane == 0) {
+                                const float eps = 1e-8f;
+                                const float c = d / (fmaxf(sqrtf(nf), eps) * fmaxf(sqrtf(nk), eps));
+                                arow[t] = (c + 1.0f) * 0.49f;
+                            }
                         }
                     }
-                }
+                } while (PACK && ++sg < pkN);
                 break;
             }
             case STAIR_TILE_ROWDOT_SIGMOID: {         // HasItem: sigmoid(w . row + b) (modules.py:131-137)
                 if (KIND == KIND_CHAIN) break;
                 const v4f w0 = *reinterpret_cast<const v4f *>(p.vw + 4 * lane), w1 = *reinterpret_cast<const v4f *>(p.vw + 256 + 4 * lane);
-                const float off = p.vb[0] + (p.extra ? p.extra[ii] : 0.f);
-                for (int t = wave; t < T; t += 8) {
-                    const v4f f0 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                const float vb0 = p.vb[0], extra0 = PACK ? 0.f : (p.extra ? p.extra[ii] : 0.f);
+                for (int R = wave; R < T; R += 8) {
+                    const float off = vb0 + (PACK ? pk_ex[R] : extra0);     // (the `extra` term is the row's instance's)
+                    const v4f f0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
                     float d = 0.f;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) d += f0[i] * w0[i] + f1[i] * w1[i];
                     d = wave_sum(d);
-                    if (lane == 0) p.out[oslot * p.out_gstride + sfr0 + t] = sigmoid_acc(d + off);
+                    if (lane == 0) TM_ROW_VAL(R) = sigmoid_acc(d + off);
                 }
                 break;
             }
@@ -1135,8 +964,8 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                 if (KIND == KIND_CHAIN) break;
                 const v4f g0 = *reinterpret_cast<const v4f *>(p.gamma + 4 * lane), g1 = *reinterpret_cast<const v4f *>(p.gamma + 256 + 4 * lane);
                 const v4f b0 = *reinterpret_cast<const v4f *>(p.beta + 4 * lane), b1 = *reinterpret_cast<const v4f *>(p.beta + 256 + 4 * lane);
-                for (int t = wave; t < T; t += 8) {
-                    v4f f0 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + t * TM_FLD + 256 + 4 * lane);
+                for (int R = wave; R < T; R += 8) {
+                    v4f f0 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 4 * lane), f1 = *reinterpret_cast<const v4f *>(F + R * TM_FLD + 256 + 4 * lane);
                     float sum = 0.f;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) sum += f0[i] + f1[i];
@@ -1147,7 +976,7 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
                     const float rstd = rsqrtf(wave_sum(sq) / (float)TM_H + p.ln_eps);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { f0[i] = (f0[i] - mean) * rstd * g0[i] + b0[i]; f1[i] = (f1[i] - mean) * rstd * g1[i] + b1[i]; }
-                    float *dst = p.out + oslot * p.out_gstride + orow0 + (int64_t)t * TM_H;
+                    float *dst = TM_ROW_OUT(TM_TILE_OUT, R);
                     *reinterpret_cast<v4f *>(dst + 4 * lane) = f0;
                     *reinterpret_cast<v4f *>(dst + 256 + 4 * lane) = f1;
                 }
@@ -1155,6 +984,14 @@ __global__ __launch_bounds__(512, 1) void tile_mlp_kernel(TmParams pp) {
             }
             default: break;
         }
+#undef TM_ALL_FIRST
+#undef TM_ROW_FIRST
+#undef TM_ROW_OR0
+#undef TM_ROW_VAL
+#undef TM_ROW_OUT
+#undef TM_ROW_SLOT
+#undef TM_ROW_T
+#undef TM_TILE_OUT
     }
     // The queue resets ITSELF: every workgroup takes exactly one ticket >= total (the one that made it leave) and then signs off;
     // the last one to sign off knows that nobody will touch the head again and zeroes both words, so the next launch on the stream

@@ -97,16 +97,18 @@ def test_filter_shape(T, cnt):
                 assert torch.equal(got[:tiles] & ~real, torch.zeros_like(want))
 
 
-@pytest.mark.parametrize('T,cnt', CASES)
-def test_filterframe_shape(T, cnt):
-    """3 layers, the sigmoid attention (with the per-instance keyword term `extra`) between the second and the third, rs_out, STORE"""
+@pytest.mark.parametrize('T,cnt,indexed', [pytest.param(T, cnt, True, id='%d-%d' % (T, cnt)) for T, cnt in CASES] +
+                         [pytest.param(8, 9, False, id='8-9-no_out_idx'), pytest.param(21, 4, False, id='21-4-no_out_idx')])
+def test_filterframe_shape(T, cnt, indexed):
+    """3 layers, the sigmoid attention (with the per-instance keyword term `extra`) between the second and the third, rs_out, STORE
+    (through out_idx, or without one: instance i into tile i of `out`)"""
     from stair_amd import ops
     g = _gen(T, cnt, 2)
     x = torch.randn(cnt, T, H, generator=g)
     vw = torch.randn(H, generator=g) / H ** 0.5; vb = torch.randn(1, generator=g); extra = torch.randn(cnt, generator=g)
-    out_idx = _perm(cnt + 2, cnt, g)
+    out_idx = _perm(cnt + 2, cnt, g) if indexed else torch.arange(cnt, dtype=torch.int32)
     layers = [(d(_lin(i)[0]), d(_lin(i)[1]), 'relu') for i in range(3)]
-    xd, oi, mid = d(x), d(out_idx), (d(vw), d(vb), d(extra))
+    xd, oi, mid = d(x), d(out_idx) if indexed else None, (d(vw), d(vb), d(extra))
 
     def run():
         out = torch.full((cnt + 2, T, H), -3.0, device=DEV)
@@ -246,10 +248,12 @@ def test_dropout_drops_the_same_elements(T, cnt):
 # ---------------------------------------------------------------------------------------------
 
 
-@pytest.mark.parametrize('T,cnt', CASES)
-def test_backward_chain_exclusive_with_first_touch_stores(T, cnt):
+@pytest.mark.parametrize('T,cnt,tail', [pytest.param(T, cnt, 6, id='%d-%d' % (T, cnt)) for T, cnt in CASES] +
+                         [pytest.param(8, 9, 1, id='8-9-store'), pytest.param(21, 4, 1, id='21-4-store')])
+def test_backward_chain_exclusive_with_first_touch_stores(T, cnt, tail):
     """KIND 3 fed by the bits of a forward launch with the same packing: dZ saves, read - add - write into targets of the instances' own,
-    some marked STORE_FIRST (their targets hold a sentinel no result may depend on)"""
+    some marked STORE_FIRST (their targets hold a sentinel no result may depend on).  `store`: the same chain ending in STORE (tail 1),
+    which writes dX over every target whatever it held and whatever its out_idx entry's STORE_FIRST bit says"""
     from stair_amd import ops
     g = _gen(T, cnt, 7)
     dy = torch.randn(cnt, T, H, generator=g)
@@ -269,7 +273,7 @@ def test_backward_chain_exclusive_with_first_touch_stores(T, cnt):
         _, sv, bits = _fwd2(T, cnt, gg)
         out = based.clone()
         gB, gA = torch.zeros(cnt, T, H, device=DEV), torch.zeros(cnt, T, H, device=DEV)
-        _launch(cnt, T, [(wT[1], None, 3), (wT[0], None, 0)], tail=6, X=dyd, x_gstride=T * H, in_bits=bits[1], in_scale=1.0, save_in=gB,
+        _launch(cnt, T, [(wT[1], None, 3), (wT[0], None, 0)], tail=tail, X=dyd, x_gstride=T * H, in_bits=bits[1], in_scale=1.0, save_in=gB,
                 act_bits=[bits[0]], act_scale=1.0, save=[gA], out=out, out_gstride=T * H, out_idx=out_idx, acc_exclusive=1)
         run.sv = sv
         return dict(out=out, gA=gA, gB=gB)
@@ -282,7 +286,7 @@ def test_backward_chain_exclusive_with_first_touch_stores(T, cnt):
     dz2, dz1, dx = _chain_ref(dy, run.sv)
     _close(on['gB'], dz2, 3e-5, 'dZ2'); _close(on['gA'], dz1, 3e-5, 'dZ1')
     for i in range(cnt):
-        ref = dx[i] if first[i] else dx[i] + base[int(tgt[i])].double()
+        ref = dx[i] if first[i] or tail == 1 else dx[i] + base[int(tgt[i])].double()
         _close(got_on[i], ref, 3e-5, ('dX', i))
 
 

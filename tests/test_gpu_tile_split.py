@@ -385,11 +385,13 @@ def _chain_layers():
     return [(_planes(1, True), None, 3), (_planes(0, True), None, 0)]
 
 
-@cases
-@pytest.mark.parametrize('exclusive', [1, 0], ids=['exclusive', 'atomic'])
+@pytest.mark.parametrize('T,cnt,lens,exclusive', [pytest.param(*c, e, id='%s-%s' % (eid, cid)) for c, cid in zip(CASES, IDS) for e, eid in ((1, 'exclusive'), (0, 'atomic'))] +
+                         [pytest.param(*CASES[0], 'store', id='store-' + IDS[0])])
 def test_backward_chain_bits_and_first_touch_stores(T, cnt, lens, exclusive):
     """form 3 fed by the bits of a segmented forward launch: dZ saves (save_in, save[0]), ACCUMULATE into targets of the instances' own
-    -- read - add - write (acc_exclusive) or float atomics, one add per address -- some marked STORE_FIRST (sentinel targets)"""
+    -- read - add - write (acc_exclusive) or float atomics, one add per address -- some marked STORE_FIRST (sentinel targets).
+    `store`: the same chain ending in STORE (tail 1), which writes dX over every target whatever it held"""
+    tail, exclusive = (1, 0) if exclusive == 'store' else (6, exclusive)
     g = _gen(T, cnt, 7)
     dy = torch.randn(cnt, T, H, generator=g)
     tgt = _perm(cnt + 2, cnt, g)
@@ -404,7 +406,7 @@ def test_backward_chain_bits_and_first_touch_stores(T, cnt, lens, exclusive):
     ln = i32(lens) if lens else None
     out = d(base.clone())
     gB, gA = torch.full((cnt, T, H), -3.0, device=DEV), torch.full((cnt, T, H), -3.0, device=DEV)
-    _launch(cnt, T, _chain_layers(), tail=6, X=dyd, x_gstride=T * H, in_bits=bits[1], in_scale=1.0, save_in=gB,
+    _launch(cnt, T, _chain_layers(), tail=tail, X=dyd, x_gstride=T * H, in_bits=bits[1], in_scale=1.0, save_in=gB,
             act_bits=[bits[0]], act_scale=1.0, save=[gA], out=out, out_gstride=T * H, out_idx=out_idx, acc_exclusive=exclusive, len=ln)
     torch.cuda.synchronize()
     r_out = d(base.clone())
@@ -412,7 +414,7 @@ def test_backward_chain_bits_and_first_touch_stores(T, cnt, lens, exclusive):
 
     def run_seg(s, f0, rows):
         sB, sA = torch.zeros(cnt, rows, H, device=DEV), torch.zeros(cnt, rows, H, device=DEV)
-        _launch(cnt, rows, _chain_layers(), tail=6, X=_at(dyd, f0 * H), x_gstride=T * H, in_bits=_seg_bits(bits[1], cnt, T, s), in_scale=1.0, save_in=sB,
+        _launch(cnt, rows, _chain_layers(), tail=tail, X=_at(dyd, f0 * H), x_gstride=T * H, in_bits=_seg_bits(bits[1], cnt, T, s), in_scale=1.0, save_in=sB,
                 act_bits=[_seg_bits(bits[0], cnt, T, s)], act_scale=1.0, save=[sA], out=_at(r_out, f0 * H), out_gstride=T * H, out_idx=out_idx,
                 acc_exclusive=exclusive)
         r_gB[:, f0:f0 + rows] = sB.cpu(); r_gA[:, f0:f0 + rows] = sA.cpu()
@@ -427,7 +429,7 @@ def test_backward_chain_bits_and_first_touch_stores(T, cnt, lens, exclusive):
     dz2, dz1, dx = _chain_ref(dy, sv)
     _close(gB, dz2, 3e-5, 'dZ2'); _close(gA, dz1, 3e-5, 'dZ1')
     for i in range(cnt):
-        ref = dx[i] if first[i] else dx[i] + base[int(tgt[i])].double()
+        ref = dx[i] if first[i] or tail == 1 else dx[i] + base[int(tgt[i])].double()
         _close(got[i], ref, 3e-5, ('dX', i))
 
 

@@ -48,3 +48,11 @@ def test_no_kernel_spills_while_two_workgroups_can_share_a_cu(tmp_path):
         if not one_per_cu:
             bad.append((k['name'], k['scratch'], k['threads'], regs))
     assert not bad, bad
+
+
+def test_tile_operator_forms_use_no_scratch(tmp_path):
+    """csrc/tile_mlp.hip is written around "a kernel with ANY scratch pays for its setup at every launch": the nine forms of
+    tile_mlp_kernel (forward, Temporal's backward chain, the backward chains; each plain, packed and split) have none"""
+    forms = [k for k in _kernels(tmp_path) if 'tile_mlp_kernel' in k['name']]
+    assert len(forms) == 9, [k['name'] for k in forms]
+    assert [k['name'] for k in forms if k['scratch'] != 0] == []
