@@ -359,14 +359,33 @@ def pack_questions(items, device, share_clips=True, pin=True):
 # ----------------------------------------------------------------------------------------------
 # checkpoints
 # ----------------------------------------------------------------------------------------------
-def save_checkpoint(output_dir, model, config):
+def save_checkpoint(output_dir, model, config, trainer=None):
     """`config.json` + `pytorch_model.bin` holding the state_dict -- the layout evaluate.py:136-139 loads.
     (train_module.py:212-216 pickles the whole module object instead; a state_dict is what its own evaluate.py and
-    this loader expect, and it loads without executing anything.)"""
+    this loader expect, and it loads without executing anything.)
+    trainer (a stair_amd.train.Trainer): also `trainer_state.bin`, its state_dict() -- Adam moments, step counts, masks and
+    counters, what a run needs beside the weights to be resumed bit for bit (load_trainer_state, Trainer.load_state_dict).
+    The state is taken first: a refused step raises StairError before any file is touched (Trainer.state_dict; synchronises).
+    Every file is written under a temporary name, fsynced and renamed into place, `trainer_state.bin` last: a job killed while
+    it saves leaves the previous files whole.  Without a trainer an older `trainer_state.bin` in the directory is left alone."""
+    from . import train_state
+    state = trainer.state_dict() if trainer is not None else None
     os.makedirs(output_dir, exist_ok=True)
-    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(output_dir, 'pytorch_model.bin'))
-    with open(os.path.join(output_dir, 'config.json'), 'w') as f:
-        json.dump(config, f)
+    weights = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    train_state.atomic_write(os.path.join(output_dir, 'pytorch_model.bin'), lambda f: torch.save(weights, f))
+    train_state.atomic_write(os.path.join(output_dir, 'config.json'), lambda f: json.dump(config, f), mode='w')
+    if state is not None:
+        train_state.save(os.path.join(output_dir, train_state.STATE_FILE), state)
+
+
+def load_trainer_state(ckpt_dir):
+    """The training state save_checkpoint(..., trainer=...) wrote beside the weights (tensors and plain containers only:
+    train_state.load), for Trainer.load_state_dict.  FileNotFoundError, naming the file, when the checkpoint holds weights only."""
+    from . import train_state
+    path = os.path.join(ckpt_dir, train_state.STATE_FILE)
+    if not os.path.isfile(path):
+        raise FileNotFoundError('%s: the checkpoint has no training state (it was saved without trainer=)' % path)
+    return train_state.load(path)
 
 
 def load_checkpoint(ckpt_dir, device=None, pretrain_modules=()):

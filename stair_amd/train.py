@@ -433,6 +433,99 @@ class Trainer:
             self._raise_if_failed(*entry)
         self._status = keep[-16:]
 
+    # ---- stopping and resuming ------------------------------------------------------------------------------------------------
+    def _hyper(self):
+        """the constructor arguments that change the trajectory, as a training state holds them (train_state.HYPER)"""
+        from .train_state import plain
+        return {'lr': self.lr, 'betas': plain(self.betas), 'eps': self.eps, 'weight_decay': self.wd,
+                'scheduler_start_factor': self.sched[0], 'scheduler_end_factor': self.sched[1], 'scheduler_total_iters': self.sched[2],
+                'skip_untouched': self.skip_untouched, 'dropout': self.dropout, 'dropout_seed': self.dropout_seed,
+                'train_module_before_iters': self.before_iters, 'train_decoder_after_iters': self.after_iters,
+                'decoder_loss_weight': self.decoder_loss_weight, 'module_loss_weight': self.module_loss_weight,
+                'contrastive_window': self.contrastive_window, 'no_intermediate': plain(self.no_intermediate),
+                'max_grad_norm': self.max_grad_norm}
+
+    def state_dict(self):
+        """The training state (stair_amd.train_state): both Adam moments, the per-tensor step counts, the touched mask and its host
+        view, the trainable flags, `iters`, `questions_seen`, `world` and the trajectory-changing constructor arguments -- per weight
+        NAME, unpadded, on the CPU.  Together with model.state_dict() (the weights are NOT in here) it is all a run needs to go on
+        bit for bit; see load_state_dict for the order.
+
+        SYNCHRONISES: it first calls check(wait=True), so a refused step raises StairError BEFORE a checkpoint is written (a second
+        call then succeeds and holds the last good step, which is what the device holds by construction; `iters` and
+        `questions_seen` have moved past the refused window, as check() documents), then copies the buffers to the host."""
+        self.check(wait=True)
+        names = self.model._weight_names
+        m, v = self.exp_avg.cpu(), self.exp_avg_sq.cpu()
+        steps, touched = self.steps.cpu().tolist(), self.touched.cpu().tolist()
+        tensors = {}
+        for i, (nme, p) in enumerate(zip(names, self._params)):
+            lo, hi = self.offsets[i], self.offsets[i] + p.numel()
+            if steps[i] != int(steps[i]):
+                raise RuntimeError('step count of %s is %r, not a whole number' % (nme, steps[i]))
+            tensors[nme] = {'exp_avg': m[lo:hi].clone().view(p.shape), 'exp_avg_sq': v[lo:hi].clone().view(p.shape),
+                            'steps': int(steps[i]), 'touched': int(touched[i]), 'ever': bool(self._ever[i]),
+                            'trainable': bool(p.requires_grad)}
+        from .train_state import FORMAT
+        return {'format': FORMAT, 'names': list(names), 'numels': [p.numel() for p in self._params], 'tensors': tensors,
+                'iters': int(self.iters), 'questions_seen': int(self.questions_seen), 'world': int(self.world), 'hyper': self._hyper()}
+
+    def load_state_dict(self, state, strict=True):
+        """Puts a training state back (state_dict() of an earlier Trainer, data.load_trainer_state of a checkpoint, or
+        train_state.from_torch_adam of a torch optimizer): exp_avg, exp_avg_sq, steps, touched, the host view of the mask, `iters`
+        and `questions_seen`.  The order that works:
+
+            model, config = data.load_checkpoint(ckpt_dir)      # the weights first ...
+            model = model.to(device)
+            trainer = Trainer(model, ...)                       # ... because the Trainer turns the parameters into views of its
+            trainer.load_state_dict(data.load_trainer_state(ckpt_dir))      # flat buffer; then the state
+
+        The state is validated as a whole first (train_state.validate) and NOTHING is written on any failure.  Weights,
+        requires_grad flags and gradient buffers are never touched; a schedule that froze or thawed parameters re-applies its flags
+        before this call.  Pending status words are checked (a refused step of THIS Trainer still raises StairError) and then
+        dropped with the pending gradient-norm figures: they belong to the run that is being replaced.  Synchronises.
+
+        strict=True (default): a trajectory-changing constructor argument (lr, betas, eps, weight_decay, the three scheduler numbers,
+        skip_untouched, dropout, dropout_seed, train_module_before_iters, train_decoder_after_iters, decoder_loss_weight,
+        module_loss_weight, contrastive_window, no_intermediate, max_grad_norm), `world`, or a trainable flag that differs
+        between the state and this Trainer / model raises ONE ValueError listing every difference as `name: saved -> now`.
+        strict=False: exactly those fields keep THIS Trainer's values -- a deliberate change of schedule --, moments, step counts,
+        masks and counters are loaded all the same.
+        At world > 1 every rank loads the same state."""
+        from . import train_state as TS
+        names = self.model._weight_names
+        TS.validate(state, names, [p.numel() for p in self._params], {nme: tuple(p.shape) for nme, p in zip(names, self._params)})
+        if strict:
+            now, diffs = self._hyper(), []
+            for key in TS.HYPER:
+                if TS.plain(state['hyper'][key]) != now[key]:
+                    diffs.append('%s: %r -> %r' % (key, state['hyper'][key], now[key]))
+            if state['world'] != self.world:
+                diffs.append('world: %r -> %r' % (state['world'], self.world))
+            for nme, p in zip(names, self._params):
+                if state['tensors'][nme]['trainable'] != bool(p.requires_grad):
+                    diffs.append('%s.trainable: %r -> %r' % (nme, state['tensors'][nme]['trainable'], bool(p.requires_grad)))
+            if diffs:
+                raise ValueError('the training state was saved by another schedule (saved -> now): ' + '; '.join(diffs) +
+                                 '.  Build the Trainer / set requires_grad as saved, or pass strict=False to keep the present values')
+        self.check(wait=True)
+        m, v = torch.zeros(self.n), torch.zeros(self.n)       # the padding between segments stays zero
+        for i, (nme, p) in enumerate(zip(names, self._params)):
+            t = state['tensors'][nme]
+            m[self.offsets[i]: self.offsets[i] + p.numel()] = t['exp_avg'].reshape(-1)
+            v[self.offsets[i]: self.offsets[i] + p.numel()] = t['exp_avg_sq'].reshape(-1)
+        self.exp_avg.copy_(m)
+        self.exp_avg_sq.copy_(v)
+        self.steps.copy_(torch.tensor([float(state['tensors'][nme]['steps']) for nme in names]))
+        self.touched.copy_(torch.tensor([state['tensors'][nme]['touched'] for nme in names], dtype=torch.int32))
+        self._ever = [bool(state['tensors'][nme]['ever']) for nme in names]
+        self.iters, self.questions_seen = int(state['iters']), int(state['questions_seen'])
+        torch.cuda.synchronize(self.flat_p.device)
+        self._status = []
+        if self.seg_grad_norm is not None:
+            self._norm_free += [host for _, host, _ in self._norms]
+            self._norms = []
+
     def grad_norms_by_name(self):
         """{weight name: L2 norm of its reduced, unclipped gradient in the last step} -- 0.0 for tensors no program of the
         window touched.  Needs max_grad_norm; synchronises (a device -> host copy)."""
