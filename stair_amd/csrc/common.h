@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 
 #include "../../include/stair_hip.h"
 
@@ -135,7 +136,6 @@ struct PolicyScope {
 // ---- internal launchers shared between the C ABI and the plan runner ----------------------
 int launch_gemm(const stair_gemm_args &a, hipStream_t s);
 int launch_lstm(const stair_lstm_args &a, hipStream_t s);
-int launch_lstm_bwd(const stair_lstm_bwd_args &a, hipStream_t s);
 // STAIR_GEMM_TRACE=1: every GEMM launcher prints its shape to stderr (tools/gemm_shapes.py joins the lines with a rocprofv3 kernel trace)
 inline bool gemm_trace_on() { static const bool on = env_int("STAIR_GEMM_TRACE", 0) == 1; return on; }
 
@@ -145,17 +145,42 @@ struct TransposeBatch {          // up to 32 matrices transposed by one launch (
     int count;
 };
 int launch_transpose_many(const TransposeBatch &tb, int total_tiles, hipStream_t s);
+int launch_gemm_tn(const stair_gemm_tn_args &a, hipStream_t s);
+int launch_gemm_tn_batch(const stair_gemm_tn_args *a, int n, hipStream_t s);
 int launch_gemm_tn_tr(const stair_gemm_tn_args &a, hipStream_t s);      // -1: not this kernel's shape
-int launch_gemm_tn_tr_slabs(const stair_gemm_tn_args &a, float *scratch, hipStream_t s);    // slab partials into scratch [8 N K] + queued reduction
-int tn_x3tr_queue(const float *P, float *dst, int nslab, int count4, hipStream_t s);
-// csrc/gemm_tn_x3tr.hip: slab partials of a weight-gradient product into scratch; tn_x3tr_flush adds every queued product's slabs
-// to its destination in fixed order (one launch), on the same stream and thread
+bool tn_tr_takes(const stair_gemm_tn_args &a);
 bool tn_x3tr_takes(const stair_gemm_tn_args &a);
 int tn_x3tr_slabs(int64_t M);
 int64_t tn_x3tr_scratch_floats(int64_t M, int64_t N, int64_t K);
-int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, hipStream_t s, int b_shift = 0, int64_t b_rows = 0);
-int tn_x3tr_flush(hipStream_t s);
-void tn_x3tr_discard();          // forget queued sums (a pass that failed half-way must not leak them into the next one)
+
+// ---- weight-gradient products dW += dZ^T (rs X), db += colsum(dZ) of a reverse pass (csrc/gemm_tn_x3tr.hip; routing table: DESIGN.md)
+// The slab kernels store partial sums in scratch; a TnSums is the queue of the sums still to be added to their destinations, in
+// slab order, one tn_slab_reduce_kernel launch per flush().  A pass owns one: what a pass that fails half-way queued dies with it.
+struct XtReduceEntry { const float *P; float *dst; int nslab; int count4; };     // count4 float4 elements per slab
+struct XtReduceBatch { XtReduceEntry e[40]; int n; };
+// Where a product's slabs go.  RING: pieces of a region in turn; when it wraps, the pending sums are added first (they read the
+// pieces).  RESERVED: a region the plan sized for this one product.  BUMP: pieces in turn, never reused; no room: the atomic kernel.
+struct TnScratch {
+    enum Kind { RING, RESERVED, BUMP } kind;
+    float *base; int64_t floats, at;
+    bool fits(int64_t need) const { return base && (kind == RESERVED || need <= (kind == RING ? floats : floats - at)); }
+};
+// A call site's policy: the rows from which a product takes the slab kernel; whether the < 32 rows past the last whole stage are
+// split off (otherwise a product whose M is no multiple of 32 goes to the atomic kernel whole); and where what the slab kernel does
+// not take goes: launched at once (launch_gemm_tn) or, with `batch`, appended there for the caller's launch_gemm_tn_batch.
+struct TnRoute { int min_rows; bool split_tail; std::vector<stair_gemm_tn_args> *batch; };
+struct TnSums {
+    hipStream_t s;
+    XtReduceBatch b;
+    explicit TnSums(hipStream_t stream) : s(stream) { b.n = 0; }
+    TnSums(const TnSums &) = delete;
+    int queue(const XtReduceEntry *e, int n);                      // flushes first where the ordering rules ask for it
+    int flush();
+    int take(TnScratch &scratch, int64_t need, float **piece);     // needs scratch.fits(need)
+    int product(const stair_gemm_tn_args &a, TnScratch &scratch, const TnRoute &route);     // the router
+};
+int launch_gemm_tn_tr_slabs(const stair_gemm_tn_args &a, float *scratch, TnSums &sums);    // slab partials into scratch [8 N K], sums queued; needs tn_tr_takes
+int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, TnSums &sums, int b_shift = 0, int64_t b_rows = 0);      // needs tn_x3tr_takes
 int launch_lstm_rec_coop(const stair_lstm_args &a, hipStream_t s);
 bool lstm_coop_usable(int Hh);
 int64_t lstm_coop_ws_bytes(int n);
@@ -176,7 +201,7 @@ int launch_lstm_project(const stair_lstm_args &a, hipStream_t s);
 int launch_lstm_recur(const stair_lstm_args &a, hipStream_t s);
 int launch_lstm_zero_tail(const stair_lstm_args &a, hipStream_t s);
 int launch_lstm_bwd_recur(const stair_lstm_bwd_args &a, hipStream_t s);
-int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, hipStream_t s);
+int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, TnSums &sums);        // on sums.s; the caller flushes
 int launch_lstm_bwd_clear_tail(const stair_lstm_bwd_args &a, hipStream_t s);
 bool lstm_bwd_takes_coop(const stair_lstm_bwd_args &a);
 int64_t lstm_coop_bwd_ws_bytes(int n);
@@ -188,8 +213,6 @@ int launch_split_planes_tiled(const float *x, void *hi, void *lo, int rows, int 
 int launch_split_planes_pad(const float *x, int64_t ldx, void *hi, void *lo, int rows, int cols, int Kp, bool tiled, hipStream_t s, int row_off = 0, int total_rows = 0);
 int launch_gemm_planes(const stair_gemm_planes_args &a, hipStream_t s);
 bool gemm_planes_supported(int64_t M, int N, int K);
-int launch_gemm_tn(const stair_gemm_tn_args &a, hipStream_t s);
-int launch_gemm_tn_batch(const stair_gemm_tn_args *a, int n, hipStream_t s);
 int launch_tile_mlp(const stair_tile_mlp_args &a, hipStream_t s);          // csrc/tile_mlp.hip
 int launch_tile_mlp_batch(const stair_tile_mlp_args *args, int n, unsigned *counter, hipStream_t s);   // <= 8 buckets, one launch
 bool tile_mlp_usable(int H, int T);

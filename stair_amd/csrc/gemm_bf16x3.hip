@@ -1011,9 +1011,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_bf16x3_t256_kernel(XTnParams p
     }
 }
 
-int launch_gemm_tn_bf16x3(const stair_gemm_tn_args &a, hipStream_t s) {
-    if (a.M == 0) return 0;
-    const bool one = matmul_mode() == STAIR_MATMUL_BF16;
+// The 128 x 128 kernel's parameters for one product; *slabs: into how many row slabs it is cut (grid = tilesN * tilesK * slabs)
+static XTnParams xtn_params(const stair_gemm_tn_args &a, int *slabs) {
     XTnParams p;
     p.A = a.A; p.lda = a.lda; p.B = a.B; p.ldb = a.ldb; p.b_gstride = a.b_gstride; p.b_gidx = a.b_gidx;
     p.R = a.rows_per_group; p.row_scale = a.row_scale; p.rs_gstride = a.rs_gstride; p.rs_gidx = a.rs_gidx;
@@ -1022,13 +1021,6 @@ int launch_gemm_tn_bf16x3(const stair_gemm_tn_args &a, hipStream_t s) {
     p.C64 = det_shadow(a.C); p.colsum64 = a.colsum ? det_shadow(a.colsum) : nullptr; p.colsum2_64 = a.colsum2 ? det_shadow(a.colsum2) : nullptr;
     p.tilesN = (a.N + 127) / 128; p.tilesK = (a.K + 127) / 128;
     p.fast8 = 0;
-    const bool bx = a.b_is_bf16 != 0;
-    if (bx) {
-        STAIR_CHECK(!one, "bf16 B rows need the bf16x3 matmul mode");
-        STAIR_CHECK(a.rows_per_group == 1 && !a.b_gidx && !a.row_scale && a.b_gstride == a.ldb && a.K % 8 == 0 && a.ldb % 4 == 0,
-                    "bf16 B rows: plain row matrix only (rows_per_group 1, no index, no row scale), K % 8 == 0");
-        STAIR_CHECK((reinterpret_cast<uintptr_t>(a.B) & 7) == 0, "bf16 B rows must be 8-byte aligned");
-    }
     const bool plain_matrix = !p.b_gidx && !p.rs_gidx && p.b_gstride == (int64_t)p.R * p.ldb && (!p.row_scale || p.rs_gstride == p.R);
     if (a.M % 8 == 0 && a.M >= 8) {
         if (p.R % 8 == 0) p.fast8 = 1;
@@ -1039,7 +1031,30 @@ int launch_gemm_tn_bf16x3(const stair_gemm_tn_args &a, hipStream_t s) {
     } else if (plain_matrix) {
         p.fast8 = 2;                  // ragged row count (e.g. the text encoder's sum of question lengths)
     }
-    if (bx) {                     // the long dW_ih shapes: row-major LDS tiles read transposed (csrc/gemm_tn_tr.hip)
+    const int tiles = p.tilesN * p.tilesK;
+    // M is split into slabs so that ~512 workgroups (2 per CU) exist; more slabs only add fp32 atomics (each slab adds
+    // its whole N x K tile set: measured 172 -> 205 TFLOP/s at M=32768, N=K=512 going from 1024 to 512 workgroups)
+    *slabs = std::max(1, std::min((a.M + 255) / 256, (512 + tiles - 1) / tiles));
+    *slabs = (*slabs + 7) / 8 * 8;                                 // a multiple of the XCD count
+    p.mslab = ((a.M + *slabs - 1) / *slabs + 63) / 64 * 64;
+    if (a.M <= p.mslab) p.C64 = nullptr;           // ONE slab holds every row: one add per element, the float atomic is reproducible as it is
+                                                   // (the bias sums still meet from several threads of a workgroup: they keep their shadow)
+    return p;
+}
+
+int launch_gemm_tn_bf16x3(const stair_gemm_tn_args &a, hipStream_t s) {
+    if (a.M == 0) return 0;
+    const bool one = matmul_mode() == STAIR_MATMUL_BF16;
+    const bool bx = a.b_is_bf16 != 0;
+    if (bx) {
+        STAIR_CHECK(!one, "bf16 B rows need the bf16x3 matmul mode");
+        STAIR_CHECK(a.rows_per_group == 1 && !a.b_gidx && !a.row_scale && a.b_gstride == a.ldb && a.K % 8 == 0 && a.ldb % 4 == 0,
+                    "bf16 B rows: plain row matrix only (rows_per_group 1, no index, no row scale), K % 8 == 0");
+        STAIR_CHECK((reinterpret_cast<uintptr_t>(a.B) & 7) == 0, "bf16 B rows must be 8-byte aligned");
+    }
+    int slabs;
+    const XTnParams p = xtn_params(a, &slabs);
+    if (bx) {                   // the long dW_ih shapes: row-major LDS tiles read transposed (csrc/gemm_tn_tr.hip)
         const int rc = launch_gemm_tn_tr(a, s);
         if (rc >= 0) return rc;
     }
@@ -1049,10 +1064,10 @@ int launch_gemm_tn_bf16x3(const stair_gemm_tn_args &a, hipStream_t s) {
         // the decoder's dW at M = 2048 took 122 us here against ~40 us on the 128 x 128 kernel, so M must be long)
         if (t2 >= 16 && p.fast8 == 1 && !p.row_scale && a.M % 64 == 0 && a.M >= 16384) {
             XTnParams q = p;
-            q.tilesN = t2n; q.tilesK = t2k;
-            int slabs = std::max(1, std::min(a.M / 64, (512 + t2 - 1) / t2));
-            slabs = (slabs + 7) / 8 * 8;
-            q.mslab = ((a.M + slabs - 1) / slabs + 63) / 64 * 64;
+            q.tilesN = t2n; q.tilesK = t2k;             // (q.C64 is set: the >= 8 slabs of p never hold all of >= 16384 rows in one)
+            int slabs2 = std::max(1, std::min(a.M / 64, (512 + t2 - 1) / t2));
+            slabs2 = (slabs2 + 7) / 8 * 8;
+            q.mslab = ((a.M + slabs2 - 1) / slabs2 + 63) / 64 * 64;
             const size_t shmem2 = 2 * 2 * 2 * IMG2 * sizeof(__bf16);
             STAIR_ACCT_MFMA("gemm_tn_bf16x3_t256", ((int64_t)a.M * a.N * 4 + (int64_t)a.M * a.K * (bx ? 2 : 4) + (int64_t)a.N * a.K * 4), 2ll * a.M * a.N * a.K);
             static bool attr_set = false;
@@ -1065,22 +1080,15 @@ int launch_gemm_tn_bf16x3(const stair_gemm_tn_args &a, hipStream_t s) {
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem2));
                 attr_set = true;
             }
-            if (bx) hipLaunchKernelGGL((gemm_tn_bf16x3_t256_kernel<3, true>), dim3(t2 * slabs), dim3(512), shmem2, s, q);
-            else if (one) hipLaunchKernelGGL(gemm_tn_bf16x3_t256_kernel<1>, dim3(t2 * slabs), dim3(512), shmem2, s, q);
-            else hipLaunchKernelGGL(gemm_tn_bf16x3_t256_kernel<3>, dim3(t2 * slabs), dim3(512), shmem2, s, q);
+            if (bx) hipLaunchKernelGGL((gemm_tn_bf16x3_t256_kernel<3, true>), dim3(t2 * slabs2), dim3(512), shmem2, s, q);
+            else if (one) hipLaunchKernelGGL(gemm_tn_bf16x3_t256_kernel<1>, dim3(t2 * slabs2), dim3(512), shmem2, s, q);
+            else hipLaunchKernelGGL(gemm_tn_bf16x3_t256_kernel<3>, dim3(t2 * slabs2), dim3(512), shmem2, s, q);
             STAIR_LAUNCH_CHECK();
             return 0;
         }
     }
     const int tiles = p.tilesN * p.tilesK;
-    // M is split into slabs so that ~512 workgroups (2 per CU) exist; more slabs only add fp32 atomics (each slab adds
-    // its whole N x K tile set: measured 172 -> 205 TFLOP/s at M=32768, N=K=512 going from 1024 to 512 workgroups)
-    int slabs = std::max(1, std::min((a.M + 255) / 256, (512 + tiles - 1) / tiles));
-    slabs = (slabs + 7) / 8 * 8;                                   // a multiple of the XCD count
-    p.mslab = ((a.M + slabs - 1) / slabs + 63) / 64 * 64;
     const size_t shmem = 2 * 2 * 2 * IMG * sizeof(__bf16);
-    if (a.M <= p.mslab) p.C64 = nullptr;           // ONE slab holds every row: one add per element, the float atomic is reproducible as it is
-                                                   // (the bias sums still meet from several threads of a workgroup: they keep their shadow)
     const bool plain = !p.row_scale && a.M % 64 == 0 && p.mslab % 64 == 0;
     STAIR_ACCT_MFMA("gemm_tn_bf16x3", ((int64_t)a.M * a.N * 4 + (int64_t)a.M * a.K * (bx ? 2 : 4) + (int64_t)a.N * a.K * 4), 2ll * a.M * a.N * a.K);
     // non-PLAIN launches without a row scale take the kernels that keep no scale registers (RS = false); bf16 B rows never
@@ -1119,26 +1127,9 @@ int launch_gemm_tn_batch(const stair_gemm_tn_args *a, int n, hipStream_t s) {
         b.first[0] = 0;
         for (int i = 0; i < XTN_BATCH; ++i) {
             if (i >= b.n) { b.p[i] = b.p[0]; b.first[i + 1] = b.first[b.n]; continue; }
-            const stair_gemm_tn_args &g = a[i0 + i];
-            XTnParams &p = b.p[i];
-            p.A = g.A; p.lda = g.lda; p.B = g.B; p.ldb = g.ldb; p.b_gstride = g.b_gstride; p.b_gidx = g.b_gidx;
-            p.R = g.rows_per_group; p.row_scale = g.row_scale; p.rs_gstride = g.rs_gstride; p.rs_gidx = g.rs_gidx;
-            p.C = g.C; p.ldc = g.ldc; p.M = g.M; p.N = g.N; p.K = g.K;
-            p.colsum = g.colsum; p.colsum2 = g.colsum2;
-            p.C64 = det_shadow(g.C); p.colsum64 = g.colsum ? det_shadow(g.colsum) : nullptr; p.colsum2_64 = g.colsum2 ? det_shadow(g.colsum2) : nullptr;
-            p.tilesN = (g.N + 127) / 128; p.tilesK = (g.K + 127) / 128;
-            p.fast8 = 0;
-            const bool plain_matrix = !p.b_gidx && !p.rs_gidx && p.b_gstride == (int64_t)p.R * p.ldb && (!p.row_scale || p.rs_gstride == p.R);
-            if (g.M % 8 == 0 && g.M >= 8) {
-                if (p.R % 8 == 0) p.fast8 = 1;
-                else if (plain_matrix) { p.R = 8; p.b_gstride = 8 * p.ldb; p.rs_gstride = 8; p.fast8 = 1; }
-            } else if (plain_matrix) p.fast8 = 2;
-            const int tiles = p.tilesN * p.tilesK;
-            int slabs = std::max(1, std::min((g.M + 255) / 256, (512 + tiles - 1) / tiles));
-            slabs = (slabs + 7) / 8 * 8;
-            p.mslab = ((g.M + slabs - 1) / slabs + 63) / 64 * 64;
-            if (g.M <= p.mslab) p.C64 = nullptr;
-            b.first[i + 1] = b.first[i] + tiles * slabs;
+            int slabs;
+            b.p[i] = xtn_params(a[i0 + i], &slabs);
+            b.first[i + 1] = b.first[i] + b.p[i].tilesN * b.p[i].tilesK * slabs;
         }
         hipLaunchKernelGGL(gemm_tn_bf16x3_batch_kernel, dim3(b.first[b.n]), dim3(256), shmem, s, b);
         STAIR_LAUNCH_CHECK();

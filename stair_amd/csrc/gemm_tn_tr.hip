@@ -273,22 +273,21 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
         }
 }
 
-// Returns -1 when the shape is not this kernel's (the caller falls back to csrc/gemm_bf16x3.hip), 0 on launch, 1 on error.
-int launch_gemm_tn_tr(const stair_gemm_tn_args &a, hipStream_t s) { return launch_gemm_tn_tr_slabs(a, nullptr, s); }
+bool tn_tr_takes(const stair_gemm_tn_args &a) {
+    if (!a.b_is_bf16 || a.row_scale || a.b_gidx || a.colsum || a.colsum2) return false;
+    if (a.rows_per_group != 1 && a.b_gstride != (int64_t)a.rows_per_group * a.ldb) return false;
+    if (a.N % 256 || a.K % 256 || a.M % (8 * 64) || a.M < 2048) return false;     // >= 4 stages per slab; measured down to M = 2048 (32 questions)
+    if (32 * a.lda + 256 >= (1ll << 31) || 32 * a.ldb + 256 >= (1ll << 31)) return false;
+    if (a.lda % 4 || a.ldb % 8 || (reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.B) & 15)) return false;
+    return matmul_mode() == STAIR_MATMUL_BF16X3;
+}
 
-// scratch (8 * N * K floats, needs ldc == K): the slabs' partial products are stored there and queued for the fixed-order reduction
-// of csrc/gemm_tn_x3tr.hip (tn_x3tr_flush on the same stream adds them to C): no atomics, the same sum every run
-int launch_gemm_tn_tr_slabs(const stair_gemm_tn_args &a, float *scratch, hipStream_t s) {
-    if (!a.b_is_bf16 || a.row_scale || a.b_gidx || a.colsum || a.colsum2) return -1;
-    if (a.rows_per_group != 1 && a.b_gstride != (int64_t)a.rows_per_group * a.ldb) return -1;
-    if (a.N % 256 || a.K % 256 || a.M % (8 * 64) || a.M < 2048) return -1;        // >= 4 stages per slab; measured down to M = 2048 (32 questions)
-    if (32 * a.lda + 256 >= (1ll << 31) || 32 * a.ldb + 256 >= (1ll << 31)) return -1;
-    if (a.lda % 4 || a.ldb % 8 || (reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.B) & 15)) return -1;
-    if (matmul_mode() != STAIR_MATMUL_BF16X3) return -1;
+// P: the slabs' partial products are stored there (8 * N * K floats, needs ldc == K); without it they are added into C
+static int launch_tr(const stair_gemm_tn_args &a, float *P, hipStream_t s) {
     TrParams p;
     p.A = a.A; p.lda = a.lda; p.B = reinterpret_cast<const __bf16 *>(a.B); p.ldb = a.ldb; p.C = a.C; p.ldc = a.ldc;
     p.M = a.M; p.N = a.N; p.K = a.K;
-    p.P = scratch && a.ldc == a.K ? scratch : nullptr;
+    p.P = P;
     p.C64 = p.P ? nullptr : det_shadow(a.C);
     p.tilesN = a.N / 256; p.tilesK = a.K / 256;
     p.mslab = a.M / 8;                                             // a multiple of 64: whole stages, an even number of them
@@ -302,8 +301,18 @@ int launch_gemm_tn_tr_slabs(const stair_gemm_tn_args &a, float *scratch, hipStre
     STAIR_ACCT_MFMA("gemm_tn_tr", (int64_t)a.M * a.N * 4 + (int64_t)a.M * a.K * 2 + (int64_t)a.N * a.K * 4, 2ll * a.M * a.N * a.K);
     hipLaunchKernelGGL(gemm_tn_tr_kernel, grid, dim3(512), shmem, s, p);
     STAIR_LAUNCH_CHECK();
-    if (p.P) return tn_x3tr_queue(p.P, a.C, 8, (int)((int64_t)a.N * a.K / 4), s);
     return 0;
+}
+
+// Returns -1 when the shape is not this kernel's (the caller falls back to csrc/gemm_bf16x3.hip), 0 on launch, 1 on error.
+int launch_gemm_tn_tr(const stair_gemm_tn_args &a, hipStream_t s) { return tn_tr_takes(a) ? launch_tr(a, nullptr, s) : -1; }
+
+// the slabs stored in scratch and queued for the fixed-order reduction (the next flush of `sums` adds them to C): no atomics
+int launch_gemm_tn_tr_slabs(const stair_gemm_tn_args &a, float *scratch, TnSums &sums) {
+    STAIR_CHECK(scratch && a.ldc == a.K && tn_tr_takes(a), "internal: not a stored-slab product of the transposed-read kernel");
+    if (int rc = launch_tr(a, scratch, sums.s)) return rc;
+    const XtReduceEntry e = {scratch, a.C, 8, (int)((int64_t)a.N * a.K / 4)};
+    return sums.queue(&e, 1);
 }
 
 }  // namespace stair

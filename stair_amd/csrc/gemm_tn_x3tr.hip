@@ -276,10 +276,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_x3tr_kernel(XtParams p) {
     }
 }
 
-// dst[i] += sum over slabs, in slab order (deterministic); one launch for every weight of a step
-struct XtReduceEntry { const float *P; float *dst; int nslab; int count4; };     // count4 float4 elements per slab
-struct XtReduceBatch { XtReduceEntry e[40]; int n; };
-
+// dst[i] += sum over slabs, in slab order (deterministic); one launch for every weight of a step (XtReduceBatch: common.h)
 __global__ __launch_bounds__(256) void tn_slab_reduce_kernel(XtReduceBatch b) {
     const XtReduceEntry e = b.e[blockIdx.y];
     for (int i = blockIdx.x * 256 + threadIdx.x; i < e.count4; i += gridDim.x * 256) {
@@ -322,11 +319,10 @@ bool tn_x3tr_takes(const stair_gemm_tn_args &a) {
     return true;
 }
 
-static thread_local XtReduceBatch g_pending;                                      // entries queued by launch_gemm_tn_x3tr, flushed by tn_x3tr_flush (one thread per plan pass)
-
-// Partial products of `a` into scratch (tn_x3tr_scratch_floats floats); the sums reach a.C / a.colsum at the next tn_x3tr_flush on the same stream.
+// Partial products of `a` into scratch (tn_x3tr_scratch_floats floats); the sums reach a.C / a.colsum at the next flush of `sums`.
 // b_shift != 0 (needs a row scale, no gather, K % 128 == 0): the SHIFT form above on the b_rows rows of a.B; row_scale is then a 0 / 1 mask
-int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, hipStream_t s, int b_shift, int64_t b_rows) {
+int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, TnSums &sums, int b_shift, int64_t b_rows) {
+    const hipStream_t s = sums.s;
     STAIR_CHECK(b_shift == 0 || (a.row_scale && !a.b_gidx && !a.rs_gidx && a.K % 128 == 0 && a.rows_per_group == 1 && b_rows >= a.M),
                 "internal: shifted slab product on a masked plain row matrix only");
     XtParams p;
@@ -361,38 +357,69 @@ int launch_gemm_tn_x3tr(const stair_gemm_tn_args &a, float *scratch, hipStream_t
     else if (a.row_scale) hipLaunchKernelGGL((gemm_tn_x3tr_kernel<false, true, false>), grid, dim3(512), XT_LDS, s, p);
     else hipLaunchKernelGGL((gemm_tn_x3tr_kernel<false, false, false>), grid, dim3(512), XT_LDS, s, p);
     STAIR_LAUNCH_CHECK();
-    // one reduction launch adds every queued product to its destination in parallel: two products into the SAME buffer (a weight
-    // used by two buckets outside the per-weight regions) must not share it -- the earlier one is added first
-    bool same_dst = false;
-    for (int i = 0; i < g_pending.n; ++i)
-        same_dst |= g_pending.e[i].dst == a.C || (a.colsum && g_pending.e[i].dst == a.colsum) || (a.colsum2 && g_pending.e[i].dst == a.colsum2);
-    if (same_dst || g_pending.n + 3 > 40) STAIR_CHECK(tn_x3tr_flush(s) == 0, "weight-gradient reduction failed");
-    g_pending.e[g_pending.n++] = {p.P, a.C, p.nslab, (int)((int64_t)a.N * a.K / 4)};
-    if (p.Pc) g_pending.e[g_pending.n++] = {p.Pc, a.colsum, p.nslab, a.N / 4};
-    if (p.Pc && a.colsum2) g_pending.e[g_pending.n++] = {p.Pc, a.colsum2, p.nslab, a.N / 4};
+    const XtReduceEntry e[3] = {{p.P, a.C, p.nslab, (int)((int64_t)a.N * a.K / 4)}, {p.Pc, a.colsum, p.nslab, a.N / 4}, {p.Pc, a.colsum2, p.nslab, a.N / 4}};
+    return sums.queue(e, 3);
+}
+
+// One reduction launch adds every queued product to its destination in parallel: two products into the SAME buffer (a weight
+// used by two buckets outside the per-weight regions) must not share it -- the earlier one is added first; and the queue is added
+// before `n` more would exceed its 40 entries.  Then the entries are appended in order (one without a destination is left out).
+int TnSums::queue(const XtReduceEntry *e, int n) {
+    bool first = b.n + n > 40;
+    for (int i = 0; i < b.n; ++i)
+        for (int j = 0; j < n; ++j) first |= b.e[i].dst == e[j].dst;
+    if (first) STAIR_CHECK(flush() == 0, "weight-gradient reduction failed");
+    for (int j = 0; j < n; ++j)
+        if (e[j].dst) b.e[b.n++] = e[j];
     return 0;
 }
 
-void tn_x3tr_discard() { g_pending.n = 0; }
-
-// another kernel's slab partials (csrc/gemm_tn_tr.hip) join the same fixed-order reduction
-int tn_x3tr_queue(const float *P, float *dst, int nslab, int count4, hipStream_t s) {
-    for (int i = 0; i < g_pending.n; ++i)
-        if (g_pending.e[i].dst == dst) { STAIR_CHECK(tn_x3tr_flush(s) == 0, "weight-gradient reduction failed"); break; }
-    if (g_pending.n + 1 > 40) STAIR_CHECK(tn_x3tr_flush(s) == 0, "weight-gradient reduction failed");
-    g_pending.e[g_pending.n++] = {P, dst, nslab, count4};
-    return 0;
-}
-
-int tn_x3tr_flush(hipStream_t s) {
-    if (g_pending.n == 0) return 0;
-    XtReduceBatch b = g_pending;
-    g_pending.n = 0;
+int TnSums::flush() {
+    if (b.n == 0) return 0;
     int most = 0;
     for (int i = 0; i < b.n; ++i) most = std::max(most, b.e[i].count4);
     hipLaunchKernelGGL(tn_slab_reduce_kernel, dim3((most + 255) / 256, b.n), dim3(256), 0, s, b);
+    b.n = 0;
     STAIR_LAUNCH_CHECK();
     return 0;
+}
+
+int TnSums::take(TnScratch &scr, int64_t need, float **piece) {
+    STAIR_CHECK(scr.fits(need), "internal: slab scratch of a weight-gradient product");
+    if (scr.kind == TnScratch::RING && scr.at + need > scr.floats) {
+        if (int rc = flush()) return rc;
+        scr.at = 0;
+    }
+    *piece = scr.base + scr.at;
+    if (scr.kind != TnScratch::RESERVED) scr.at += need;
+    return 0;
+}
+
+// One weight-gradient product, routed (the table of DESIGN.md): stored-bf16 rows through the transposed-read kernel with its eight
+// slabs stored, else the whole 32-row stages through the slab kernel from route.min_rows rows on -- where the shape is the kernel's
+// and the scratch has room.  What is left, tail rows or the whole product, takes the atomic kernels.
+int TnSums::product(const stair_gemm_tn_args &a, TnScratch &scratch, const TnRoute &route) {
+    float *piece;
+    stair_gemm_tn_args rest = a;
+    if (a.b_is_bf16) {
+        const int64_t need = align_up((int64_t)8 * a.N * a.K, 64);
+        if (a.ldc == a.K && tn_tr_takes(a) && scratch.fits(need)) {
+            if (int rc = take(scratch, need, &piece)) return rc;
+            return launch_gemm_tn_tr_slabs(a, piece, *this);
+        }
+    } else {
+        stair_gemm_tn_args head = a;
+        if (route.split_tail) head.M = a.M & ~31;
+        const int64_t need = align_up(tn_x3tr_scratch_floats(head.M, a.N, a.K), 64);
+        if (head.M >= route.min_rows && tn_x3tr_takes(head) && scratch.fits(need)) {
+            if (int rc = take(scratch, need, &piece)) return rc;
+            if (int rc = launch_gemm_tn_x3tr(head, piece, *this)) return rc;
+            if (head.M == a.M) return 0;
+            rest.A += (int64_t)head.M * a.lda; rest.B += (int64_t)head.M * a.ldb; rest.M -= head.M;
+        }
+    }
+    if (route.batch) { route.batch->push_back(rest); return 0; }
+    return launch_gemm_tn(rest, s);
 }
 
 }  // namespace stair
@@ -404,7 +431,7 @@ extern "C" int stair_gemm_tn_slabs(const stair_gemm_tn_args *args, float *scratc
     STAIR_CHECK(stair::tn_x3tr_takes(*args), "shape not supported: needs the split matmul mode, fp32 operands, N % 256 == 0, K % 128 == 0, ldc == K, "
                                              "M and rows_per_group multiples of 32, 16-byte aligned rows");
     STAIR_CHECK(scratch_floats >= stair::tn_x3tr_scratch_floats(args->M, args->N, args->K), "scratch too small (stair_gemm_tn_slabs_scratch)");
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = stair::launch_gemm_tn_x3tr(*args, scratch, s)) return rc;
-    return stair::tn_x3tr_flush(s);
+    stair::TnSums sums(static_cast<hipStream_t>(stream));
+    if (int rc = stair::launch_gemm_tn_x3tr(*args, scratch, sums)) return rc;
+    return sums.flush();
 }

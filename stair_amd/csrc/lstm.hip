@@ -840,40 +840,15 @@ int launch_lstm_bwd_recur(const stair_lstm_bwd_args &a, hipStream_t s) {
     return 0;
 }
 
-// h(t-1) rows + the four weight-gradient products of a layer whose gate gradients are in a.gates
-// One weight-gradient product of a layer: through the slab-reduced kernel (csrc/gemm_tn_x3tr.hip: no atomics; the sums are added
-// by the caller's tn_x3tr_flush) when the shape is its and the scratch suffices, the < 32 rows past the last whole stage through the
-// atomic kernel (one add per element: still deterministic); otherwise the atomic kernel.
-static int lstm_weight_product(stair_gemm_tn_args g, float *&scr, int64_t &left, hipStream_t s) {
-    if (g.b_is_bf16 && scr) {               // dW_ih on stored-bf16 rows: the transposed-read kernel with its 8 slabs stored, then added in order
-        const int64_t need = align_up((int64_t)8 * g.N * g.K, 64);
-        if (need <= left) {
-            const int rc = launch_gemm_tn_tr_slabs(g, scr, s);
-            if (rc >= 0) {
-                if (rc == 0) { scr += need; left -= need; }
-                return rc;
-            }
-        }
-    }
-    stair_gemm_tn_args h = g;
-    h.M = g.M & ~31;
-    if (scr && h.M >= 2048 && tn_x3tr_takes(h)) {
-        const int64_t need = align_up(tn_x3tr_scratch_floats(h.M, h.N, h.K), 64);
-        if (need <= left) {
-            if (int rc = launch_gemm_tn_x3tr(h, scr, s)) return rc;
-            scr += need; left -= need;
-            if (g.M == h.M) return 0;
-            g.A += (int64_t)h.M * g.lda; g.B += (int64_t)h.M * g.ldb; g.M -= h.M;
-        }
-    }
-    return launch_gemm_tn(g, s);
-}
-
-int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, hipStream_t s) {
+// h(t-1) rows + the four weight-gradient products of a layer whose gate gradients are in a.gates.  From 2048 rows on they take
+// the slab kernels on pieces of a.tn_ws (TnSums::product: no atomics; the caller's flush of `sums` adds the sums), the < 32 rows
+// past the last whole stage the atomic kernel (one add per element: still deterministic), as does a product that finds no room.
+int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, TnSums &sums) {
     if (a.n == 0 || a.rows == 0) return 0;
+    const hipStream_t s = sums.s;
     const int Hh = a.Hh;
-    float *scr = a.tn_ws;
-    int64_t left = a.tn_ws ? a.tn_ws_floats : 0;
+    TnScratch scr = {TnScratch::BUMP, a.tn_ws, a.tn_ws ? a.tn_ws_floats : 0};
+    const TnRoute route = {2048, true, nullptr};
     // dW_hh = dG^T Hprev.  Where the slab kernel takes the product, Hprev is not materialised: h(t-1) of the forward direction is the
     // output row before, of the reverse direction the row behind, so the product reads `out` moved by one row under a 0 / 1 row mask
     // (hprev_ws[0 .. 2 rows): rows floats per direction) -- at 2048 questions the copy was 268 MB written and read again per step.
@@ -888,7 +863,7 @@ int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, hipStream_t s) {
     hh.colsum = a.db_ih[0]; hh.colsum2 = a.db_hh[0];
     const int64_t need_hh = align_up(tn_x3tr_scratch_floats(m_slab, 4 * Hh, Hh), 64);
     const int64_t need_ih = std::max(align_up((int64_t)8 * 4 * Hh * a.I, 64), align_up(tn_x3tr_scratch_floats(m_slab, 4 * Hh, a.I), 64));
-    const bool shifted = scr && m_slab >= 2048 && Hh % 128 == 0 && tn_x3tr_takes(hh) && 2 * (need_hh + need_ih) <= left;
+    const bool shifted = m_slab >= route.min_rows && Hh % 128 == 0 && tn_x3tr_takes(hh) && scr.fits(2 * (need_hh + need_ih));
     const int row_begin = shifted ? m_slab : 0;
     if (shifted) {
         hipLaunchKernelGGL(lstm_hmask_kernel, dim3(a.n), dim3(64), 0, s, a.seq_off, a.seq_len, (int64_t)a.rows, a.hprev_ws);
@@ -906,7 +881,7 @@ int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, hipStream_t s) {
         g.B = a.x_bf16 ? static_cast<const float *>(a.x_bf16) : a.x; g.b_is_bf16 = a.x_bf16 ? 1 : 0;
         g.ldb = a.ldx; g.b_gstride = a.ldx; g.rows_per_group = 1;
         g.C = a.dw_ih[dir]; g.ldc = a.I; g.M = a.rows; g.N = 4 * Hh; g.K = a.I;
-        if (int rc = lstm_weight_product(g, scr, left, s)) return rc;
+        if (int rc = sums.product(g, scr, route)) return rc;
         g.b_is_bf16 = 0;
         g.B = a.hprev_ws + dir * Hh; g.ldb = 2 * (int64_t)Hh; g.b_gstride = 2 * (int64_t)Hh;
         g.C = a.dw_hh[dir]; g.ldc = Hh; g.K = Hh;
@@ -914,15 +889,15 @@ int launch_lstm_bwd_weights(const stair_lstm_bwd_args &a, hipStream_t s) {
         if (shifted) {
             hh.A = g.A; hh.B = a.out + dir * Hh; hh.row_scale = a.hprev_ws + (int64_t)dir * a.rows;
             hh.C = g.C; hh.colsum = g.colsum; hh.colsum2 = g.colsum2;
-            if (need_hh > left) STAIR_FAIL("internal: slab scratch of the dW_hh product");
-            if (int rc = launch_gemm_tn_x3tr(hh, scr, s, dir == 0 ? -1 : 1, a.rows)) return rc;
-            scr += need_hh; left -= need_hh;
+            float *piece;
+            if (int rc = sums.take(scr, need_hh, &piece)) return rc;
+            if (int rc = launch_gemm_tn_x3tr(hh, piece, sums, dir == 0 ? -1 : 1, a.rows)) return rc;
             if (m_slab == a.rows) continue;
             g.A += (int64_t)m_slab * g.lda; g.B += (int64_t)m_slab * g.ldb; g.M = a.rows - m_slab;
             if (int rc = launch_gemm_tn(g, s)) return rc;
             continue;
         }
-        if (int rc = lstm_weight_product(g, scr, left, s)) return rc;
+        if (int rc = sums.product(g, scr, route)) return rc;
     }
     return 0;
 }
@@ -936,11 +911,6 @@ int launch_lstm_bwd_clear_tail(const stair_lstm_bwd_args &a, hipStream_t s) {
                        a.gates, a.rows);
     STAIR_LAUNCH_CHECK();
     return 0;
-}
-
-int launch_lstm_bwd(const stair_lstm_bwd_args &a, hipStream_t s) {
-    if (int rc = launch_lstm_bwd_recur(a, s)) return rc;
-    return launch_lstm_bwd_weights(a, s);
 }
 
 int launch_lstm_zero_tail(const stair_lstm_args &a, hipStream_t s);
@@ -1073,9 +1043,8 @@ extern "C" int stair_lstm_bidir_bwd(const stair_lstm_bwd_args *args, stair_strea
     }
     // with tn_ws the slab-reduced weight gradients are queued by the launcher: added here, before returning (inside
     // stair_plan_backward the plan does that once for both encoders)
-    stair::tn_x3tr_discard();
-    int rc = stair::launch_lstm_bwd(*args, static_cast<hipStream_t>(stream));
-    if (rc == 0) rc = stair::tn_x3tr_flush(static_cast<hipStream_t>(stream));
-    else stair::tn_x3tr_discard();
-    return rc;
+    stair::TnSums sums(static_cast<hipStream_t>(stream));
+    if (int rc = stair::launch_lstm_bwd_recur(*args, sums.s)) return rc;
+    if (int rc = stair::launch_lstm_bwd_weights(*args, sums)) return rc;
+    return sums.flush();
 }

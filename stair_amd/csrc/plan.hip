@@ -2603,6 +2603,7 @@ int det_begin(stair_ctx *ctx, hipStream_t s) {
 }
 
 struct BwdCtx {
+    explicit BwdCtx(hipStream_t stream) : s(stream), tn(stream) {}
     hipStream_t s;
     float *wt;                       // transposed weight images
     float *splitk = nullptr;         // split-K scratch (plan workspace): dX products that overwrite their target stage partials there
@@ -2610,19 +2611,10 @@ struct BwdCtx {
     bool dead(const Lin &l) const { return l.dw == discard && l.db == discard; }
     std::vector<int64_t> wt_off;     // per weight id
     std::vector<char> deferred;      // per weight id: its weight-gradient product runs once, after all buckets (per-weight regions)
-    // scratch ring of the slab-reduced weight-gradient products of the remaining map-level layers (csrc/gemm_tn_x3tr.hip): a product
-    // takes the next piece; when the ring wraps, the pending sums are added first (tn_x3tr_flush)
-    float *tn_ring = nullptr; int64_t tn_ring_floats = 0;
-    mutable int64_t tn_ring_at = 0;
-    int ring_take(int64_t need, float **piece) const {
-        if (tn_ring_at + need > tn_ring_floats) {
-            if (int rc = tn_x3tr_flush(s)) return rc;
-            tn_ring_at = 0;
-        }
-        *piece = tn_ring + tn_ring_at;
-        tn_ring_at += need;
-        return 0;
-    }
+    // the pass's slab-reduced weight-gradient products (common.h TnSums): the sums still to be added -- dropped with this object
+    // when the pass fails half-way -- and the scratch ring of the products that run per bucket and of the vector-level ones
+    TnSums tn;
+    TnScratch tn_ring;
 };
 
 // rows from which a per-bucket weight-gradient product takes the slab-reduced kernel (below it the atomic kernel's single pass is
@@ -2631,7 +2623,7 @@ int g_tn_slab_min_rows = 4096;
 
 // Backward of Y = act(rs * X W^T + b) given dZ (already multiplied by act'):
 //   dW += dZ^T (rs * X);  db += colsum(dZ);  dX (+)= dZ W      (dX is w.r.t. the scaled input rs*X)
-int dense_bwd(const BwdCtx &B, const float *dZ, int groups, int R, int N, int K, const float *X, int64_t ldx, int64_t x_gs,
+int dense_bwd(BwdCtx &B, const float *dZ, int groups, int R, int N, int K, const float *X, int64_t ldx, int64_t x_gs,
               const int32_t *x_gidx, const Lin &l, float *dX, int64_t ldd, int64_t d_gs, const int32_t *d_gidx, int accumulate,
               const float *rs = nullptr, int64_t rs_gs = 0, const int32_t *rs_gidx = nullptr) {
     const int M = groups * R;
@@ -2642,12 +2634,8 @@ int dense_bwd(const BwdCtx &B, const float *dZ, int groups, int R, int N, int K,
     t.C = l.dw; t.ldc = K; t.M = M; t.rows_per_group = R; t.N = N; t.K = K;
     t.colsum = l.db;                 // db += colsum(dZ), summed while the TN kernel stages dZ
     if (!(l.id >= 0 && l.id < (int)B.deferred.size() && B.deferred[l.id]) && !B.dead(l)) {
-        const int64_t need = M >= policy_or(STAIR_OPT_TN_SLAB_MIN_ROWS, g_tn_slab_min_rows) && B.tn_ring && tn_x3tr_takes(t) ? align_up(tn_x3tr_scratch_floats(M, N, K), 64) : 0;
-        if (need && need <= B.tn_ring_floats) {
-            float *piece;
-            if (int rc = B.ring_take(need, &piece)) return rc;
-            if (int rc = launch_gemm_tn_x3tr(t, piece, B.s)) return rc;
-        } else if (int rc = launch_gemm_tn(t, B.s)) return rc;
+        const TnRoute route = {policy_or(STAIR_OPT_TN_SLAB_MIN_ROWS, g_tn_slab_min_rows), false, nullptr};
+        if (int rc = B.tn.product(t, B.tn_ring, route)) return rc;
     }
     if (dX) {
         stair_gemm_args g = {};
@@ -2716,9 +2704,6 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     PolicyScope policy_scope(&ctx->policy);
     TileSwitchForce tile_scope(pl->tile_sw);               // the packing and segments of the forward pass that wrote the saves and bits
     STAIR_CHECK(pl->train, "plan was not built with STAIR_PLAN_TRAIN");
-    // slab products queued by a pass that failed half-way must not be added into THIS pass's buffers: the queue starts empty and
-    // is emptied again however this function returns
-    struct PendingScope { PendingScope() { tn_x3tr_discard(); } ~PendingScope() { tn_x3tr_discard(); } } pending_scope;
     STAIR_CHECK(workspace_bytes >= pl->total * (int64_t)sizeof(float), "workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     Weights W;
@@ -2778,9 +2763,9 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         if (int rcz_ = launch_zero(ws + pl->o_zero_beg, (pl->o_zero_end - pl->o_zero_beg) * sizeof(float), s)) return rcz_;
 
     // transposed images of every 2-D weight that needs a dX product
-    BwdCtx B;
-    B.s = s; B.wt = ws + pl->o_wt; B.splitk = ws + pl->o_splitk; B.discard = discard;
-    B.tn_ring = pl->o_tnring ? ws + pl->o_tnring : nullptr; B.tn_ring_floats = pl->tnring_floats;
+    BwdCtx B(s);
+    B.wt = ws + pl->o_wt; B.splitk = ws + pl->o_splitk; B.discard = discard;
+    B.tn_ring = {TnScratch::RING, pl->o_tnring ? ws + pl->o_tnring : nullptr, pl->tnring_floats};
     B.wt_off.assign(ctx->names.size(), 0);
     // run-to-run reproducible weight gradients: kernels that add into a gradient tensor from several workgroups add into its
     // fixed-point shadow while this scope is open (common.h det_shadow); the shadows reach the fp32 gradients at the end of the pass.
@@ -2906,7 +2891,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         }
     }
     if (!walk) {                // decoder only: the pass ends here (dW, db of the decoder went through the fixed-point shadows)
-        RUN(tn_x3tr_flush(s));
+        RUN(B.tn.flush());
         RUN(det_flush(ctx, s));
         if (pl->bwd_event) STAIR_HIP(hipEventRecord(static_cast<hipEvent_t>(pl->bwd_event), s));
         if (g_det.active) ctx->gshadow_dirty = false;
@@ -3228,6 +3213,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
     // HBM-bound on its saved state -- touches none of their operands.  Running them on a second stream beside it was measured
     // slower (profiles/r03_*): 19.11 ms per 2048-question step with the overlap, 18.72 ms without, 5.53 against 5.44 ms at 128
     // questions -- the two streams contend for the same LDS / L2 / HBM paths.
+    const TnRoute whole = {0, false, nullptr};     // any row count the slab kernel takes; no tail split
     for (int w = 0; w < WF_COUNT; ++w) {
         if (w == WF_FFD || pl->wg_rows[w] == 0) continue;
         const Lin &l = WIX.wf[w]->lin(W);
@@ -3243,13 +3229,14 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
             t.B = map; t.ldb = H; t.b_gstride = TH; t.b_gidx = didx + pl->wg_off_idx[w];
             if (w == WF_TD) { t.row_scale = att; t.rs_gstride = T; t.rs_gidx = didx + pl->wg_off_rs[w]; }
         }
-        if (pl->wg_part[w] && tn_x3tr_takes(t)) RUN(launch_gemm_tn_x3tr(t, ws + pl->wg_part[w], s));      // deterministic: no atomics
-        else RUN(launch_gemm_tn(t, s));
+        TnScratch part = {TnScratch::RESERVED, pl->wg_part[w] ? ws + pl->wg_part[w] : nullptr};     // deterministic: no atomics
+        RUN(B.tn.product(t, part, whole));
     }
     // the vector-level weights (and Filter's dense layer on the pooled rows): one product per weight over the rows of all its
     // buckets; from 2048 rows on through the slab kernel (whole 32-row stages; the < 32 rows left over by the atomic kernel, one
     // add per element), below that the atomic kernel's single pass is shorter
     std::vector<stair_gemm_tn_args> small_tn;
+    const TnRoute vec_route = {2048, true, &small_tn};
     for (int w = 0; w < VD_COUNT; ++w) {
         if (pl->vd_rows[w] == 0) continue;
         const Lin &l = WIX.vd[w]->lin(W);
@@ -3260,20 +3247,10 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         t.B = ws + pl->vd_x[w]; t.ldb = Kw; t.b_gstride = Kw; t.rows_per_group = 1;
         t.C = l.dw; t.ldc = Kw; t.colsum = l.db;
         t.M = (int)pl->vd_rows[w]; t.N = H; t.K = Kw;
-        stair_gemm_tn_args h = t;
-        h.M = t.M & ~31;
-        const int64_t need = h.M >= 2048 && B.tn_ring && tn_x3tr_takes(h) ? align_up(tn_x3tr_scratch_floats(h.M, H, Kw), 64) : 0;
-        if (need && need <= B.tn_ring_floats) {
-            float *piece;
-            RUN(B.ring_take(need, &piece));
-            RUN(launch_gemm_tn_x3tr(h, piece, s));
-            if (t.M == h.M) continue;
-            t.A += (int64_t)h.M * t.lda; t.B += (int64_t)h.M * t.ldb; t.M -= h.M;
-        }
-        small_tn.push_back(t);
+        RUN(B.tn.product(t, B.tn_ring, vec_route));
     }
     if (!small_tn.empty()) RUN(launch_gemm_tn_batch(small_tn.data(), (int)small_tn.size(), s));
-    RUN(tn_x3tr_flush(s));                    // dW, db += the slabs of every product above, in slab order: one launch
+    RUN(B.tn.flush());                        // dW, db += the slabs of every product above, in slab order: one launch
     // Every gradient except the two encoders' is final here (decoder, all module levels, their weight-gradient products): a
     // data-parallel trainer starts reducing that part of its bucket now, beside the BPTT below (stair_plan_set_backward_event)
     RUN(det_flush(ctx, s));                   // ... including what went through the fixed-point shadows (module levels, decoder)
@@ -3303,7 +3280,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         // the single form of the same kernel; with one, BPTT runs and only the weight products are dropped -- what is left of
         // them is clearing the gate gradients behind a short clip's end, which the input-gradient product reads)
         auto enc_products = [&](const stair_lstm_bwd_args &a, int e) -> int {
-            return enc_dw[e] ? launch_lstm_bwd_weights(a, s) : launch_lstm_bwd_clear_tail(a, s);
+            return enc_dw[e] ? launch_lstm_bwd_weights(a, B.tn) : launch_lstm_bwd_clear_tail(a, s);
         };
         int rc_pair = -1;
         if (!(enc_run[0] && enc_run[1])) {
@@ -3325,7 +3302,7 @@ static int plan_backward(stair_ctx *ctx, stair_plan *pl, const float *video, con
         }
         }
     }
-    RUN(tn_x3tr_flush(s));                   // the encoders' slab-reduced weight gradients
+    RUN(B.tn.flush());                       // the encoders' slab-reduced weight gradients
     RUN(det_flush(ctx, s));                  // the encoders' fixed-point shadows -> the fp32 gradients
     if (g_det.active) ctx->gshadow_dirty = false;    // every touched shadow has been emptied again
     g_det.active = false;

@@ -80,3 +80,57 @@ def test_step_gradients_with_every_map_level_product_on_the_slab_kernel():
         test_gpu_train.test_full_size_backward_sample('bf16x3')
     finally:
         check(lib.stair_set_tn_slab_min_rows(4096))
+
+
+def test_ring_wrap_and_shared_destinations_give_the_same_bits_twice():
+    """At the 64-row floor the products of the six-question full-size sample share the scratch ring (it wraps: the pending sums
+    must be added before a piece is reused) and several add into one weight (a destination already queued is added first).  Two
+    passes from identical inputs: every gradient tensor bit-equal; the fp64 check of the same pass is the test above."""
+    from stair_amd import spec, synth
+    from stair_amd._lib import lib, check
+    import test_gpu_train as T
+    config = dict(spec.DEFAULT_CONFIG)
+    qs = [synth.make_question(config, 21, i, form=f) for i, f in enumerate(['P0', 'P2', 'P3', 'P5', 'C0', 'C1'])]
+    check(lib.stair_set_tn_slab_min_rows(64))
+    try:
+        runs = []
+        for _ in range(2):
+            model = T._model(config, 3)
+            for p in model.parameters():
+                p.grad = torch.zeros_like(p)
+            progs, spans, video, question, q_lens, answers = T._pack(model, qs)
+            model.run_programs(progs, spans, video, question, q_lens, train=True).backward(answers, 1.0 / len(qs))
+            runs.append({n: p.grad.cpu() for n, p in model.named_parameters()})
+    finally:
+        check(lib.stair_set_tn_slab_min_rows(4096))
+    assert len(runs[0]) > 50 and any(float(g.abs().max()) > 0 for g in runs[0].values())
+    differing = [n for n in runs[0] if not torch.equal(runs[0][n], runs[1][n])]
+    assert not differing, differing
+
+
+def test_nothing_queued_by_a_stand_alone_call_survives_into_the_next():
+    """stair_gemm_tn_slabs and stair_lstm_bidir_bwd each own the queue of their slab sums and add them before they return: the
+    two calls one after the other, then both again from the same inputs, give bit-equal results."""
+    from stair_amd import ops
+    import test_gpu_lstm_shifted as S
+    M, N, K, R = 64, 256, 128, 32
+    X, idx, dZ, rs, C0, b0 = _case(M, N, K, R, 11)
+    d = lambda t: t.to(DEV)
+    dZd, Xd, idxd, rsd = d(dZ), d(X), d(idx), d(rs)
+    n, L, I = 37, 64, 64                                    # the ('uniform', 37, 64, 64) case of test_gpu_lstm_shifted.py
+    g = torch.Generator().manual_seed(1000 + n)
+    seq_off = torch.arange(n + 1, dtype=torch.int32, device=DEV) * L
+    x = torch.randn(n * L, I, generator=g).to(DEV)
+    d_out = torch.randn(n * L, 2 * S.Hh, generator=g).to(DEV)
+    d_hn = torch.randn(n, 2 * S.Hh, generator=g).to(DEV)
+    ws = S._weights(I, n)
+    out, h_n, gates0, cbuf = ops.lstm_bidir(x, seq_off, L, ws, save=True)
+    results = []
+    for _ in range(2):
+        Cm, b1 = d(C0.clone()), d(b0.clone())
+        ops.gemm_tn(dZd, Xd, Cm, M, N, K, rows_per_group=R, b_gstride=R * K, b_gidx=idxd, row_scale=rsd, rs_gstride=R, rs_gidx=idxd,
+                    colsum=b1, deterministic=True)
+        grads = ops.lstm_bidir_bwd(x, seq_off, L, ws, out, gates0.clone(), cbuf, d_out, d_hn, slabs=True)
+        results.append([Cm.cpu(), b1.cpu()] + [t.cpu() for t in grads])
+    assert not torch.equal(results[0][0], C0) and all(float(t.abs().max()) > 0 for t in results[0])
+    assert all(torch.equal(a, b) for a, b in zip(results[0], results[1]))
