@@ -9,13 +9,16 @@
 //   * X needs no register round trip at all: global -> LDS by LDS-DMA (global_load_lds_dwordx4), swizzle on the SOURCE address;
 //   * dG is split once per element into bf16 hi + lo on its way through registers (no transposes) and written row-major;
 //   * a product is dGhi * X + dGlo * X (X is exact): two v_mfma_f32_32x32x16_bf16 per pair, fp32 accumulate.
-// 256 (n) x 256 (k) output tile per workgroup, 8 waves as 4 (n) x 2 (k) of 64 x 128, reduction in stages of 32 rows through a
-// ring of 3 LDS stages (3 planes of 16 KB each: dG hi, dG lo, X), one raw s_barrier per stage, the DMA of two stages ahead
-// and the dG loads of two stages ahead in flight across it behind a counted s_waitcnt vmcnt.  M is cut into 8 slabs (one per
-// XCD, so that a slab's rows leave HBM once and are shared through that XCD's L2 by the 32 tiles); slabs add up with fp32 atomics.
+// 128 (n) x 512 (k) output tile per workgroup, 8 waves as 2 (n) x 4 (k) of 64 x 128, reduction in stages of 32 rows through a
+// ring of 3 LDS stages (48 KB each: dG hi 8 KB, dG lo 8 KB, X 32 KB), one raw s_barrier per stage, the DMA of two stages ahead
+// and the dG loads of two stages ahead in flight across it behind a counted s_waitcnt vmcnt.  The tile is wide in k because the
+// two operands do not cost the same to stage: X's DMA takes no VALU and no ds_write, dG's split and writes take both -- per
+// stage a thread splits 8 floats of dG (16 with the 256 x 256 tile this kernel had first; same MFMAs, fragment reads and LDS
+// bytes per stage, same summation order of every output element).  M is cut into 8 slabs (one per XCD, so that a slab's rows
+// leave HBM once and are shared through that XCD's L2 by the 32 tiles); slabs add up with fp32 atomics.
 //
-// LDS image of a plane of one stage: two half images (columns 0..127, 128..255) of [32 rows][256 B]; the 16-byte chunk ch of
-// row r of half h sits at chunk  ch ^ (((r & 3) << 2) | ((r >> 2) & 3)) ^ h  (cdna_hip_programming.md T10, image (b)): the
+// LDS image of a plane of one stage: half images (128 columns each: one of dG, four of X) of [32 rows][256 B]; the 16-byte chunk
+// ch of row r of half h sits at chunk  ch ^ (((r & 3) << 2) | ((r >> 2) & 3)) ^ h  (cdna_hip_programming.md T10, image (b)): the
 // transposed reads of a 32-lane half touch all 64 banks once, and so do the 16-byte staging writes of a row.
 #include <algorithm>
 #include <cstdlib>
@@ -33,8 +36,10 @@ using v4f = __attribute__((ext_vector_type(4))) float;
 
 constexpr int TR_ROWS = 32;                   // reduction rows per stage
 constexpr int TR_HALF = TR_ROWS * 256;        // one 128-column half image: 8 KB
-constexpr int TR_PLANE = 2 * TR_HALF;         // 256 columns: 16 KB
-constexpr int TR_STAGE = 3 * TR_PLANE;        // dG hi, dG lo, X: 48 KB
+constexpr int TR_TN = 128, TR_TK = 512;       // output tile
+constexpr int TR_GPLANE = TR_HALF;            // dG hi or lo, 128 columns: 8 KB
+constexpr int TR_XOFF = 2 * TR_GPLANE;        // X's plane behind them: 512 columns, four half images, 32 KB
+constexpr int TR_STAGE = TR_XOFF + 4 * TR_HALF;     // 48 KB
 constexpr int TR_NST = 3;
 
 struct TrParams {
@@ -79,43 +84,42 @@ __device__ __forceinline__ bf16x8 join8(v2u a, v2u b) {
 }  // namespace
 
 __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
-    extern __shared__ __attribute__((aligned(16))) char tl[];      // [3 stages][3 planes][2 halves][32 rows][256 B]
+    extern __shared__ __attribute__((aligned(16))) char tl[];      // [3 stages][dG hi | dG lo | X: 4 halves][32 rows][256 B]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // one slab per XCD (blocks with equal blockIdx % 8 share an XCD: speed only)
     const int slab = blockIdx.x & 7, tile = blockIdx.x >> 3;
     const int tn = tile / p.tilesK, tk = tile - tn * p.tilesK;
-    const int n0 = tn * 256, k0 = tk * 256;
+    const int n0 = tn * TR_TN, k0 = tk * TR_TK;
     const int m_beg = slab * p.mslab, m_end = min(p.M, m_beg + p.mslab);
     const int S = (m_end - m_beg) / TR_ROWS;                       // whole stages, an even number >= 2 of them (the launcher checks)
     if (S < 2) return;
 
     // ---- staging roles ----
-    // dG: thread = (row 0..31, 16 consecutive columns): 4 float4 loads, split, two 16-byte writes per plane
+    // dG: thread = (row 0..31, 8 consecutive columns = chunk g_seg of the one half image): 2 float4 loads, split, one 16-byte
+    // write per plane
     const int g_row = tid >> 4, g_seg = tid & 15;
-    const int g_h = g_seg >> 3, g_ch = 2 * (g_seg & 7);
-    const int g_src = g_row * (int)p.lda + 16 * g_seg;             // float offset inside the slab's column block (32-bit: < 2^31 checked by the launcher)
+    const int g_src = g_row * (int)p.lda + 8 * g_seg;              // float offset inside the slab's column block (32-bit: < 2^31 checked by the launcher)
     const float *g_base = p.A + (int64_t)m_beg * p.lda + n0;
-    const int g_dst0 = g_h * TR_HALF + 256 * g_row + 16 * tr_chunk(g_row, g_ch, g_h);
-    const int g_dst1 = g_h * TR_HALF + 256 * g_row + 16 * tr_chunk(g_row, g_ch + 1, g_h);
-    // X: wave w issues DMA instructions 2w, 2w+1 of the 16 that fill a stage's plane; instruction idx fills rows
-    // 4 (idx & 7) .. +3 of half idx >> 3 linearly (1 KB), lane = (row in group, physical chunk)
-    int x_dst[2], x_src[2];
+    const int g_dst = 256 * g_row + 16 * tr_chunk(g_row, g_seg, 0);
+    // X: wave w issues DMA instructions 4w .. 4w+3 of the 32 that fill a stage's plane (= half image w >> 1, rows 16 (w & 1) ..
+    // +15); instruction idx fills rows 4 (idx & 7) .. +3 of half idx >> 3 linearly (1 KB), lane = (row in group, physical chunk)
+    int x_dst[4], x_src[4];
     const __bf16 *x_base = p.B + (int64_t)m_beg * p.ldb + k0;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int idx = 2 * wave + i, h = idx >> 3, rg = idx & 7;
+    for (int i = 0; i < 4; ++i) {
+        const int idx = 4 * wave + i, h = idx >> 3, rg = idx & 7;
         const int row = 4 * rg + (lane >> 4);
         const int ch = tr_chunk(row, lane & 15, h);                // logical chunk stored at physical slot lane & 15 (the XOR is an involution)
-        x_dst[i] = __builtin_amdgcn_readfirstlane(2 * TR_PLANE + h * TR_HALF + rg * 1024);
+        x_dst[i] = __builtin_amdgcn_readfirstlane(TR_XOFF + h * TR_HALF + rg * 1024);
         x_src[i] = row * (int)p.ldb + 128 * h + 8 * ch;
     }
     // ---- fragment addresses (byte offsets inside a plane, stage-relative) ----
     // lane l of a 32x32x16 operand: column l & 31 of its 32-column tile, reduction rows 8 (l >> 5) .. +7 of the 16-row k-step.
     // transposed read: 16-lane group gi = (l >> 4) & 1 covers columns 16 gi .. +15; lane 4 q + pq of the group supplies the
     // address of row (base + q), columns 4 pq .. +3
-    const int wn = wave >> 1, wk = wave & 1;                       // wave tile: n 64 wn .. +63, k 128 wk .. +127
+    const int wn = wave >> 2, wk = wave & 3;                       // wave tile: n 64 wn .. +63, k 128 wk .. +127 (= X's half image wk)
     const int kg = lane >> 5, gi = (lane >> 4) & 1, q = (lane >> 2) & 3, pq = lane & 3;
-    auto frag_off = [&](int col, int rd) {                         // col: first column of the 32-column tile inside the 256-column tile
+    auto frag_off = [&](int col, int rd) {                         // col: first column of the 32-column tile inside the plane (dG: 0..127, half 0; X: 0..511)
         const int c = col + 16 * gi + 4 * pq;
         const int h = c >> 7, ch = (c & 127) >> 3;
         const int row = 8 * kg + 4 * rd + q;                        // + 16 per k-step: leaves (row & 3) and ((row >> 2) & 3) unchanged
@@ -143,7 +147,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
     auto issue_x = [&](int s) {                                    // stage s of this slab -> ring slot s % 3
         const unsigned st = lds0 + (s % TR_NST) * TR_STAGE;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < 4; ++i) {
             const __bf16 *src = x_base + (int64_t)s * TR_ROWS * p.ldb + x_src[i];
             const unsigned dst = st + x_dst[i];
             unsigned keep;
@@ -154,26 +158,24 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
     };
     // dG goes through ordinary loads: hipcc counts them and waits for exactly the set it is about to split.  (X's DMA is asm
     // and therefore NOT counted by hipcc: its counted waits for dG may leave fewer operations in flight than they say, never more.)
-    auto load_g = [&](int s, v4f (&g)[4]) {
+    auto load_g = [&](int s, v4f (&g)[2]) {
         const float *src = g_base + (int64_t)s * TR_ROWS * p.lda + g_src;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) g[i] = *(const __attribute__((address_space(1))) v4f *)(src + 4 * i);
+        for (int i = 0; i < 2; ++i) g[i] = *(const __attribute__((address_space(1))) v4f *)(src + 4 * i);
     };
-    auto write_g = [&](int s, const v4f (&g)[4]) {
+    auto write_g = [&](int s, const v4f (&g)[2]) {
         const unsigned st = lds0 + (s % TR_NST) * TR_STAGE;
-        bf16x8 hi[2], lo[2];
+        bf16x8 hi, lo;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const __bf16 hv = (__bf16)g[i][e];
-                hi[i >> 1][4 * (i & 1) + e] = hv;
-                lo[i >> 1][4 * (i & 1) + e] = (__bf16)(g[i][e] - (float)hv);
+                hi[4 * i + e] = hv;
+                lo[4 * i + e] = (__bf16)(g[i][e] - (float)hv);
             }
-        lds_write16<0>(st + g_dst0, __builtin_bit_cast(v4u, hi[0]));
-        lds_write16<0>(st + g_dst1, __builtin_bit_cast(v4u, hi[1]));
-        lds_write16<TR_PLANE>(st + g_dst0, __builtin_bit_cast(v4u, lo[0]));
-        lds_write16<TR_PLANE>(st + g_dst1, __builtin_bit_cast(v4u, lo[1]));
+        lds_write16<0>(st + g_dst, __builtin_bit_cast(v4u, hi));
+        lds_write16<TR_GPLANE>(st + g_dst, __builtin_bit_cast(v4u, lo));
     };
     auto compute = [&](int s) {
         const unsigned st = lds0 + (s % TR_NST) * TR_STAGE;
@@ -181,14 +183,14 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
         {                                                                                                                 \
             v2u rb[4][2], rh[2][2], rl[2][2];                                                                             \
             _Pragma("unroll") for (int t = 0; t < 4; ++t) {                                                               \
-                rb[t][0] = tr_read<2 * TR_PLANE + (KS_) * 4096>(st + offB[t][0]);                                         \
-                rb[t][1] = tr_read<2 * TR_PLANE + (KS_) * 4096>(st + offB[t][1]);                                         \
+                rb[t][0] = tr_read<TR_XOFF + (KS_) * 4096>(st + offB[t][0]);                                         \
+                rb[t][1] = tr_read<TR_XOFF + (KS_) * 4096>(st + offB[t][1]);                                         \
             }                                                                                                             \
             _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                               \
                 rh[i][0] = tr_read<(KS_) * 4096>(st + offA[i][0]);                                                        \
                 rh[i][1] = tr_read<(KS_) * 4096>(st + offA[i][1]);                                                        \
-                rl[i][0] = tr_read<TR_PLANE + (KS_) * 4096>(st + offA[i][0]);                                             \
-                rl[i][1] = tr_read<TR_PLANE + (KS_) * 4096>(st + offA[i][1]);                                             \
+                rl[i][0] = tr_read<TR_GPLANE + (KS_) * 4096>(st + offA[i][0]);                                             \
+                rl[i][1] = tr_read<TR_GPLANE + (KS_) * 4096>(st + offA[i][1]);                                             \
             }                                                                                                             \
             /* the fragments are in flight: nothing may touch them before this wait (the operands tie every later use to it) */ \
             asm volatile("s_waitcnt lgkmcnt(0)"                                                                           \
@@ -212,8 +214,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
     };
 
     // ---- prologue: stage 0 complete in LDS, stage 1's loads in flight ----
-    // Vector-memory operations per stage, in issue order: dG (4 loads), then X's DMA (2 instructions).
-    v4f ga[4], gb[4];
+    // Vector-memory operations per stage, in issue order: dG (2 loads), then X's DMA (4 instructions).
+    v4f ga[2], gb[2];
     load_g(0, ga);
     issue_x(0);
     load_g(1, gb);
@@ -224,10 +226,14 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
     // issue stage s + 2 (its ring slot was last read in stage s - 1); multiply stage s; split dG(s + 1) and write it (its slot
     // was last read in stage s - 2).  The steady-state loop is branch-free -- on a path that skips a wait hipcc has to assume
     // the loads still pending and drains everything (vmcnt(0)) at the next use -- and the last two stages are peeled.
-    auto stage = [&](int s, v4f (&g_next)[4], v4f (&g_next2)[4]) {
+    auto stage = [&](int s, v4f (&g_next)[2], v4f (&g_next2)[2]) {
         // g_next holds dG(s+1) (in flight or landed); g_next2 is free and receives dG(s+2)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's ds_writes of dG(s) are done
-        // X(s) has landed once at most the 6 operations issued after its DMA -- dG(s+1) and X(s+1) -- are outstanding
+        // Issue order up to here: ... dG(s) [2], X(s) [4], dG(s+1) [2], X(s+1) [4] (stage s + 2 is issued below the barrier).
+        // Vector-memory operations retire in order, so X(s) has landed once at most the 2 + 4 = 6 operations issued after its
+        // DMA -- dG(s+1) and X(s+1) -- are outstanding.  (The 256 x 256 tile issued 4 + 2 per stage: the count is the same,
+        // the split of it is not.)  hipcc's own wait in front of the split of dG(s+1) counts the 2 loads of dG(s+2) behind it
+        // and knows nothing of the DMA: it retires X(s+1), dG(s+2) and the first half of X(s+2), all issued a multiply phase earlier.
         asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -276,8 +282,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_tr_kernel(TrParams p) {
 bool tn_tr_takes(const stair_gemm_tn_args &a) {
     if (!a.b_is_bf16 || a.row_scale || a.b_gidx || a.colsum || a.colsum2) return false;
     if (a.rows_per_group != 1 && a.b_gstride != (int64_t)a.rows_per_group * a.ldb) return false;
-    if (a.N % 256 || a.K % 256 || a.M % (8 * 64) || a.M < 2048) return false;     // >= 4 stages per slab; measured down to M = 2048 (32 questions)
-    if (32 * a.lda + 256 >= (1ll << 31) || 32 * a.ldb + 256 >= (1ll << 31)) return false;
+    if (a.N % TR_TN || a.K % TR_TK || a.M % (8 * 64) || a.M < 2048) return false;     // >= 4 stages per slab; measured down to M = 2048 (32 questions)
+    if (32 * a.lda + TR_TN >= (1ll << 31) || 32 * a.ldb + TR_TK >= (1ll << 31)) return false;
     if (a.lda % 4 || a.ldb % 8 || (reinterpret_cast<uintptr_t>(a.A) & 15) || (reinterpret_cast<uintptr_t>(a.B) & 15)) return false;
     return matmul_mode() == STAIR_MATMUL_BF16X3;
 }
@@ -289,7 +295,7 @@ static int launch_tr(const stair_gemm_tn_args &a, float *P, hipStream_t s) {
     p.M = a.M; p.N = a.N; p.K = a.K;
     p.P = P;
     p.C64 = p.P ? nullptr : det_shadow(a.C);
-    p.tilesN = a.N / 256; p.tilesK = a.K / 256;
+    p.tilesN = a.N / TR_TN; p.tilesK = a.K / TR_TK;
     p.mslab = a.M / 8;                                             // a multiple of 64: whole stages, an even number of them
     const size_t shmem = (size_t)TR_NST * TR_STAGE;
     static bool attr_set = false;

@@ -222,7 +222,10 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_x3tr_kernel(XtParams p) {
     // (Tried: the two waves of a SIMD running a stage's two phases in opposite order -- 5 % slower; s_setprio(1) around the MFMA
     // clusters -- 3-5 % slower; __builtin_amdgcn_iglp_opt(0) in the multiply phase -- within noise, (1) -- 6 % slower
     // (tools/scratch/build_variant.sh, one box each).  Parts compiled out at
-    // M = 109 056: loads + split + writes alone 0.52 of the full time, loads + multiplies alone 0.76: the phases add up.)
+    // M = 109 056: loads + split + writes alone 0.52 of the full time, loads + multiplies alone 0.76: the phases add up.
+    // Tried as well: a 256 x 256 tile with 64 x 128 per wave, gemm_tn_tr.hip's geometry, for a third fewer splits per MFMA -- with BOTH
+    // operands staged through registers it needs well over the 256 registers a wave has here, spills 428-812 bytes per lane into
+    // the loop and runs three times slower with the same bits: DESIGN.md, "Weight-gradient kernels: tile geometry".)
     for (; s + 4 <= S; s += 2) {                                     // steady state: both halves have a stage to load, no branches
         __syncthreads();
         load(g0);                                                    // stage s + 2
