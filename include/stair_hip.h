@@ -948,6 +948,25 @@ int stair_adam_step_scaled(float *params, const float *grads, float *exp_avg, fl
 int stair_grad_norm(const float *grads, int64_t n, const int32_t *seg_first_block, const int64_t *seg_numel, int32_t n_seg,
                     float max_norm, float *block_scratch, float *seg_norm, float *out, uint32_t *guard, stair_stream stream);
 
+/* Device-resident inputs (additive to ABI 7; csrc/gather.hip): the dense tensors a pass reads, gathered on the stream from a clip
+ * library and a word table that were uploaded once, so that a step sends row numbers instead of rows.  One launch each; 16-byte
+ * loads and stores, plain stores, every output element written exactly once (the caller clears nothing); no atomics, LDS or scratch.
+ *   stair_gather_clips   clip v of dst [n, T, V] (dense, the element type of src: elem_bytes 2 = bf16, 4 = fp32) receives the first
+ *                        lens[v] frames of src + rows[v] * clip_stride_elems and exact zeros from frame lens[v] up to T; a library
+ *                        clip holds rows_cap frames of V elements and nothing behind a clip's frames is read.  rows and lens are
+ *                        DEVICE int32 [n]; lens == NULL: every clip has min(rows_cap, T) frames.  A lens[v] outside 0 ..
+ *                        min(rows_cap, T) is clamped to it.  rows may repeat and come in any order; the library cannot check their
+ *                        upper end: the caller checks its host copy (1 <= lens[v] <= min(rows_cap, T), rows[v] inside the
+ *                        library) before the upload.  Checked here: V * elem_bytes % 16 == 0, clip_stride_elems >= rows_cap * V
+ *                        and a multiple of 16 bytes, src and dst 16-byte aligned.
+ *   stair_gather_words   dst[i, :] = table[ids[i], :], fp32 rows of E floats (E % 4 == 0), ids DEVICE int32 [n]; several rows share
+ *                        a workgroup.  The caller checks its host copy of ids against n_table_rows before the upload; an id outside
+ *                        0 .. n_table_rows - 1 reads nothing and its row is stored as NaN. */
+int stair_gather_clips(const void *src, int32_t elem_bytes, int64_t clip_stride_elems, int32_t rows_cap, int32_t V,
+                       const int32_t *rows, const int32_t *lens, int32_t n, int32_t T, void *dst, stair_stream stream);
+int stair_gather_words(const float *table, int32_t E, int32_t n_table_rows, const int32_t *ids, int32_t n, float *dst,
+                       stair_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

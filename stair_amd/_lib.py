@@ -251,6 +251,9 @@ SIGNATURES = [
     ('stair_plan_set_encoded_video_grad', C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     ('stair_plan_run_flags', C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p]),
+    ('stair_gather_clips', C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_void_p]),
+    ('stair_gather_words', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 ]
 
 

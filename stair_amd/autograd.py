@@ -54,7 +54,7 @@ class PlanLogits(torch.autograd.Function):
             model._ws, model._proj = shared
         ctx.model, ctx.res = model, res
         ctx.video_dtype = video.dtype if video is not None else None
-        ctx.encoded = src.video is None
+        ctx.encoded = src.enc is not None        # (a ClipLibrary pass has neither tensor here: its clips are gathered inside the pass)
         return res.logits
 
     @staticmethod

@@ -223,6 +223,88 @@ def load_answer_vocab(path):
     return v
 
 
+def _unknown_word_vector(word, dim):
+    """The vector of a word GloVe does not hold, under the default per-word seed: uniform [0, 1) noise like the reference's
+    np.random.rand (dataset.py:253), seeded by the word so that runs -- and a WordTable -- repeat it."""
+    seed = int.from_bytes(word.encode()[:8].ljust(8, b'\0'), 'little') & 0x7fffffff
+    return np.random.default_rng(seed).random(dim)
+
+
+class WordTable:
+    """The question vocabulary's word vectors on the device, one fp32 row per distinct lower-cased word: a question then travels
+    as row numbers (4 bytes per word) and one launch (stair_gather_words) makes the rows the text encoder reads.
+    `table[ids(sent)]` equals `AGQAQuestions.embed_sent(sent)` bit for bit under its default per-word seed for unknown words;
+    the per-occurrence noise of a caller-supplied `rng` has no table form (AGQAQuestions refuses the combination)."""
+
+    def __init__(self, words, table, tokenize=None):
+        self.words = list(words)
+        self.row = {w: i for i, w in enumerate(self.words)}
+        if len(self.row) != len(self.words) or tuple(table.shape[:1]) != (len(self.words),) or table.dim() != 2:
+            raise ValueError('a word table needs one [E] row per distinct word')
+        if table.dtype != torch.float32 or not table.is_contiguous() or table.shape[1] % 4:
+            raise ValueError('the table must be contiguous float32 [n_words, E] with E % 4 == 0')
+        self.table, self.device, self.dim = table, table.device, int(table.shape[1])
+        self.tokenize = tokenize or frontend.Normaliser().tokenize
+
+    @classmethod
+    def from_glove(cls, glove, words, device, tokenize=None):
+        """glove: {word: vector} (load_glove).  words: strings -- single words or whole sentences (the records' questions); each is
+        lower-cased and tokenized as embed_sent does, every distinct word gets a row in order of first appearance.  A word GloVe
+        does not hold gets embed_sent's default vector for it."""
+        tok = tokenize or frontend.Normaliser().tokenize
+        dim = int(next(iter(glove.values())).size)
+        seen, rows = {}, []
+        for s in words:
+            for w in tok(s.lower()):
+                if w not in seen:
+                    seen[w] = len(rows)
+                    v = glove.get(w)
+                    rows.append(_unknown_word_vector(w, dim) if v is None else v)
+        if not rows:
+            raise ValueError('from_glove needs at least one word')
+        table = torch.tensor(np.asarray(rows), dtype=torch.float32)           # (the conversion embed_sent applies to its rows)
+        return cls(list(seen), table.to(device).contiguous(), tokenize=tok)
+
+    def __len__(self):
+        return len(self.words)
+
+    def __contains__(self, word):
+        return word in self.row
+
+    def ids(self, sent):
+        """int32 array of table rows for a sentence (a string, tokenized as embed_sent does, or a list of words); a word the
+        table does not hold raises KeyError naming it."""
+        words = self.tokenize(sent.lower()) if isinstance(sent, str) else [s.lower() for s in sent]
+        out = np.empty(len(words), dtype=np.int32)
+        for i, w in enumerate(words):
+            if w not in self.row:
+                raise KeyError('word %r is not in the word table' % (w,))
+            out[i] = self.row[w]
+        return out
+
+    def check_ids(self, ids, n=None):
+        """The host copy of a batch's ids as a contiguous int32 array, ValueError when one lies outside the table (or, with n, when
+        there are not n of them): what the device cannot check without a synchronise is checked here, before the upload."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
+        if ids.ndim != 1 or (n is not None and ids.shape[0] != n):
+            raise ValueError('question_ids must be int32 [sum(q_lens)]%s' % ('' if n is None else ' = [%d]' % n))
+        if ids.size and (ids.min() < 0 or ids.max() >= len(self.words)):
+            raise ValueError('question_ids must hold rows of the word table (0 .. %d)' % (len(self.words) - 1))
+        return ids
+
+    def gather(self, ids):
+        """[n, E] fp32 rows of the DEVICE int32 array ids on the current stream (stair_gather_words)."""
+        import ctypes as C
+        from ._lib import check, lib
+        n = int(ids.shape[0])
+        out = torch.empty(n, self.dim, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return out
+        check(lib.stair_gather_words(C.c_void_p(self.table.data_ptr()), self.dim, len(self.words), C.c_void_p(ids.data_ptr()), n,
+                                     C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out
+
+
 def rescale_interval(interval, src_length, tgt_length):
     """dataset.py:258-261 frame_interval_change_fps."""
     return (interval[0] / src_length * tgt_length, interval[1] / src_length * tgt_length)
@@ -241,13 +323,19 @@ class AGQAQuestions:
     answer_vocab   {word2id, id2word}
     video_secs     {video_id: seconds} -- needed only for train/valid items with gold intervals
     tokenize       callable str -> [str]; default is the regex tokenizer of frontend.Normaliser (nltk is absent)
+    word_table     a WordTable over the questions' words: every item also carries 'question_ids' (int32 table rows of its
+                   words; 'question' stays).  Not together with `rng`: per-occurrence noise has no table form (ValueError)
     """
 
-    def __init__(self, records, clips, glove, answer_vocab, split='test', video_secs=None, tokenize=None, rng=None):
+    def __init__(self, records, clips, glove, answer_vocab, split='test', video_secs=None, tokenize=None, rng=None, word_table=None):
+        if rng is not None and word_table is not None:
+            raise ValueError('rng= together with word_table=: with a caller-supplied rng every OCCURRENCE of an unknown word draws its '
+                             'own vector, which a table of one row per word cannot hold; leave rng=None (the per-word seed)')
         self.records, self.clips, self.glove, self.answer_vocab = records, clips, glove, answer_vocab
         self.split, self.video_secs = split, video_secs or {}
         self.tokenize = tokenize or frontend.Normaliser().tokenize
         self.rng = rng
+        self.word_table = word_table
         self.dim = int(next(iter(glove.values())).size)
 
     def __len__(self):
@@ -262,8 +350,7 @@ class AGQAQuestions:
                 if self.rng is not None:
                     v = self.rng.random(self.dim)
                 else:
-                    seed = int.from_bytes(w.encode()[:8].ljust(8, b'\0'), 'little') & 0x7fffffff
-                    v = np.random.default_rng(seed).random(self.dim)
+                    v = _unknown_word_vector(w, self.dim)
             rows.append(v)
         return torch.tensor(np.asarray(rows), dtype=torch.float32)
 
@@ -280,6 +367,8 @@ class AGQAQuestions:
                 'prog_str_to_question_tokens': r['nmn_program_span_by_word'],
                 'nmn_program_list': r['nmn_program'], 'nmn_program_idx': r['nmn_program_idx'],
                 'qa_id': r['qa_id'], 'question_raw': r['question'], 'video_id': r['video_id']}
+        if self.word_table is not None:
+            item['question_ids'] = self.word_table.ids(self.tokenize(r['question'].lower()))
         if self.split == 'test':
             return item
         T = clip.size(0)
@@ -309,31 +398,53 @@ class AGQAQuestions:
 # items -> executor tensors
 # ----------------------------------------------------------------------------------------------
 class PackedBatch:
-    __slots__ = ('programs', 'spans', 'video', 'video_index', 'question', 'q_lens', 'answers', 'n_clips', 'h2d_bytes', 'video_len')
+    __slots__ = ('programs', 'spans', 'video', 'video_index', 'question', 'q_lens', 'answers', 'n_clips', 'h2d_bytes', 'video_len',
+                 'library', 'words', 'question_ids')
 
 
-def pack_questions(items, device, share_clips=True, pin=True):
+def pack_questions(items, device, share_clips=True, pin=True, clip_library=None, word_table=None):
     """Question dicts -> the arguments of VideoNMN.run_programs.  Clips are staged once each (items of one clip carry
     the same feature tensor); clips of different frame counts are padded to the longest and their lengths kept in
     `video_len` (None when all agree); every tensor goes through one pinned host buffer and one asynchronous H2D copy on
-    the current stream."""
+    the current stream.
+
+    clip_library (a ClipLibrary that holds every item's 'video_id'): no clip is staged or copied -- `video` and `video_len` are
+    None, `video_index` holds the LIBRARY ROW of every question's clip (int32 numpy, a host array: the pass uploads the rows it
+    uses), `library` the library, and `h2d_bytes` counts no clip bytes.
+    word_table (a WordTable; the items carry 'question_ids', AGQAQuestions(word_table=...)): `question` is None, `question_ids`
+    (int32 numpy [sum(q_lens)]) and `words` (the table) take its place, and `h2d_bytes` counts 4 bytes per word.
+    Hand the batch on as run_programs(b.programs, b.spans, b.video, b.question, b.q_lens, video_index=b.video_index,
+    video_len=b.video_len, library=b.library, question_ids=b.question_ids, words=b.words)."""
     from .evaluate import clip_key
     n = len(items)
-    keys, order, index = {}, [], []
-    for d in items:
-        k = clip_key(d) if share_clips else len(order)
-        if k not in keys:
-            keys[k] = len(order)
-            order.append(d['video_features'])
-        index.append(keys[k])
-    frames = [int(c.shape[0]) for c in order]
-    Tm = max(frames)
-    order = [torch.as_tensor(c) for c in order]
-    # clips stored as bf16 (load_clip_features(..., dtype='bf16')) stay bf16: half the H2D bytes and the plane-GEMM input path
-    vdtype = torch.bfloat16 if all(c.dtype == torch.bfloat16 for c in order) else torch.float32
-    video = torch.stack([torch.nn.functional.pad(c.to(vdtype), (0, 0, 0, Tm - int(c.shape[0]))) for c in order])
-    qs = [torch.as_tensor(d['question'], dtype=torch.float32) for d in items]
-    question = torch.cat(qs)
+    video = frames = None
+    if clip_library is not None:
+        index = clip_library.rows([d['video_id'] for d in items])
+        n_clips = len(set(index.tolist()))
+    else:
+        keys, order, index = {}, [], []
+        for d in items:
+            k = clip_key(d) if share_clips else len(order)
+            if k not in keys:
+                keys[k] = len(order)
+                order.append(d['video_features'])
+            index.append(keys[k])
+        frames = [int(c.shape[0]) for c in order]
+        Tm = max(frames)
+        order = [torch.as_tensor(c) for c in order]
+        # clips stored as bf16 (load_clip_features(..., dtype='bf16')) stay bf16: half the H2D bytes and the plane-GEMM input path
+        vdtype = torch.bfloat16 if all(c.dtype == torch.bfloat16 for c in order) else torch.float32
+        video = torch.stack([torch.nn.functional.pad(c.to(vdtype), (0, 0, 0, Tm - int(c.shape[0]))) for c in order])
+        n_clips = len(order)
+    question = question_ids = None
+    if word_table is not None:
+        ids = [np.asarray(d['question_ids'], dtype=np.int32) for d in items]
+        q_lens = [int(q.shape[0]) for q in ids]
+        question_ids = word_table.check_ids(np.concatenate(ids))
+    else:
+        qs = [torch.as_tensor(d['question'], dtype=torch.float32) for d in items]
+        q_lens = [int(q.shape[0]) for q in qs]
+        question = torch.cat(qs)
     answers = torch.tensor([int(d['answer']) for d in items], dtype=torch.int32) if 'answer' in items[0] else None
     cuda = torch.device(device).type == 'cuda'
 
@@ -347,12 +458,15 @@ def pack_questions(items, device, share_clips=True, pin=True):
     b = PackedBatch()
     b.programs = [d['nmn_program_list'] for d in items]
     b.spans = [d['prog_str_to_question_tokens'] for d in items]
-    b.h2d_bytes = video.numel() * video.element_size() + question.numel() * 4 + (answers.numel() * 4 if answers is not None else 0)
+    b.h2d_bytes = ((video.numel() * video.element_size() if video is not None else 0) +
+                   (question.numel() * 4 if question is not None else question_ids.size * 4) +
+                   (answers.numel() * 4 if answers is not None else 0))
     b.video, b.question, b.answers = up(video), up(question), up(answers)
-    b.video_index = index if len(order) < n else None
-    b.q_lens = [int(q.shape[0]) for q in qs]
-    b.n_clips = len(order)
-    b.video_len = frames if len(set(frames)) > 1 else None
+    b.video_index = index if clip_library is not None or n_clips < n else None
+    b.q_lens = q_lens
+    b.n_clips = n_clips
+    b.video_len = frames if frames is not None and len(set(frames)) > 1 else None
+    b.library, b.words, b.question_ids = clip_library, word_table, question_ids
     return b
 
 

@@ -66,10 +66,12 @@ def group_by_frames(batch, ragged=True):
     return groups
 
 
-def predict(model, questions, batch_size=1024, clip_cache=None):
+def predict(model, questions, batch_size=1024, clip_cache=None, clip_library=None):
     """Top-1 answer ids (python ints) for a list of question dicts, in order.
     clip_cache (here and in the drivers below): a ClipCache of model.encode_clips -- the clips are looked up by the questions'
-    'video_id' instead of being encoded again in every launch batch (VideoNMN.forward_batch)."""
+    'video_id' instead of being encoded again in every launch batch (VideoNMN.forward_batch).
+    clip_library (here and in the drivers below): a ClipLibrary -- the clips' raw features are looked up by 'video_id' on the device
+    and encoded there; nothing of them is packed or copied on the host."""
     preds = [None] * len(questions)
     for T, idxs in sorted(group_by_frames(questions, ragged=model.config['max_video_length'] > 32).items()):
         # questions of one clip next to each other, so a launch batch encodes each of its clips once
@@ -79,7 +81,7 @@ def predict(model, questions, batch_size=1024, clip_cache=None):
         idxs = sorted(idxs, key=lambda i: (first[clip_key(questions[i])], i))
         for s in range(0, len(idxs), batch_size):
             chunk = idxs[s:s + batch_size]
-            res = model.forward_batch([questions[i] for i in chunk], clip_cache=clip_cache)
+            res = model.forward_batch([questions[i] for i in chunk], clip_cache=clip_cache, clip_library=clip_library)
             for i, p in zip(chunk, res.pred.cpu().tolist()):
                 preds[i] = int(p)
     return preds
@@ -93,7 +95,7 @@ def accuracy(preds, golds, unk_token_id):
 
 
 def evaluate(model, questions, unk_token_id, rank=0, world=1, batch_size=1024, predict_fn=None, preds_file=None,
-             id2word=None, shard='round_robin', clip_cache=None):
+             id2word=None, shard='round_robin', clip_cache=None, clip_library=None):
     """Sharded accuracy evaluation.  Every rank passes the SAME full question list; returns
     (accuracy, preds) on every rank.  `predict_fn(questions) -> list[int]` defaults to the HIP path
     (tests substitute a CPU function to exercise the sharding logic without a GPU).
@@ -101,7 +103,7 @@ def evaluate(model, questions, unk_token_id, rank=0, world=1, batch_size=1024, p
     if shard not in ('round_robin', 'clip'):
         raise ValueError("shard must be 'round_robin' or 'clip'")
     mine = shard_indices(len(questions), rank, world) if shard == 'round_robin' else shard_by_clip(questions, rank, world)
-    fn = predict_fn or (lambda qs: predict(model, qs, batch_size, clip_cache=clip_cache))
+    fn = predict_fn or (lambda qs: predict(model, qs, batch_size, clip_cache=clip_cache, clip_library=clip_library))
     local = fn([questions[i] for i in mine])
     if world > 1:
         import torch.distributed as dist
@@ -122,7 +124,7 @@ def evaluate(model, questions, unk_token_id, rank=0, world=1, batch_size=1024, p
     return acc, preds
 
 
-def filter_text_results(model, questions, filter_vocab, phrase_embeddings, batch_size=1024, top=10, clip_cache=None):
+def filter_text_results(model, questions, filter_vocab, phrase_embeddings, batch_size=1024, top=10, clip_cache=None, clip_library=None):
     """Batched counterpart of /root/reference/evaluate.py:65-117 (get_filter_text_results): for every `Filter`
     node of every question, the `top` phrases of `filter_vocab` whose text-encoder representation is most similar
     (cosine) to the node's output.  phrase_embeddings[i] = word embeddings [L_i, E] of filter_vocab[i] (the reference
@@ -140,7 +142,7 @@ def filter_text_results(model, questions, filter_vocab, phrase_embeddings, batch
     for T, idxs in sorted(group_by_frames(questions, ragged=model.config['max_video_length'] > 32).items()):
         for s in range(0, len(idxs), batch_size):
             chunk = [questions[i] for i in idxs[s:s + batch_size]]
-            res = model.forward_batch(chunk, clip_cache=clip_cache)
+            res = model.forward_batch(chunk, clip_cache=clip_cache, clip_library=clip_library)
             where, slots = [], []
             for qi, d in enumerate(chunk):
                 prog = d['nmn_program_list']
@@ -165,7 +167,7 @@ def filter_text_results(model, questions, filter_vocab, phrase_embeddings, batch
 
 
 def evaluate_by_module(model, questions, unk_token_id, batch_size=1024, module_loss_weight=1.0, preds_file=None, id2word=None,
-                       clip_cache=None):
+                       clip_cache=None, clip_library=None):
     """Batched counterpart of /root/reference/train_module.py:219-270 (`evaluate_by_module`, the validation pass of the
     training loop): returns (accuracy, {module: mean validation loss}).  Supervised nodes are those of
     `model.pretrain_modules` whose program_idx has a gold value in the question's `sg_res_by_step`; contrastive modules
@@ -179,7 +181,7 @@ def evaluate_by_module(model, questions, unk_token_id, batch_size=1024, module_l
         for s in range(0, len(idxs), batch_size):
             chunk_idx = idxs[s:s + batch_size]
             chunk = [questions[i] for i in chunk_idx]
-            res = model.forward_batch(chunk, clip_cache=clip_cache)
+            res = model.forward_batch(chunk, clip_cache=clip_cache, clip_library=clip_library)
             if module_loss_weight != 0:
                 for m, vals in L.evaluate_module_losses(model, res, chunk, modules & L.CRITERION_MODULES).items():
                     losses[m].extend(vals)

@@ -44,6 +44,11 @@ class ClipSource(NamedTuple):
     index: Optional[np.ndarray]         # int32 [n]: the plan clip of every question; None: question q asks about clip q
     lens: Optional[np.ndarray]          # int32 [n_videos]: frames of every plan clip; None: all of them have T
     T: int
+    # clips named by ClipLibrary row (run_programs(library=...)): the library and the row of every plan clip.  Until the pass has
+    # gathered them `video` is None; from then on it is the dense [n_videos, T, V] staging tensor and the source reads like one
+    # made of clip features (VideoNMN._gathered)
+    library: Any = None
+    library_rows: Optional[np.ndarray] = None
 
     def video_arg(self):
         """(the clip features' address or NULL, RUN_VIDEO_BF16 or 0): the video arguments of every run and reverse-pass call."""
@@ -104,6 +109,29 @@ def _init_param(name, p, config):
             wshape = table[name[:-5] + '.weight'] if name.endswith('.bias') else tuple(p.shape)
             b = 1.0 / math.sqrt(int(np.prod(wshape[1:])))
             p.uniform_(-b, b)                                      # nn.Linear / nn.Conv1d default
+
+
+class _IndexRing:
+    """Host int32 arrays -> the device through a ring of page-locked buffers, without a synchronise: the host waits only for the
+    copy issued `depth` uploads ago (the reasoning of train._PinnedRing; the buffers here grow with the arrays)."""
+
+    def __init__(self, depth=8):
+        self.bufs, self.events, self.i = [None] * depth, [None] * depth, 0
+
+    def upload(self, values, device):
+        k = self.i
+        self.i = (k + 1) % len(self.bufs)
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        n = int(values.shape[0])
+        if self.bufs[k] is None or self.bufs[k].numel() < n:
+            self.bufs[k] = torch.empty(max(n * 3 // 2, 256), dtype=torch.int32).pin_memory()
+        host = self.bufs[k][:n]
+        host.copy_(torch.from_numpy(values))
+        t = host.to(device, non_blocking=True)
+        self.events[k] = torch.cuda.Event()
+        self.events[k].record()
+        return t
 
 
 def _clip_key(x):
@@ -402,6 +430,7 @@ class VideoNMN(nn.Module):
         self._trainable = [True] * len(self._weight_names)      # what the context holds (stair_ctx_set_trainable; its default is 1)
         self._ws = None
         self._proj = None
+        self._index_ring = None             # page-locked staging of the row numbers of library / word-table passes (made on first use)
         # run_programs: enqueue the encoders' input projections before the plan is built (False: inside the plan's pass)
         self.early_projection = True
         self._programs = frontend.ProgramCache()
@@ -498,9 +527,12 @@ class VideoNMN(nn.Module):
             raise ValueError('dropout is a training-mode operation (train=True)' +
                              ('; this pass on cached clips is inference' if encoded else ''))
 
-    def _clip_source(self, n, video, video_index, video_len, clips=None, encoded=None, train=False, dropout=None):
+    def _clip_source(self, n, video, video_index, video_len, clips=None, encoded=None, train=False, dropout=None, library=None):
         """The ClipSource of a pass over n questions, one public form each: clips= (a ClipCache), encoded= (caller-made encodings),
-        else video.  Checks everything that can be refused before a plan exists; enqueues nothing."""
+        library= (a ClipLibrary of raw clip features), else video.  Checks everything that can be refused before a plan exists;
+        enqueues nothing."""
+        if library is not None:
+            return self._source_of_library(n, library, video, video_index, video_len, clips, encoded, train, dropout)
         if clips is not None:
             return self._source_of_cache(n, clips, video, video_index, video_len, train, dropout)
         if encoded is not None:
@@ -563,6 +595,63 @@ class VideoNMN(nn.Module):
             raise ValueError('video_len must hold the frames (1 .. %d) of each of the %d encoded clips' % (cap, n_clips))
         return self._source_of_rows(encoded, None, video_index, lengths, n, 'encoded')
 
+    def _source_of_library(self, n, library, video, video_index, video_len, clips, encoded, train, dropout):
+        """Clips named by ClipLibrary row: the plan's clips are the distinct rows in order of first use, as for a cache; the pass
+        gathers them into a dense tensor (VideoNMN._gathered) and is from there on the pass of _source_of_video on that tensor."""
+        if video is not None or clips is not None or encoded is not None:
+            raise ValueError('library= given together with video=, clips= or encoded=: a pass on a clip library takes video=None and '
+                             'names its clips by library row in video_index')
+        if video_len is not None:
+            raise ValueError('video_len= given together with library=: the library holds its clips\' lengths')
+        if video_index is None:
+            raise ValueError('video_index is required with library=: the library row of every question\'s clip')
+        dev, V = next(self.parameters()).device, self.config['video_size']
+        if library.device != dev or library.video_size != V:
+            raise ValueError('library= belongs to another device or video_size: it holds %d features per frame on %s, the model reads '
+                             '%d on %s' % (library.video_size, library.device, V, dev))
+        if library.dtype == torch.bfloat16 and V % 32:
+            raise ValueError('library= holds bf16 clip features, which need video_size % 32 == 0')
+        used, index, lens, T = self._clips_of_rows(video_index, library.lengths, n, 'the library')
+        if T > self.config['max_video_length'] or int(lens.max()) > self.config['max_video_length']:
+            raise ValueError('library= holds a clip of %d frames among those asked for, max_video_length is %d'
+                             % (int(lens.max()), self.config['max_video_length']))
+        self._check_mode(False, train, dropout)
+        return ClipSource(None, None, None, None, len(used), index, lens if bool((lens != T).any()) else None, T, library, used)
+
+    def _gathered(self, src):
+        """The source of a library pass once its clips are on their way: rows and lengths go up through a ring of page-locked buffers
+        (no synchronise, no read-back) and one launch (stair_gather_clips) writes the dense [n_videos, T, V] tensor the encoder
+        reads; the BatchResult keeps it (the reverse pass reads the clips again for dW_ih, an autograd call until backward())."""
+        if src.library is None or src.video is not None:
+            return src
+        if self._index_ring is None:
+            self._index_ring = _IndexRing()
+        nv = src.n_videos
+        host = src.library_rows if src.lens is None else np.concatenate([src.library_rows, src.lens])
+        dev_idx = self._index_ring.upload(host, src.library.device)
+        return src._replace(video=src.library.gather(dev_idx[:nv], dev_idx[nv:] if src.lens is not None else None, src.T))
+
+    def _question_rows(self, question, question_ids, words, q_lens):
+        """The question rows of a pass: `question` itself, or with question_ids= (host int32 [sum(q_lens)], rows of the WordTable
+        `words`) the rows one launch gathers from the table (stair_gather_words).  Refusals come first; then the ids are uploaded
+        and the gather enqueued."""
+        if question_ids is None:
+            if words is not None:
+                raise ValueError('words= given without question_ids=: the table is read through the ids')
+            return question
+        if question is not None:
+            raise ValueError('question_ids= given together with question=: a pass on a word table takes question=None')
+        if words is None:
+            raise ValueError('question_ids= needs words=: the WordTable the ids are rows of')
+        dev, E = next(self.parameters()).device, self.config['text_size']
+        if words.device != dev or words.dim != E:
+            raise ValueError('words= belongs to another device or text_size: it holds %d floats per word on %s, the model reads %d on %s'
+                             % (words.dim, words.device, E, dev))
+        ids = words.check_ids(question_ids, int(sum(q_lens)))
+        if self._index_ring is None:
+            self._index_ring = _IndexRing()
+        return words.gather(self._index_ring.upload(ids, dev))
+
     def _source_of_rows(self, enc, cache, video_index, lengths, n, what):
         used, index, lens, T = self._clips_of_rows(video_index, lengths, n, what)
         return ClipSource(None, enc, cache, used, len(used), index, lens if bool((lens != T).any()) else None, T)
@@ -588,7 +677,7 @@ class VideoNMN(nn.Module):
         return used, index, lens, T
 
     def run_programs(self, programs, spans, video, question, q_lens, train=False, video_index=None, dropout=None, video_len=None,
-                     before_run=None, cse=True, clips=None):
+                     before_run=None, cse=True, clips=None, library=None, question_ids=None, words=None):
         """Batched pass.  programs: list of token lists; spans: list of {pos: (lo, hi)}; video
         [n,T,V] and question [sum(q_lens), E] float32 on the GPU.  Returns a BatchResult.
 
@@ -618,8 +707,19 @@ class VideoNMN(nn.Module):
         all eight tensors of the video encoder are frozen (requires_grad = False) and raises ValueError otherwise: the training
         plan keeps none of the encoder's saves, the reverse pass is the frozen-encoder pass, the encoder's tensors report
         untouched and the cache stays fresh.  dropout with train=False raises ValueError, and so does a cache whose encoder
-        weights or matmul mode are no longer the model's (ClipCache.check)."""
-        src = self._clip_source(len(programs), video, video_index, video_len, clips, None, train, dropout)
+        weights or matmul mode are no longer the model's (ClipCache.check).
+        library (optional, a ClipLibrary: raw clip features kept on the device): video is None, video_index [n] (required) names
+        the LIBRARY ROW of every question's clip, in any order and with repeats; every distinct row becomes one clip of the plan, in
+        order of first use.  One launch (stair_gather_clips) writes the plan's clips, with their own lengths, into a dense tensor
+        that the BatchResult keeps; from there the pass -- and, with train=True, the reverse pass of a TRAINABLE video encoder --
+        is the one on `video`, the same launches on the same bytes.  The step uploads the rows and lengths only.  ValueError before
+        anything is enqueued: library= with video=, clips=, encoded= or video_len=; a library on another device or of another
+        video_size; bf16 features with video_size % 32 != 0; a clip longer than max_video_length.
+        question_ids (optional, int32 [sum(q_lens)] on the HOST) with words (a data.WordTable) and question=None: the question rows
+        are gathered on the device from the table's rows (stair_gather_words), bit for bit the rows embed_sent makes.  ValueError:
+        question_ids= with question=, or without words=; an id outside the table."""
+        src = self._clip_source(len(programs), video, video_index, video_len, clips, None, train, dropout, library)
+        question = self._question_rows(question, question_ids, words, q_lens)
         return self._run(src, programs, spans, question, q_lens, train, dropout, before_run, cse)
 
     def _run(self, src, programs, spans, question, q_lens, train, dropout, before_run, cse):
@@ -634,6 +734,7 @@ class VideoNMN(nn.Module):
         drop_on = dropout is not None and dropout[0] > 0
         stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+        src = self._gathered(src)               # a library pass: its clips' gather goes first, the rest is the pass on clip features
         video, bf16 = src.video_arg()
         # The encoders' input projections need the inputs only: enqueue them BEFORE packing the programs and building the plan (3-4 ms
         # of host work at 2048 questions), so the device is busy meanwhile (stair_encoders_project; results bit-identical).
@@ -716,21 +817,37 @@ class VideoNMN(nn.Module):
             raise StairError('a cooperative LSTM hand-off timed out while encoding clips (its workgroups were not co-resident: another '
                              'queue on this GPU?); the encodings of this chunk hold NaN.  STAIR_LSTM_COOP=0 selects the one-workgroup kernels')
 
-    def encode_clips(self, clips, ids=None, video_len=None, batch_size=1024):
+    def encode_clips(self, clips=None, ids=None, video_len=None, batch_size=1024, library=None):
         """Run the video encoder once over a library of clips and keep the result: a ClipCache (stair_amd/clip_cache.py) for
         run_programs(clips=...), forward_batch(clip_cache=...) and the evaluate drivers.  clips: a list of [L_i, V] tensors, or
         a padded [N, T, V] tensor with video_len; fp32, or bf16 (the stored clip-feature format).  ids: one hashable per clip
         (forward_batch looks clips up by the questions' 'video_id'); default: the row numbers.  The encodings are those a plan's
         own encoder pass computes (stair_encode_clips: the same kernels, in this model's matmul mode), [N, max_video_length, H]
-        fp32 with zeros behind each clip's frames.  cache.add(...) appends more clips later."""
+        fp32 with zeros behind each clip's frames.  cache.add(...) appends more clips later.
+        library (a ClipLibrary, with clips=None): the clips are the library's, read where they lie on the device -- no clip bytes
+        cross from the host.  ids: the library ids to encode, in that order (default: all, in row order); they are the cache's ids."""
         from .clip_cache import ClipCache
         dev = next(self.parameters()).device
+        if library is not None:
+            if clips is not None or video_len is not None:
+                raise ValueError('library= given together with clips= or video_len=: the library holds the clips and their lengths')
+            if library.device != dev or library.video_size != self.config['video_size']:
+                raise ValueError('library= belongs to another device or video_size')
+            if ids is None:
+                ids, clips, video_len = library.ids, library.clips, library.lengths
+            else:
+                ids = list(ids)
+                rows = library.rows(ids)
+                video_len = library.lengths[rows]
+                clips = library.gather(torch.from_numpy(rows).to(dev), torch.from_numpy(video_len).to(dev), int(video_len.max()))
+        elif clips is None:
+            raise ValueError('encode_clips needs clips= or library=')
         cache = ClipCache(self.config['max_video_length'], self.config['hidden_size'], self._encode_chunk, self._clip_stamp, dev)
         cache.add(clips, ids=ids, video_len=video_len, batch_size=batch_size)
         return cache
 
     def logits(self, programs, spans, video, question, q_lens, video_index=None, video_len=None, dropout=None, cse=True, clips=None,
-               encoded=None):
+               encoded=None, library=None, question_ids=None, words=None):
         """[n, A] logits of a batch (arguments as for run_programs) with a torch autograd graph: when grad mode is on and any
         parameter, `video` or `question` requires grad, the result has a grad_fn whose backward runs the native reverse pass
         seeded by the logits gradient (stair_amd.autograd.PlanLogits) -- parameter gradients, and input gradients for `video`
@@ -742,14 +859,23 @@ class VideoNMN(nn.Module):
         encoded=enc, a float32 [n_clips, T, H] tensor on the GPU (the output of a clip encoder of the caller's own, in torch),
         video_index [n] (optional when n_clips == n) = the clip of every question, video_len [n_clips] (optional) = the clips'
         frames.  When enc requires grad it receives a gradient of its own shape: a clip's gradient is summed over the questions
-        that share it, zero behind its video_len and zero for clips that no question reads."""
+        that share it, zero behind its video_len and zero for clips that no question reads.
+
+        library=lib (a ClipLibrary, video=None, video_index = the library row of every question's clip) and question_ids= / words=
+        are those of run_programs.  The video encoder may be trainable: its parameters receive their gradients as on `video`.  A
+        library is data: no gradient goes to it, and a call that asks for the video's gradient has to hand the clips in as video=
+        (a `video` tensor beside library= is refused like any other).  The gathered question rows receive no gradient either."""
         params = [dict(self.named_parameters())[n] for n in self._weight_names]
-        if (clips is not None or encoded is not None) and (video is not None or (clips is not None and encoded is not None)):
+        if library is None and (clips is not None or encoded is not None) and (video is not None or (clips is not None and encoded is not None)):
             raise ValueError('video given together with clips= / encoded=: a pass on encoded clips takes video=None and one of the two')
+        if library is not None and isinstance(video, torch.Tensor) and video.requires_grad:
+            raise ValueError('library= given together with a video= that requires grad: a library is data and receives no gradient; '
+                             'the gradient of the video needs the clips handed in as video= alone')
         tensor = video if video is not None else encoded        # what of the source autograd may differentiate (a ClipCache: nothing)
-        grad = torch.is_grad_enabled() and (question.requires_grad or any(p.requires_grad for p in params) or
+        grad = torch.is_grad_enabled() and ((question is not None and question.requires_grad) or any(p.requires_grad for p in params) or
                                             (isinstance(tensor, torch.Tensor) and tensor.requires_grad))
-        src = self._clip_source(len(programs), video, video_index, video_len, clips, encoded, grad, dropout if grad else None)
+        src = self._clip_source(len(programs), video, video_index, video_len, clips, encoded, grad, dropout if grad else None, library)
+        question = self._question_rows(question, question_ids, words, q_lens)
         if not grad:
             with torch.no_grad():
                 return self._run(src if tensor is None else src.with_tensor(tensor.detach()), programs, spans, question, q_lens,
@@ -757,7 +883,7 @@ class VideoNMN(nn.Module):
         from .autograd import PlanLogits
         return PlanLogits.apply(self, (programs, spans, q_lens, dropout, cse, src), tensor, question, *params)
 
-    def forward_batch(self, batch, train=False, share_videos=True, dropout=None, cse=True, clip_cache=None):
+    def forward_batch(self, batch, train=False, share_videos=True, dropout=None, cse=True, clip_cache=None, clip_library=None):
         """batch: list of question dicts in the reference layout (dataset.py:191-233).  Clips may differ in their
         number of frames (they are padded to the longest of the batch and run with their own lengths, see run_programs);
         Linear-Temporal configurations (max_video_length <= 32) need every clip at max_video_length, like the reference.
@@ -769,18 +895,22 @@ class VideoNMN(nn.Module):
 
         clip_cache (a ClipCache of encode_clips): the clips are looked up by d['video_id'] and not encoded again (their
         'video_features' are not read); an id the cache does not hold raises KeyError naming it.  With train=True the video
-        encoder must be frozen (see run_programs, `clips`)."""
+        encoder must be frozen (see run_programs, `clips`).
+        clip_library (a ClipLibrary): the clips are looked up by d['video_id'] in the library and gathered on the device (their
+        'video_features' are not read, nothing of them is copied from the host); a missing id raises KeyError naming it."""
         dev = next(self.parameters()).device
         video = video_len = None
-        if clip_cache is not None:
-            index = clip_cache.rows([d['video_id'] for d in batch])
+        if clip_cache is not None and clip_library is not None:
+            raise ValueError('clip_cache= given together with clip_library=: one source of clips per pass')
+        if clip_cache is not None or clip_library is not None:
+            index = (clip_cache if clip_cache is not None else clip_library).rows([d['video_id'] for d in batch])
         else:
             video, index, video_len = self._pack_clips(batch, share_videos, dev)
         qs = [torch.as_tensor(d['question']) for d in batch]
         question = torch.cat(qs).to(dev, torch.float32).contiguous()
         return self.run_programs([d['nmn_program_list'] for d in batch], [d['prog_str_to_question_tokens'] for d in batch], video, question,
                                  [q.shape[0] for q in qs], train=train, video_index=index, dropout=dropout, video_len=video_len, cse=cse,
-                                 clips=clip_cache)
+                                 clips=clip_cache, library=clip_library)
 
     @staticmethod
     def _pack_clips(batch, share_videos, dev):

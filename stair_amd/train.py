@@ -262,7 +262,7 @@ class Trainer:
         return end if self.iters > total else start + (end - start) / total * self.iters
 
     def step(self, programs, spans, video, question, q_lens, answers, global_batch=None, questions=None, video_index=None,
-             video_len=None, clips=None):
+             video_len=None, clips=None, library=None, question_ids=None, words=None):
         """One optimizer step over this rank's shard of a window.  `questions` -- the dicts, with 'sg_res_by_step', or their
         losses.GoldBatch (losses.collate_gold: the data loader's collate step; the per-question bookkeeping then costs the stepping
         process nothing) -- switches the per-module intermediate losses on (train_module.py:351-373, 388-406).
@@ -272,11 +272,17 @@ class Trainer:
         video encoder must be frozen (Trainer(freeze=('video_encoder',)) / requires_grad = False on its eight tensors), else
         ValueError before anything is enqueued; its tensors report untouched and keep weights, moments, step counts and torch
         version, so the cache is still fresh after the step.
+        library (a ClipLibrary, with video=None and video_index = the library row of every question's clip): the raw clip features
+        stay on the device and one launch gathers the step's clips (VideoNMN.run_programs); the video encoder trains as on `video`,
+        and the step is that step bit for bit.  question_ids (host int32 [sum(q_lens)]) with words (a data.WordTable) and
+        question=None: the question rows are gathered from the table.  Either way the step's host-to-device traffic is row numbers.
+        At world > 1 every rank holds the whole library and table; the exchange is unchanged.
         Returns (per-question decoder CE of the local shard, BatchResult)."""
         from . import losses as L
         n = len(programs)
         # the checks of the clips, once per step; what they refuse is refused here: nothing of the step has been enqueued or counted yet
-        src = self.model._clip_source(n, video, video_index, video_len, clips, train=True)
+        src = self.model._clip_source(n, video, video_index, video_len, clips, train=True, library=library)
+        question = self.model._question_rows(question, question_ids, words, q_lens)
         if global_batch is None:
             global_batch = self.global_batch
         if global_batch is None and self.world > 1:           # ragged shards: the window is the SUM of the shard sizes
