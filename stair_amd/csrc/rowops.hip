@@ -544,6 +544,12 @@ int launch_superlative_pool(const float *S, const float *rowbase, const int32_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// (a, ai) comes before (b, bi) in torch.argmax's order: a NaN is the largest value, equal values (two NaN among them) keep the lower
+// index.  A lane without an element holds (-inf, 0x7fffffff), which loses to every element of the row, a -inf included.
+__device__ __forceinline__ bool argmax_before(float a, int ai, float b, int bi) {
+    if (a != a) return b == b || ai < bi;
+    return b == b && (a > b || (a == b && ai < bi));
+}
 __global__ void argmax_kernel(const float *logits, int32_t *out, int n, int A) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
@@ -552,11 +558,11 @@ __global__ void argmax_kernel(const float *logits, int32_t *out, int n, int A) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int c = lane; c < A; c += 64)
-        if (x[c] > best) { best = x[c]; bi = c; }     // first maximum, like torch.argmax
+        if (argmax_before(x[c], c, best, bi)) { best = x[c]; bi = c; }     // first maximum, like torch.argmax
     for (int o = 32; o > 0; o >>= 1) {
         const float ob = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        if (argmax_before(ob, oi, best, bi)) { best = ob; bi = oi; }
     }
     if (lane == 0) out[i] = bi;
 }

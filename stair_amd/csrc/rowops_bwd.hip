@@ -225,8 +225,10 @@ int launch_span_mean_bwd_rows(float *dtok, int64_t ld, int rows, const int32_t *
 
 // ---------------------------------------------------------------------------------------------
 // cosine attention backward.  out = (cos+1)*0.49, cos = f.k / (nf * nk), nf = max(|f|,eps), nk likewise.
-//   dF[fi][t][:] += dcos * (k/(nf nk) - cos f/nf^2)        (atomic: pairs of one Localize share the tile)
-//   dK[p][:]     += sum_t dcos_t * (f_t/(nf_t nk) - cos_t k/nk^2)
+//   dF[fi][t][:] += dcos * (k/(nf nk) - [|f| >= eps] cos f/nf^2)        (atomic: pairs of one Localize share the tile)
+//   dK[p][:]     += sum_t dcos_t * (f_t/(nf_t nk) - [|k| >= eps] cos_t k/nk^2)
+// [.]: a norm under the clamp is a constant to autograd (clamp_min passes no gradient below eps), so the second term of that side,
+// which is the derivative of the norm, is absent there.
 // One block per pair: phase 1 computes per-frame scalars into LDS, phase 2 is column-parallel.
 __global__ void cosine_attn_bwd_kernel(const float *F, int64_t f_gs, const int32_t *f_idx, const float *Kmat,
                                        const int32_t *k_idx, const float *datt, const int32_t *out_idx, float *dF,
@@ -243,17 +245,19 @@ __global__ void cosine_attn_bwd_kernel(const float *F, int64_t f_gs, const int32
     float nk2 = 0.f;
     for (int c = lane; c < H; c += 64) nk2 += k[c] * k[c];
     nk2 = wave_sum(nk2);
-    const float nk = fmaxf(sqrtf(nk2), 1e-8f);
-    if (threadIdx.x == 0) s_nk2 = nk * nk;
+    // A clamped norm is a constant (torch's clamp_min passes no gradient below eps): the cos * x / n^2 term of that side is absent.
+    // For k: s_nk2 = inf, whose reciprocal below is 0; for f_t: sb[t] = 0.
+    const float rk = sqrtf(nk2), nk = fmaxf(rk, 1e-8f);
+    if (threadIdx.x == 0) s_nk2 = rk < 1e-8f ? INFINITY : nk * nk;
     for (int t = wave; t < T; t += kWavesPerBlock) {
         const float *ft = f + (int64_t)t * H;
         float d = 0.f, nf2 = 0.f;
         for (int c = lane; c < H; c += 64) { d += ft[c] * k[c]; nf2 += ft[c] * ft[c]; }
         d = wave_sum(d); nf2 = wave_sum(nf2);
-        const float nf = fmaxf(sqrtf(nf2), 1e-8f);
+        const float rf = sqrtf(nf2), nf = fmaxf(rf, 1e-8f);
         const float cosv = d / (nf * nk);
         const float dcos = 0.49f * g[t];
-        if (lane == 0) { sa[t] = dcos / (nf * nk); sb[t] = dcos * cosv / (nf * nf); sc[t] = dcos * cosv; }
+        if (lane == 0) { sa[t] = dcos / (nf * nk); sb[t] = rf < 1e-8f ? 0.f : dcos * cosv / (nf * nf); sc[t] = dcos * cosv; }
     }
     __syncthreads();
     const float inv_nk2 = 1.0f / s_nk2;
@@ -283,7 +287,9 @@ int launch_cosine_attn_bwd(const float *F, int64_t f_gs, const int32_t *f_idx, c
 // per instance, no atomics.  The forward scores are saved (out = (cos+1)*0.49), so cos is recovered from them and
 // only the row norms are recomputed:
 //   dF[t][:] = sum_a sa[a][t] k_a  -  (sum_a sb[a][t]) f_t ;   dK[a][:] = sum_t sa[a][t] f_t  -  (sum_t sc[a][t]) k_a / nk_a^2
-// with sa = dcos/(nf nk), sb = dcos*cos/nf^2, sc = dcos*cos, dcos = 0.49 * dscore.  (The per-pair kernel above
+// with sa = dcos/(nf nk), sb = dcos*cos/nf^2, sc = dcos*cos, dcos = 0.49 * dscore; sb = 0 where |f_t| < eps and sc = 0 where
+// |k_a| < eps, as in the per-pair kernel.  That kernel sees the raw norm and tests `raw < eps`; this one reads the CLAMPED norms
+// rownorm_kernel wrote and tests `clamped > eps`, which is the same set but for a norm of exactly eps.  (The per-pair kernel above
 // issues Ka*T*H atomic adds per instance -- half a billion for a batch of Superlatives with Ka = T = 64.)
 __global__ void rownorm_kernel(const float *X, int64_t rows, int H, float *out) {
     const int lane = threadIdx.x & 63;
@@ -370,12 +376,12 @@ __global__ __launch_bounds__(256) void cosine_attn_bwd_grouped_kernel(const floa
         for (int t = threadIdx.x; t < T; t += blockDim.x) {
             float acc = 0.f;
             for (int a = 0; a < Ka; ++a) acc += su[a * TS + t];
-            sbsum[t] = acc / (nf[t] * nf[t]);
+            sbsum[t] = nf[t] > 1e-8f ? acc / (nf[t] * nf[t]) : 0.f;      // a clamped norm is a constant: no cos * f / nf^2 term
         }
         for (int a = threadIdx.x; a < Ka; a += blockDim.x) {
             float acc = 0.f;
             for (int t = 0; t < T; ++t) acc += su[a * TS + t];
-            scsum[a] = acc;
+            scsum[a] = nk[a] > 1e-8f ? acc : 0.f;                         // likewise no cos * k / nk^2 term
         }
         __syncthreads();
     }
