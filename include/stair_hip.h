@@ -967,6 +967,54 @@ int stair_gather_clips(const void *src, int32_t elem_bytes, int64_t clip_stride_
 int stair_gather_words(const float *table, int32_t E, int32_t n_table_rows, const int32_t *ids, int32_t n, float *dst,
                        stair_stream stream);
 
+/* Audit decoders (additive to ABI 7; csrc/audit.hip): the supervised intermediate results of a finished pass turned into what a
+ * person reads -- a frame interval, a yes/no, a ranked class list -- and scored against gold where there is gold.  They read the
+ * arenas of a plan's workspace and write arrays of their own; nothing of the plan changes.  Common rules: one launch each on
+ * `stream`, one wave per item, plain stores, no atomics, no memset, no LDS beyond 4 KB, no scratch; EVERY output slot is written
+ * by every launch; n == 0 returns 0 without a launch; the scalar arguments are checked first, then (n > 0) the pointers, all
+ * before anything is enqueued.  slot[] lives on the device where the launcher cannot see it: a slot outside its arena
+ * (0 .. att_rows / vec_rows - 1) is never read and decodes as an unreadable item (below).
+ *
+ * stair_audit_attention   rows slot[i] .. slot[i] + K[i] - 1 of the att arena [att_rows, T] (Localize: K rows; Temporal's
+ *   related_attn row, ExistsFrame: K = 1).  Outputs are per ROW: row iv_off[i] + k of item i (iv_off [n + 1], iv_off[i + 1] -
+ *   iv_off[i] == K[i]; the caller sizes the outputs to iv_off[n] rows).  len[i] (NULL: T; clamped to 0 .. T) = frames L of the
+ *   item's clip; nothing at or beyond frame L is read.  For the row's values a[0 .. L):
+ *     peak       index of the largest value, the FIRST index among equal values; a NaN frame is never the peak; no comparable
+ *                frame (L == 0, all NaN, unreadable row): peak = -1, [start, end) = [0, 0), peak_value = NaN
+ *     on-frame   a[t] >= threshold as an fp32 comparison (the value equal to the threshold is on; NaN is off)
+ *     start,end  the maximal run of on-frames that holds the peak, [start, end); peak frame off: the empty [peak, peak)
+ *     on         number of on-frames of the whole row;   peak_value = a[peak]
+ *     iou        sum_t m_t g_t / sum_t max(m_t, g_t) over t < L with m the 0/1 mask of [start, end) and g the soft mask
+ *                span_to_attention draws for L frames from intervals[2 * (iv_off[i] + k)] = (start, end), double, as
+ *                stair_loss_attention_len reads them (the same device code); 0 when the denominator is 0; -1 without gold:
+ *                intervals == NULL (no item has gold) or has_gold[i] == 0 (has_gold == NULL: every item has gold).
+ *   The caller refuses gold ends the criterion refuses (end < -L) before the call.
+ * stair_audit_head   pretrain head W [nout, H], b [nout] on vec[slot[i]] (vec arena [vec_rows, H]).
+ *     nout == 2 (Exists, Xor): score = z1 - z0, pred = score > 0 (a tie goes to class 0, as torch.argmax)
+ *     nout == 1 (Equals):      score = z,       pred = score >= 0.5
+ *   pred is the decision of the returned fp32 score, bit for bit.  label[i] < 0 (or label == NULL): no gold, correct = -1; else
+ *   correct = (pred == (label[i] != 0)).  Unreadable item: score = NaN, pred = 0.
+ * stair_audit_rank   vec[slot[i]] against the class table reps [n_cls, H] (n_cls <= 1024; vec and reps 16-byte aligned):
+ *   similarities exactly as stair_cosine_topk forms them (dot / (max(|q|, 1e-8) max(|k|, 1e-8)), the same sums in the same order),
+ *   the k best classes in top / top_sim [n, k], best first, equal similarities lower class first (1 <= k <= n_cls);
+ *     best_gold_sim = max similarity over the item's gold classes gold_cls[gold_off[i] .. gold_off[i + 1])
+ *     rank          = 1 + #{c : sim_c > best_gold_sim}   (strict: a table row identical to the gold row does not worsen it)
+ *   an item without gold (empty range, or gold_off == NULL: no item has gold): rank = 0, best_gold_sim = -inf.  gold_off
+ *   [n + 1] and gold_cls [n_gold] are device arrays; gold_cls_host (optional) is the caller's HOST copy of gold_cls, checked here
+ *   against 0 .. n_cls - 1 before the launch (the kernel itself skips a class outside the table).  Unreadable item: top = -1,
+ *   top_sim = NaN, rank = 0.  The class norms are formed once per workgroup in LDS: no workspace, no second launch. */
+int stair_audit_attention(const float *att, int32_t att_rows, const int32_t *slot, const int32_t *K, const int32_t *len,
+                          const int32_t *iv_off, const double *intervals, const int32_t *has_gold, int32_t n, int32_t T,
+                          float threshold, int32_t *start, int32_t *end, int32_t *peak, int32_t *on, float *peak_value,
+                          float *iou, stair_stream stream);
+int stair_audit_head(int32_t nout, const float *vec, int32_t vec_rows, const int32_t *slot, const int32_t *label,
+                     const float *W, const float *b, int32_t n, int32_t H, int32_t *pred, float *score, int32_t *correct,
+                     stair_stream stream);
+int stair_audit_rank(const float *vec, int32_t vec_rows, const int32_t *slot, const float *reps, int32_t n_cls, int32_t H,
+                     const int32_t *gold_off, const int32_t *gold_cls, const int32_t *gold_cls_host, int32_t n_gold,
+                     int32_t n, int32_t k, int32_t *top, float *top_sim, int32_t *rank, float *best_gold_sim,
+                     stair_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,10 @@ SIGNATURES = [
     ('stair_gather_clips', C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     ('stair_gather_words', C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ('stair_audit_attention', C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 7),
+    ('stair_audit_head', C.c_int, [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    ('stair_audit_rank', C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
 ]
 
 

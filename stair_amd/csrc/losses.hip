@@ -3,6 +3,7 @@
 // (so that stair_plan_backward continues from them).  One wave or one small block per loss item; items are
 // few (a handful per question) and rows short, so these kernels are launch/latency bound by nature.
 #include "ops.h"
+#include "span_gold.h"
 
 namespace stair {
 // stair_loss_groups: the NEXT stair_loss_* launch of this thread evaluates its items group by group (items that add into the same
@@ -26,22 +27,7 @@ __device__ __forceinline__ void arena_add(float *p, float v, bool owned) {
     else unsafeAtomicAdd(p, v);
 }
 
-// span_to_attention, train_module.py:67-81, evaluated per frame t (double arithmetic like the reference)
-__device__ __forceinline__ float span_gold(double g0, double g1, int L, int t) {
-    const double start = fmin((double)L - 0.002, fmax(0.001, g0));
-    const double end = fmin((double)L - 0.001, g1);
-    const int si = (int)ceil(start), ei = (int)floor(end);
-    double v = 0.0;
-    if (si < ei && t >= si && t < ei) v += 1.0;
-    if (si <= ei) {
-        if (t == si - 1) v += (double)si - start;
-        if (t == ei) v += end - (double)ei;
-    } else if (t == (ei < 0 ? ei + L : ei)) {      // gold_tensor[end_int]: a negative end counts from the clip's end as in Python
-        v += end - start;                             // (only here can ei be < 0: si >= 1; the host refuses ei < -L)
-    }
-    return (float)v;
-}
-}  // namespace
+}  // namespace      (span_gold, the interval mask of span_to_attention: csrc/span_gold.h)
 
 // attention_score_criterion (:83-90) for Localize [K,T] (:173-182), Temporal / ExistsFrame [T] (:157-164,184-191)
 // `len` (optional): frames of item i's clip; the attention rows keep the stride T, criterion and gold mask see L frames

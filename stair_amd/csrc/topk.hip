@@ -7,22 +7,16 @@
 // in all lanes, and lane c % 64 keeps it.  Selection is k rounds of a wave-wide arg-max (ties: lower index), so
 // the kernel is bound by C wave reductions per query, not by memory: n*C*H*4 bytes of L2 reads, n*k*8 bytes written.
 #include "common.h"
+#include "cosine_rank.h"
 #include "ops.h"
 
 namespace stair {
 
-namespace {
-constexpr int TK_MAXJ = 4;       // H <= 1024: float4 groups per lane
-constexpr int TK_SLOTS = 16;     // C <= 1024: candidates per lane
-}  // namespace
-
 __global__ __launch_bounds__(256) void key_invnorm_kernel(const float *keys, float *inv, int C, int H) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= C) return;
-    float s = 0.0f;
-    for (int h = lane; h < H; h += 64) { const float v = keys[(int64_t)c * H + h]; s += v * v; }
-    s = wave_sum(s);
-    if (lane == 0) inv[c] = 1.0f / fmaxf(sqrtf(s), 1e-8f);        // nn.CosineSimilarity eps, per operand
+    const float v = key_invnorm(keys, c, H, lane);
+    if (lane == 0) inv[c] = v;
 }
 
 __global__ __launch_bounds__(256) void cosine_topk_kernel(const float *queries, int64_t ldq, const int32_t *q_idx,
@@ -31,62 +25,9 @@ __global__ __launch_bounds__(256) void cosine_topk_kernel(const float *queries, 
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= n) return;
     const float *qp = queries + (int64_t)(q_idx ? q_idx[q] : q) * ldq;
-    const int nj = H >> 8;                     // full float4 groups per lane (H % 256 == 0 fast path)
-    const bool vec = (H & 255) == 0 && nj <= TK_MAXJ;
-    float4 qv[TK_MAXJ];
-    float qn = 0.0f;
-    if (vec) {
-#pragma unroll
-        for (int j = 0; j < TK_MAXJ; ++j)
-            if (j < nj) {
-                qv[j] = *reinterpret_cast<const float4 *>(qp + j * 256 + lane * 4);
-                qn += qv[j].x * qv[j].x + qv[j].y * qv[j].y + qv[j].z * qv[j].z + qv[j].w * qv[j].w;
-            }
-    } else {
-        for (int h = lane; h < H; h += 64) qn += qp[h] * qp[h];
-    }
-    const float qinv = 1.0f / fmaxf(sqrtf(wave_sum(qn)), 1e-8f);
-
     float sims[TK_SLOTS];
-#pragma unroll
-    for (int t = 0; t < TK_SLOTS; ++t) sims[t] = -INFINITY;
-    for (int c = 0; c < C; ++c) {
-        const float *kp = keys + (int64_t)c * H;
-        float d = 0.0f;
-        if (vec) {
-#pragma unroll
-            for (int j = 0; j < TK_MAXJ; ++j)
-                if (j < nj) {
-                    const float4 kv = *reinterpret_cast<const float4 *>(kp + j * 256 + lane * 4);
-                    d += qv[j].x * kv.x + qv[j].y * kv.y + qv[j].z * kv.z + qv[j].w * kv.w;
-                }
-        } else {
-            for (int h = lane; h < H; h += 64) d += qp[h] * kp[h];
-        }
-        d = wave_sum(d) * qinv * kinv[c];
-        const int slot = c >> 6;
-#pragma unroll
-        for (int t = 0; t < TK_SLOTS; ++t)
-            if (t == slot && (c & 63) == lane) sims[t] = d;
-    }
-    for (int r = 0; r < k; ++r) {
-        float best = -INFINITY;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int t = 0; t < TK_SLOTS; ++t) {
-            const int c = t * 64 + lane;
-            if (c < C && (sims[t] > best || (sims[t] == best && c < bi))) { best = sims[t]; bi = c; }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
-        if (lane == 0) { out_idx[(int64_t)q * k + r] = bi; out_sim[(int64_t)q * k + r] = best; }
-#pragma unroll
-        for (int t = 0; t < TK_SLOTS; ++t)
-            if (t * 64 + lane == bi) sims[t] = -INFINITY;
-    }
+    cosine_sims(qp, keys, kinv, C, H, lane, sims);       // csrc/cosine_rank.h
+    cosine_select(sims, C, k, lane, out_idx + (int64_t)q * k, out_sim + (int64_t)q * k);
 }
 
 }  // namespace stair

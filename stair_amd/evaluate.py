@@ -166,6 +166,43 @@ def filter_text_results(model, questions, filter_vocab, phrase_embeddings, batch
     return out
 
 
+def audit(model, questions, unk_token_id, class_table=None, batch_size=1024, threshold=0.5, top=5, records=False, clip_cache=None,
+          clip_library=None):
+    """Audit pass over a question list (stair_amd.audit): every supervised intermediate node decoded on the device -- the frame
+    interval of Localize / Temporal / ExistsFrame, the yes / no of Exists / Xor / Equals, the `top` nearest classes of Filter /
+    ToAction / Superlative in `class_table` (a losses.ClassTable) -- and scored against `sg_res_by_step` where a question has it.
+    Batched exactly as evaluate_by_module.  Returns (accuracy, report) or, with records=True, (accuracy, report, records):
+      report[module]  attention modules: n, n_scored, mean_iou, recall@0.3, recall@0.5, recall@0.7 (share of scored rows with
+                      iou >= the bound); head modules: n, n_scored, accuracy; contrastive modules: n, n_scored, hit@1, hit@top
+                      (rank <= top), mrr -- float64 on the host from the per-node arrays; NaN where no node was scored
+      report['skipped']  only without class_table: {contrastive module: nodes left out}
+      records         {qa_id: {program_idx: {...}}} as AuditBatch.records renders them (qa_id: q['qa_id'], else the question's index)"""
+    from . import audit as A
+    values, kinds, skipped, recs = {}, {}, {}, {}
+    preds = [None] * len(questions)
+    for T, idxs in sorted(group_by_frames(questions, ragged=model.config['max_video_length'] > 32).items()):
+        for s in range(0, len(idxs), batch_size):
+            chunk_idx = idxs[s:s + batch_size]
+            chunk = [questions[i] for i in chunk_idx]
+            res = model.forward_batch(chunk, clip_cache=clip_cache, clip_library=clip_library)
+            batch = A.audit_batch(model, res, chunk, class_table=class_table, threshold=threshold, top=top)
+            for i, p in zip(chunk_idx, res.pred.cpu().tolist()):
+                preds[i] = int(p)
+            for module, (kind, vals) in A.module_values(batch).items():
+                kinds[module] = kind
+                values.setdefault(module, []).append(vals)
+            for module, n in batch.skipped.items():
+                skipped[module] = skipped.get(module, 0) + n
+            if records:
+                recs.update(batch.records(chunk, class_table, ids=chunk_idx))
+    import numpy as np
+    report = {module: A.module_report(kinds[module], np.concatenate(parts), top=top) for module, parts in sorted(values.items())}
+    if skipped:
+        report['skipped'] = skipped
+    acc = accuracy(preds, [int(q['answer']) for q in questions], unk_token_id)
+    return (acc, report, recs) if records else (acc, report)
+
+
 def evaluate_by_module(model, questions, unk_token_id, batch_size=1024, module_loss_weight=1.0, preds_file=None, id2word=None,
                        clip_cache=None, clip_library=None):
     """Batched counterpart of /root/reference/train_module.py:219-270 (`evaluate_by_module`, the validation pass of the

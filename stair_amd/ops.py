@@ -305,6 +305,104 @@ def cosine_topk(queries, keys, k, q_idx=None, n=None):
     return idx, sim
 
 
+def _audit_out(out, specs, device):
+    """The output tensors of an audit launcher: the caller's (checked) or fresh ones.  specs: [(name, shape, dtype)]."""
+    if out is None:
+        return [torch.empty(shape, device=device, dtype=dt) for _, shape, dt in specs]
+    if len(out) != len(specs):
+        raise ValueError('out: %d tensors (%s)' % (len(specs), ', '.join(s[0] for s in specs)))
+    for t, (name, shape, dt) in zip(out, specs):
+        _req(t, name, dt)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError('%s must have shape %s' % (name, tuple(shape)))
+    return list(out)
+
+
+def audit_attention(att, slot, K, iv_off, n_rows, threshold=0.5, lens=None, intervals=None, has_gold=None, out=None):
+    """stair_audit_attention: decode rows slot[i] .. slot[i] + K[i] - 1 of att [rows, T] into (start, end, peak, on int32
+    [n_rows], peak_value, iou float32 [n_rows]); output row iv_off[i] + k belongs to row k of item i, n_rows = iv_off[n]
+    (a host int: iv_off lives on the device).  lens int32 [n] (None: T frames), intervals float64 [n_rows, 2] gold (None: no
+    gold, iou = -1), has_gold int32 [n] (None: every item has gold).  out: the six tensors to write into."""
+    _req(att, 'att')
+    if att.dim() != 2:
+        raise ValueError('att must be [rows, T]')
+    n = slot.shape[0]
+    for t, name in ((slot, 'slot'), (K, 'K'), (lens, 'lens'), (has_gold, 'has_gold')):
+        if t is not None:
+            _req(t, name, torch.int32)
+            if t.shape[0] != n:
+                raise ValueError('%s must have one entry per item' % name)
+    _req(iv_off, 'iv_off', torch.int32)
+    if iv_off.shape[0] != n + 1:
+        raise ValueError('iv_off must have n + 1 entries')
+    if intervals is not None:
+        _req(intervals, 'intervals', torch.float64)
+        if intervals.numel() != 2 * n_rows:
+            raise ValueError('intervals must be [n_rows, 2]')
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError('the threshold is NaN')
+    i32, f32 = torch.int32, torch.float32
+    res = _audit_out(out, [(nm, (n_rows,), dt) for nm, dt in (('start', i32), ('end', i32), ('peak', i32), ('on', i32),
+                                                              ('peak_value', f32), ('iou', f32))], att.device)
+    check(lib.stair_audit_attention(_ptr(att), att.shape[0], _ptr(slot), _ptr(K), _ptr(lens), _ptr(iv_off), _ptr(intervals),
+                                    _ptr(has_gold), n, att.shape[1], C.c_float(threshold), *[_ptr(t) for t in res], _stream()))
+    return tuple(res)
+
+
+def audit_head(vec, slot, weight, bias, label=None, out=None):
+    """stair_audit_head: the pretrain head weight [nout, H], bias [nout] on vec[slot[i]] -> (pred int32, score float32, correct
+    int32) [n]; nout 2: score = z1 - z0, pred = score > 0; nout 1: pred = score >= 0.5; label int32 [n], < 0 = no gold
+    (correct = -1)."""
+    _req(vec, 'vec'); _req(weight, 'weight'); _req(bias, 'bias'); _req(slot, 'slot', torch.int32)
+    if vec.dim() != 2 or weight.dim() != 2 or weight.shape[1] != vec.shape[1] or bias.numel() != weight.shape[0]:
+        raise ValueError('vec [rows, H], weight [nout, H], bias [nout]')
+    if weight.shape[0] not in (1, 2):
+        raise ValueError('head width must be 1 (Equals) or 2 (Exists/Xor)')
+    n = slot.shape[0]
+    if label is not None:
+        _req(label, 'label', torch.int32)
+        if label.shape[0] != n:
+            raise ValueError('label must have one entry per item')
+    res = _audit_out(out, [('pred', (n,), torch.int32), ('score', (n,), torch.float32), ('correct', (n,), torch.int32)], vec.device)
+    check(lib.stair_audit_head(weight.shape[0], _ptr(vec), vec.shape[0], _ptr(slot), _ptr(label), _ptr(weight), _ptr(bias), n,
+                               vec.shape[1], *[_ptr(t) for t in res], _stream()))
+    return tuple(res)
+
+
+def audit_rank(vec, slot, reps, k, gold_off=None, gold_cls=None, gold_cls_host=None, out=None):
+    """stair_audit_rank: vec[slot[i]] against the class table reps [n_cls, H] -> (top int32 [n, k], top_sim float32 [n, k],
+    rank int32 [n], best_gold_sim float32 [n]); k is clamped to n_cls.  gold_off int32 [n + 1] / gold_cls int32 on the device
+    (None: no gold, rank 0); gold_cls_host: the host copy (numpy int32) of gold_cls, checked against the table before the launch."""
+    import numpy as np
+    _req(vec, 'vec'); _req(reps, 'reps'); _req(slot, 'slot', torch.int32)
+    if vec.dim() != 2 or reps.dim() != 2 or reps.shape[1] != vec.shape[1]:
+        raise ValueError('vec [rows, H] and reps [n_cls, H] must share H')
+    n, n_cls = slot.shape[0], reps.shape[0]
+    if k < 1:
+        raise ValueError('k must be at least 1')
+    k = min(int(k), n_cls)
+    n_gold = 0
+    if gold_off is not None:
+        _req(gold_off, 'gold_off', torch.int32)
+        if gold_off.shape[0] != n + 1:
+            raise ValueError('gold_off must have n + 1 entries')
+        if gold_cls is not None:
+            _req(gold_cls, 'gold_cls', torch.int32)
+            n_gold = gold_cls.shape[0]
+    host = None
+    if gold_cls_host is not None:
+        host = np.ascontiguousarray(gold_cls_host, dtype=np.int32)
+        if host.size != n_gold:
+            raise ValueError('gold_cls_host must be the host copy of gold_cls')
+    res = _audit_out(out, [('top', (n, k), torch.int32), ('top_sim', (n, k), torch.float32), ('rank', (n,), torch.int32),
+                           ('best_gold_sim', (n,), torch.float32)], vec.device)
+    check(lib.stair_audit_rank(_ptr(vec), vec.shape[0], _ptr(slot), _ptr(reps), n_cls, vec.shape[1], _ptr(gold_off), _ptr(gold_cls),
+                               C.c_void_p(host.ctypes.data if host is not None and host.size else 0), n_gold, n, k,
+                               *[_ptr(t) for t in res], _stream()))
+    return tuple(res)
+
+
 def temporal_relate(att, att_idx, att_k, n, T, mode, conv, ksize, w6):
     """Temporal relate nets; att [rows,T]; returns r [n,T]."""
     _req(att, 'att')
